@@ -1,6 +1,12 @@
 """bench.py -- GFLOPS of C = A*A (CSR, FP64) on MI355X, the BASELINE.json metric.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--matrix NAME] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--matrix NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, the workload).  --dump-outputs DIR also writes the C of the last timed step
+(dump_outputs below).  Everything else this file measures -- roofline, phases, cold call,
+configs, HBM peak, CPU baseline; for N > 1 the one-GPU leg, the other exchange mode and the
+gatherv of C -- runs only with --full, after the timed steps, and adds its blocks to the line.
 
 Workload (BASELINE.json configs[1]): cant.mtx A*A.  The real file is read from
 $MHS_MATRIX_DIR/cant/cant.mtx when present; otherwise the synthetic cant-like
@@ -18,14 +24,15 @@ partitioned by flop, each rank starts with its row block of A (= of B); the
 exchange plan is built once (mhspgemm.distributed.ShardPlan, outside the timed
 steps) and a step is the exchange of B's rows over xGMI (--exchange halo: the
 rows the block references; full: the north_star's allgatherv of every block)
-+ the local SpGEMM; C stays distributed in `value`, and the gatherv of C to rank 0
++ the local SpGEMM; C stays distributed in `value`, and with --full the gatherv of C to rank 0
 is timed beside it (gather_C_ms, value_C_gathered; --no-gather skips it).  Total work is fixed, so scaling is "strong".
 
 One JSON line on rank 0: value = 2*flop / (max over ranks of the time per step).
+The blocks below are written with --full only.
   roofline: the dominant kernel = the numeric phase (every numeric bin launch of a
             call: k_num_wave<10240,true> alone on this workload), timed with
             hipEvents recorded on the launch stream during the timed steps
-            (MHS_OPT_NUMERIC_EVENTS).  achieved = COMPULSORY bytes of that phase
+            (MHS_OPT_NUMERIC_EVENTS, a ring of at most 4096 calls).  achieved = COMPULSORY bytes of that phase
             per call / its average duration: read A once (row_ptr, col, val; B
             aliases A), read C's row_ptr, write C's col and val:
                 B_comp = 8 (M+1) + 12 nnz(A) [+ B's arrays when B != A] + 12 nnz(C)
@@ -78,6 +85,45 @@ NUM_BIN_KERNELS = (["", "k_num_wave_direct<5120>", "k_num_wave_direct<10240>", "
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 # BASELINE.json configs[1..3] beyond the headline (configs[4]'s matrix at 1 GPU) + the perturbed cant
 CONFIG_MATRICES = ["cant", "webbase-1M", "mac_econ_fwd500", "scircuit", "cop20k_A", "cage15", "cant-perturbed"]
+
+
+DUMP_SAMPLE = 1_500_000  # --dump-outputs: entries of C written when C has more
+DUMP_ROWS = 1_000_000    # --dump-outputs: row pointers of C written when C has more
+CONFIG_STEPS = 20        # --full: the configs block times at most this many steps a matrix
+EVENT_RING = 4096        # mhs_ctx_set_option's limit for MHS_OPT_NUMERIC_EVENTS
+
+
+def _sample(n, k):
+    """Every position of range(n) when n <= k, else k sorted positions drawn without replacement
+    by numpy's default_rng(0): the same in every run for the same n."""
+    return np.arange(n) if n <= k else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+
+
+def dump_outputs(dirpath, C):
+    """Write the device CSR `C` (what a caller of the timed path receives) as float64 .npy
+    files under `dirpath`, 60 MB at most (integers up to 2^53 are exact in float64):
+      C_row_index.npy    positions i in C.ptr (0..M): all M+1 when M+1 <= DUMP_ROWS, else a sample
+      C_row_ptr.npy      C.ptr[i]
+      C_val_rowsum.npy   the sum of row i's values (every value of C counts when no row is left
+                         out; 0 for i = M, which starts no row)
+      C_sample_index.npy positions j in C.col / C.val: all when nnz(C) <= DUMP_SAMPLE, else a sample
+      C_col_sample.npy, C_val_sample.npy   C.col[j], C.val[j]
+    Samples are _sample's: fixed by the array length alone."""
+    ptr, col, val = C.to_host()
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    M, nnz = len(ptr) - 1, len(col)
+    rowsum = np.zeros(M + 1)
+    full = np.flatnonzero(np.diff(ptr))  # rows with entries: their segments of val tile it
+    if len(full):
+        rowsum[full] = np.add.reduceat(val, ptr[full])
+    i, j = _sample(M + 1, DUMP_ROWS), _sample(nnz, DUMP_SAMPLE)
+    np.save(d / "C_row_index.npy", i.astype(np.float64))
+    np.save(d / "C_row_ptr.npy", ptr[i].astype(np.float64))
+    np.save(d / "C_val_rowsum.npy", rowsum[i])
+    np.save(d / "C_sample_index.npy", j.astype(np.float64))
+    np.save(d / "C_col_sample.npy", col[j].astype(np.float64))
+    np.save(d / "C_val_sample.npy", val[j].astype(np.float64))
 
 
 def b_alg(M, nnzA, flop, nnzC):
@@ -207,15 +253,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--matrix", default=None,
                     help="default: cant (BASELINE configs[1]) on 1 GPU, cage15 (configs[4], row-sharded) on N > 1")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N=1: after the timed steps, write the C of the last timed step as DIR/<name>.npy "
+                         "(float64; a fixed seeded sample of C's entries when C is large)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and report the roofline, phases, cold call, configs, "
+                         "HBM peak and CPU baseline (N>1: the one-GPU leg, the other exchange mode, the gatherv of C)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full, N=1: skip the CPU baseline")
     ap.add_argument("--no-gather", action="store_true",
-                    help="N>1: skip timing the gatherv of C to rank 0 (timed by default: SURVEY §8(e) asks for "
+                    help="--full, N>1: skip timing the gatherv of C to rank 0 (timed by default: SURVEY §8(e) asks for "
                          "the speed-up with C distributed and with C gathered)")
     ap.add_argument("--exchange", default="full", choices=["halo", "full"],
                     help="N>1: B rows moved per step: every row block (full: the north_star's allgatherv, "
-                         "the headline) or only the referenced rows (halo); the other mode is timed beside it")
-    ap.add_argument("--no-configs", action="store_true", help="N=1: skip the configs block")
+                         "the headline) or only the referenced rows (halo); --full times the other mode beside it")
+    ap.add_argument("--no-configs", action="store_true", help="--full, N=1: skip the configs block")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1, --warmup at least 0")
+    if args.dump_outputs is not None and args.gpus != 1:
+        ap.error("--dump-outputs writes the one-GPU product: use --gpus 1")
 
     # MHS_BENCH_BACKEND=gloo: a rehearsal of the N > 1 path on a one-GPU box (every rank on
     # cuda:0, the exchange over gloo on host tensors) -- never a measurement
@@ -294,29 +350,39 @@ def main():
     if world == 1:
         from mhspgemm import _lib as L
 
-        def time_steps(A, steps, warmup):
-            """Pipelined steps (no per-call host sync; hipEvents around each numeric phase on
-            the launch stream).  Returns (elapsed s, numeric ms list)."""
+        def time_steps(A, steps, warmup, events):
+            """Pipelined steps (no per-call host sync; with `events`, hipEvents around each
+            numeric phase on the launch stream, the last EVENT_RING calls at most).  Each C goes
+            back to the pool before the next call; the last step's C is returned unreleased.
+            Returns (elapsed s, numeric ms list, last C)."""
+            ring = min(steps, EVENT_RING) if events else 0
             tool.set_option(L.MHS_OPT_SYNC, 0)
-            tool.set_option(L.MHS_OPT_NUMERIC_EVENTS, max(1, steps))
+            tool.set_option(L.MHS_OPT_NUMERIC_EVENTS, ring)
             for _ in range(warmup):
                 C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
                 C.release()
             barrier()
             t0 = time.perf_counter()
+            C = None
             for _ in range(steps):
+                if C is not None:
+                    C.release()
                 C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
-                C.release()
             barrier()
             el = time.perf_counter() - t0
-            nms = tool.numeric_ms(steps)
+            nms = tool.numeric_ms(ring) if ring else []
             tool.set_option(L.MHS_OPT_SYNC, 1)
             tool.set_option(L.MHS_OPT_NUMERIC_EVENTS, 0)
-            return el, nms
+            return el, nms, C
 
         A.H2D(local)
-        elapsed, numeric_ms = time_steps(A, args.steps, args.warmup)
+        elapsed, numeric_ms, C = time_steps(A, args.steps, args.warmup, events=args.full)
         t_max = elapsed
+        nnzC = C.nnz
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, C)
+        C.release()
+    if world == 1 and args.full:
         # phase breakdown (reference Timing fields): separate, synchronised calls after
         # the timed region
         for _ in range(5):
@@ -343,8 +409,9 @@ def main():
                 Am, src_m = synth.load_or_synth(m)
                 fm = mhspgemm.flop_count_np(Am.col, Am.ptr)
                 Am.H2D(local)
-                st = max(3, min(args.steps, 10 if Am.M > 1_000_000 else args.steps))
-                el, nms = time_steps(Am, st, max(1, min(args.warmup, 3)))  # >= 1: workspace growth untimed
+                st = max(3, min(args.steps, 10 if Am.M > 1_000_000 else CONFIG_STEPS))
+                el, nms, C = time_steps(Am, st, max(1, min(args.warmup, 3)), events=True)  # >= 1: workspace growth untimed
+                C.release()
                 C, tm = mhspgemm.spgemm(tool, Am, Am, timing=True)
                 C.release()
                 ms = el / st * 1e3
@@ -374,13 +441,13 @@ def main():
             hbm = tool.hbm_peak(2 << 30, 10)
         except Exception as e:  # a diagnostic: never fails the bench
             hbm = {"error": str(e)}
-    else:
+    if world > 1:
         from mhspgemm import distributed as D
         from mhspgemm import _lib as L
-        # the same matrix on ONE GPU first (rank 0, the other ranks wait): the speed-up of
-        # this line is computed on one workload
+        # --full: the same matrix on ONE GPU first (rank 0, the other ranks wait): the speed-up
+        # of this line is computed on one workload
         one_gpu = None
-        if rank == 0:
+        if args.full and rank == 0:
             A1 = mhspgemm.CSR(M_glob, N_glob, np.array(s_ptr), np.array(s_col), np.array(s_val))
             A1.H2D(local)
             t1 = mhspgemm.Tool(local)
@@ -447,12 +514,13 @@ def main():
 
         t_max, (nnzC, xbytes, xrows) = timed(plan)
         log(f"{args.exchange} steps: {t_max / args.steps * 1e3:.3f} ms per step")
-        # the other exchange mode beside it (the north_star's allgatherv when the headline is halo)
+        # --full: the other exchange mode beside it (the north_star's allgatherv when the headline is halo)
         alt_mode = "full" if args.exchange == "halo" else "halo"
-        alt_plan = D.ShardPlan(blk, M_glob, mode=alt_mode)
-        t_alt, (_, alt_bytes, _) = timed(alt_plan)
-        del alt_plan
-        if not args.no_gather:
+        if args.full:
+            alt_plan = D.ShardPlan(blk, M_glob, mode=alt_mode)
+            t_alt, (_, alt_bytes, _) = timed(alt_plan)
+            del alt_plan
+        if args.full and not args.no_gather:
             # gatherv of C's row blocks to rank 0 (the speed-up is reported with C
             # distributed and with C gathered); median of 3, max over ranks
             tool.set_option(L.MHS_OPT_SYNC, 1)
@@ -495,19 +563,21 @@ def main():
         "vs_baseline": None,
         "dtype": "f64",
         "data": "synthetic" if source.startswith("synthetic") else "file",
+        "full": args.full,
         "config": {
             "workload": f"{args.matrix}.mtx A*A ({source}), device-resident A -> device-resident sorted C",
             "matrix": args.matrix, "rows": M_glob, "nnzA": nnzA, "flop": flop, "nnzC": nnzC,
             "parallelism": "single GPU" if N_GPUS == 1 else
                            f"row-sharded x{N_GPUS}, {'full allgatherv (north_star)' if args.exchange == 'full' else 'halo'} "
-                           f"exchange of B's rows in every step (value), {'halo' if args.exchange == 'full' else 'full allgatherv'} "
-                           f"beside it (exchange_alt), C distributed"
+                           f"exchange of B's rows in every step (value), "
+                           + (f"{'halo' if args.exchange == 'full' else 'full allgatherv'} beside it (exchange_alt), "
+                              if args.full else "") + "C distributed"
                            + (" [gloo rehearsal on one GPU: not a measurement]" if backend == "gloo" else ""),
             "memory": "steady-state steps reuse the context's workspace and pooled C buffers "
-                      "(no hipMalloc in a step); cold_call times a fresh context",
+                      "(no hipMalloc in a step)" + ("; cold_call times a fresh context" if args.full else ""),
         },
     }
-    if N_GPUS == 1:
+    if N_GPUS == 1 and args.full:
         avg_num = float(np.mean(numeric_ms))
         bc = b_comp(M_glob, nnzA, nnzC)
         achieved = bc / (avg_num * 1e-3) / 1e9
@@ -571,19 +641,20 @@ def main():
             }
         else:
             out["cpu_baseline"] = None
-    else:
-        out["roofline"] = None
-        out["cpu_baseline"] = None
+    if N_GPUS > 1:
         out["exchange"] = {"mode": args.exchange, "bytes_in_per_step_all_ranks": xbytes,
                            "local_B_rows_all_ranks": xrows, "plan_ms": round(plan_ms, 3),
                            "plan": "distributed flop balance from equal-row blocks (mhspgemm.distributed.rebalance) "
                                    "+ ShardPlan, collectives only, timed once before the steps"}
-        ms_alt = t_alt / args.steps * 1e3
-        out["exchange_alt"] = {"mode": alt_mode, "value": round(2.0 * flop / (ms_alt * 1e-3) / 1e9, 2),
-                               "ms_per_step": round(ms_alt, 4), "bytes_in_per_step_all_ranks": alt_bytes}
         out["dist_backend"] = dist.get_backend()
         out["rccl_world_size"] = dist_world if backend != "gloo" else None
         out["launch"] = os.environ.get("MHS_BENCH_LAUNCH", "external launcher (WORLD_SIZE set)")
+    if N_GPUS > 1 and args.full:
+        out["roofline"] = None
+        out["cpu_baseline"] = None
+        ms_alt = t_alt / args.steps * 1e3
+        out["exchange_alt"] = {"mode": alt_mode, "value": round(2.0 * flop / (ms_alt * 1e-3) / 1e9, 2),
+                               "ms_per_step": round(ms_alt, 4), "bytes_in_per_step_all_ranks": alt_bytes}
         out["single_gpu_same_matrix"] = one_gpu
         out["speedup_vs_1gpu"] = round(one_gpu["ms_per_step"] / ms_per_step, 3)
         if gather_ms is not None:

@@ -1,5 +1,6 @@
 """bench.py's N-rank launch logic (CPU only): `python bench.py --gpus N` without a launcher
-starts N ranks itself, and --gpus beyond the visible GPUs is an error."""
+starts N ranks itself, and --gpus beyond the visible GPUs is an error;
+what --dump-outputs writes (CPU), and a plain run end to end (the one GPU test)."""
 import os
 import subprocess
 import sys
@@ -51,3 +52,88 @@ def test_bare_bench_refuses_more_gpus_than_visible():
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0
     assert "GPU(s) visible" in p.stderr
+
+
+class _HostC:
+    """Stands in for a DeviceCSR: dump_outputs only calls to_host()."""
+
+    def __init__(self, ptr, col, val):
+        self.h = (ptr, col, val)
+
+    def to_host(self):
+        return self.h
+
+
+def test_dump_outputs_writes_whole_small_product_and_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    rng = np.random.default_rng(1)
+    lens = rng.integers(0, 6, 200)
+    lens[[0, 7, 199]] = 0  # empty rows, the last one too
+    ptr = np.zeros(201, np.int32)
+    ptr[1:] = np.cumsum(lens)
+    col = rng.integers(0, 1000, ptr[-1]).astype(np.int32)
+    val = rng.uniform(-1, 1, ptr[-1])
+    C = _HostC(ptr, col, val)
+    bench.dump_outputs(tmp_path / "all", C)
+    got = {f.stem: np.load(f) for f in (tmp_path / "all").iterdir()}
+    assert sorted(got) == ["C_col_sample", "C_row_index", "C_row_ptr", "C_sample_index", "C_val_rowsum",
+                           "C_val_sample"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["C_row_index"], np.arange(201)) and np.array_equal(got["C_row_ptr"], ptr)
+    assert np.array_equal(got["C_sample_index"], np.arange(ptr[-1]))
+    assert np.array_equal(got["C_col_sample"], col) and np.array_equal(got["C_val_sample"], val)
+    rowsum = np.array([val[ptr[i]:ptr[i + 1]].sum() for i in range(200)] + [0.0])
+    assert np.allclose(got["C_val_rowsum"], rowsum, rtol=1e-14, atol=1e-15) and np.all(got["C_val_rowsum"][:200][lens == 0] == 0)
+    # a product larger than the samples: the same sorted positions in every run
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 50)
+    monkeypatch.setattr(bench, "DUMP_ROWS", 30)
+    bench.dump_outputs(tmp_path / "s1", C)
+    bench.dump_outputs(tmp_path / "s2", C)
+    idx = np.load(tmp_path / "s1" / "C_sample_index.npy").astype(np.int64)
+    assert len(idx) == 50 and np.all(np.diff(idx) > 0) and idx[-1] < ptr[-1]
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "C_sample_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "C_col_sample.npy"), col[idx])
+    assert np.array_equal(np.load(tmp_path / "s1" / "C_val_sample.npy"), val[idx])
+    ri = np.load(tmp_path / "s1" / "C_row_index.npy").astype(np.int64)
+    assert len(ri) == 30 and np.all(np.diff(ri) > 0) and ri[-1] <= 200
+    assert np.array_equal(ri, np.load(tmp_path / "s2" / "C_row_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "C_row_ptr.npy"), ptr[ri])
+    assert np.array_equal(np.load(tmp_path / "s1" / "C_val_rowsum.npy"), got["C_val_rowsum"][ri])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_last_C(tmp_path):
+    # a plain run on the small cage4-like matrix: the line holds the headline fields and none
+    # of the --full blocks, and the dumped C is the oracle's (pattern exact, values to 1e-6)
+    import json
+    import numpy as np
+    sys.path[:0] = [str(ROOT / "mh-spgemm_amd")]
+    import mhspgemm
+    from mhspgemm import synth
+    from oracle import oracle as orc
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--matrix", "cage4", "--dump-outputs", str(tmp_path / "d")],
+                       capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "GFLOPS" and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0
+    A = synth.SYNTH["cage4"]()
+    flop = mhspgemm.flop_count_np(A.col, A.ptr)
+    # value = 2 flop / ms_per_step, both rounded in the line (to 0.01 GFLOPS and 1e-4 ms)
+    gflops = 2.0 * flop / (line["ms_per_step"] * 1e-3) / 1e9
+    assert abs(line["value"] - gflops) <= 0.005 + gflops * 0.5e-4 / line["ms_per_step"] + 1e-9
+    for k in ("roofline", "phases_ms", "cold_call", "configs", "hbm_peak", "cpu_baseline"):
+        assert k not in line, k
+    Cp, Ci, Cv = orc.spgemm(A.ptr, A.col, A.val, A.ptr, A.col, A.val, A.N)
+    assert line["config"]["nnzC"] == len(Ci)
+    d = tmp_path / "d"
+    assert np.array_equal(np.load(d / "C_row_index.npy"), np.arange(A.M + 1))
+    assert np.array_equal(np.load(d / "C_row_ptr.npy"), Cp)
+    assert np.array_equal(np.load(d / "C_sample_index.npy"), np.arange(len(Ci)))
+    assert np.array_equal(np.load(d / "C_col_sample.npy"), Ci)
+    ok, *_ = mhspgemm.compare_tol(Cp, Ci, Cv, Cp, Ci, np.load(d / "C_val_sample.npy"), 1e-6, 1e-12)
+    assert ok
+    rs = np.bincount(np.repeat(np.arange(A.M), np.diff(Cp)), weights=Cv, minlength=A.M + 1)
+    assert np.allclose(np.load(d / "C_val_rowsum.npy"), rs, rtol=1e-6, atol=1e-12)

@@ -1,5 +1,5 @@
-"""Per-kernel statistics of the headline part of a `rocprofv3 --kernel-trace --stats -- python3 bench.py`
-run: bench.py times the headline matrix first (warmup + steps pipelined calls, then 5 synchronised
+"""Per-kernel statistics of the headline part of a `rocprofv3 --kernel-trace --stats -- python3 bench.py --full`
+run: bench.py --full times the headline matrix first (warmup + steps pipelined calls, then 5 synchronised
 phase calls and one cold call) and the configs block after it, so the rocprof --stats file mixes
 the configs' launches of the same kernels into its averages.  This splits the kernel trace at the
 first mask launch (k_mask_b / k_mask_lane) past the headline's calls and writes rocprof-style stats of each part.

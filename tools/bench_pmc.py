@@ -3,10 +3,10 @@
 
   python tools/bench_pmc.py <tag> <out dir>
 
-FETCH_SIZE and WRITE_SIZE come from separate --pmc passes of `bench.py --no-cpu --no-configs`
+FETCH_SIZE and WRITE_SIZE come from separate --pmc passes of `bench.py --full --no-cpu --no-configs`
 (the headline's calls only); hbm_bytes_per_launch = (2 * FETCH_SIZE + WRITE_SIZE) KiB * 1024
 (the gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md); avg_us from the kernel trace of the
-default bench command (its headline part, tools/bench_kernel_stats.py)."""
+default `bench.py --full` command (its headline part, tools/bench_kernel_stats.py)."""
 import collections
 import csv
 import glob

@@ -12,6 +12,6 @@ fi
 tail -1 $out/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail -20 $out/smoke.log; exit 1; }
 tail -1 $out/smoke.log
-timeout -k 10 400 python bench.py > $out/bench_default.json 2> $out/bench_default.err || { echo "bench failed"; tail $out/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err || { echo "bench failed"; tail $out/bench_default.err; exit 1; }
 cut -c1-1500 $out/bench_default.json
 echo CHECKDONE

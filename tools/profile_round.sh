@@ -4,7 +4,7 @@
 # usage: tools/profile_round.sh <tag> [bench args]
 export TMPDIR=/tmp
 tag=$1; shift
-args=${*:-"--steps 10 --warmup 2 --no-cpu"}
+args=${*:-"--full --steps 10 --warmup 2 --no-cpu"}
 out=gpurun_out/$tag
 mkdir -p $out
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py $args > $out/trace.log 2>&1 || exit $?

@@ -11,7 +11,7 @@ for m in $mats; do
   i=0
   for p in "${passes[@]}"; do
     i=$((i+1)); d=$out/$m/pmc_$i; mkdir -p $d
-    timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $p --output-format csv -d $d -o run -- python3 bench.py --matrix $m --no-cpu --no-configs > $d.log 2>&1 || { echo "pass $i $m failed"; tail -3 $d.log; exit 1; }
+    timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $p --output-format csv -d $d -o run -- python3 bench.py --full --matrix $m --no-cpu --no-configs > $d.log 2>&1 || { echo "pass $i $m failed"; tail -3 $d.log; exit 1; }
     echo "== $m pass $i ok"
   done
 done
