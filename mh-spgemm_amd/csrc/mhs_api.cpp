@@ -11,7 +11,15 @@
 // The reference makes 5 binning round trips (2 blocking copies each), 3 scalar
 // reads and 6 device-wide syncs per call; here the only host round
 // trip is the single Stats readback that C's allocation needs anyway.
+//
+// On the host, mhs_spgemm checks its arguments and runs spgemm_attempt (again after a
+// speculation miss); an attempt is one Call taken through its phases
+//   plan_workspace -> analyze_rows -> choose_plan -> launch_symbolic -> launch_scan
+//   -> speculate_numeric (phase A of the previous call's plan) -> handoff
+//   -> finish_speculated (phase B, or the miss) -> numeric_after_handoff -> finish_call
+// and C's arrays belong to the Call's owner (mhs_owner.hpp) until finish_call commits.
 #include "mhs_internal.hpp"
+#include "mhs_owner.hpp"
 #include "../../include/mhspgemm.h"
 
 #include <algorithm>
@@ -181,15 +189,6 @@ hipError_t pool_get(mhs_ctx* ctx, void** p, size_t bytes) {
 // The buffer's true size comes from the runtime (not from a side table: a buffer
 // freed with mhs_csr_free and handed out again by hipMalloc at the same address
 // would otherwise be filed under its old size).
-void pool_put(mhs_ctx* ctx, void* p);
-// C.col / C.val back to the pool (C.ptr kept)
-void mhs_ctx_recycle_cols(mhs_ctx* ctx, mhs_csr* out) {
-    pool_put(ctx, out->col);
-    pool_put(ctx, out->val);
-    out->col = nullptr;
-    out->val = nullptr;
-}
-
 void pool_put(mhs_ctx* ctx, void* p) {
     if (!p) return;
     hipDeviceptr_t base = nullptr;
@@ -206,6 +205,22 @@ void pool_put(mhs_ctx* ctx, void* p) {
         ctx->pool.erase(ctx->pool.begin());
     }
 }
+
+// The owner of a call's C arrays (mhs_owner.hpp): released into the pool or freed, after a
+// wait for the call's stream and the aux streams a call forks to.
+struct OwnerOps {
+    static void release(mhs_ctx* ctx, void* p, bool pooled) {
+        if (pooled) pool_put(ctx, p);
+        else if (p) (void)hipFree(p);
+    }
+    static void sync(mhs_ctx* ctx) {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (hipStream_t x : ctx->aux)
+            if (x) (void)hipStreamSynchronize(x);
+        (void)hipGetLastError();
+    }
+};
+using Owner = OutputOwner<mhs_ctx, OwnerOps>;
 
 struct Layout {
     size_t btcol, btmask, bmeta, bhi, rflop, rtflop, rlo, rhi, ctiles, sym_bin, asame, grp, bin_list, scan_part, mcache,
@@ -304,7 +319,7 @@ hipError_t alloc_c(mhs_ctx* ctx, mhs_csr* out, long long nnz) {
 }
 
 // The call's Work over the workspace laid out by `L` (rows of this pass: M).
-Work make_work(mhs_ctx* ctx, const Layout& L, int M, long long nnzA, long long nnzB, int Bn, int mc_list) {
+Work make_work(mhs_ctx* ctx, const Layout& L, int M, long long nnzA, long long nnzB, int mc_list) {
     Work w{};
     w.btcol = (int*)(ctx->ws + L.btcol);
     w.btmask = (unsigned long long*)(ctx->ws + L.btmask);
@@ -320,7 +335,6 @@ Work make_work(mhs_ctx* ctx, const Layout& L, int M, long long nnzA, long long n
     w.grp = (unsigned char*)(ctx->ws + L.grp);
     w.groups = ctx->groups ? 1 : 0;
     w.tiny_num = ctx->tiny_num ? 1 : 0;  // per row: packed sort keys hold its column offsets in 23 bits
-    (void)Bn;
     w.bin_list = (int*)(ctx->ws + L.bin_list);
     w.blkflop = (unsigned long long*)(ctx->ws + L.blkflop);
     w.nflop = M > 0 ? analyze_blocks(nnzA, M) : 0;
@@ -362,6 +376,23 @@ std::string err_text(int err) {
     return m;
 }
 
+// The device-side checks' verdict (Stats::err != 0) as the call's error.
+int fail_stats(mhs_ctx* ctx, int err) {
+    return fail(ctx, (err & ERR_OVERFLOW) ? MHS_ERR_OVERFLOW : MHS_ERR_INVALID, err_text(err));
+}
+
+// mhs_timing's bin counters from per-bin row counts ([0]: the rows in no bin).
+void fill_bins(mhs_timing& tm, int M, const int* sym, const int* num) {
+    static_assert(NBINS <= sizeof tm.sym_bins / sizeof tm.sym_bins[0], "mhs_timing holds every bin");
+    long long ns = 0, nn = 0;
+    for (int i = 1; i < NBINS; ++i) {
+        ns += tm.sym_bins[i] = sym[i];
+        nn += tm.num_bins[i] = num[i];
+    }
+    tm.sym_bins[0] = (int)(M - ns);
+    tm.num_bins[0] = (int)(M - nn);
+}
+
 // Everything before the numeric launches for the rows of `a` (M > 0): (mask of B), row
 // analysis, symbolic bins, row_ptr scan into Cptr[0..M] + numeric bins, the Stats hand-off.
 int front_pass(mhs_ctx* ctx, const Csr& a, const Csr& b, Work& w, int* Cptr, bool mask, Stats& h) {
@@ -383,9 +414,6 @@ int front_pass(mhs_ctx* ctx, const Csr& a, const Csr& b, Work& w, int* Cptr, boo
     ++ctx->front_passes;
     return MHS_OK;
 }
-
-// Global-bin scratch for the numeric pass of `h` (grown on demand).
-int ensure_gscratch(mhs_ctx* ctx, Work& w, const Stats& h);
 
 constexpr int NUM_GLOBAL_GRID = 128;
 #ifndef MHS_MULTI_FLOP_LOG2
@@ -474,6 +502,7 @@ int run_numeric(mhs_ctx* ctx, const Csr& a, const Csr& b, const Work& w, const S
     return MHS_OK;
 }
 
+// Global-bin scratch for the numeric pass of `h` (grown on demand).
 int ensure_gscratch(mhs_ctx* ctx, Work& w, const Stats& h) {
     if (h.num_count[NUM_GLOBAL] <= 0) return MHS_OK;
     const size_t per = (size_t)align16(h.num_global_need);
@@ -545,25 +574,26 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
     long long total = 0;
     unsigned long long flop = 0;
     {
-        int* tptr = nullptr;
-        MHS_HIP(pool_get(ctx, (void**)&tptr, (size_t)(Mc + 1) * 4));
+        Owner tmp(ctx, true);  // a chunk's row_ptr
+        MHS_HIP(pool_get(ctx, (void**)&tmp.out.ptr, (size_t)(Mc + 1) * 4));
+        tmp.queued = true;
         for (int c = 0; c < nch && rc == MHS_OK; ++c) {
             const Csr a = view(c);
-            Work w = make_work(ctx, L, a.M, a.nnz, B->nnz, B->N, mc_list);
-            rc = front_pass(ctx, a, b, w, tptr, c == 0, h);
-            if (rc == MHS_OK && h.err)
-                rc = fail(ctx, (h.err & ERR_OVERFLOW) ? MHS_ERR_OVERFLOW : MHS_ERR_INVALID, err_text(h.err));
+            Work w = make_work(ctx, L, a.M, a.nnz, B->nnz, mc_list);
+            rc = front_pass(ctx, a, b, w, tmp.out.ptr, c == 0, h);
+            if (rc == MHS_OK && h.err) rc = fail_stats(ctx, h.err);
             total += h.nnzC;
             flop += h.flop;
         }
-        pool_put(ctx, tptr);
         if (rc) return rc;
+        tmp.give_back();  // (every pass has been waited for)
     }
     if (total > INT_MAX) return fail(ctx, MHS_ERR_OVERFLOW, "nnz(C) exceeds INT32_MAX");
     // C before the second pass's workspace: it does not depend on the chunking
     const int Mc1 = Mc;
     free_cached(ctx);
-    mhs_csr out{};
+    Owner own(ctx, false);  // (a real free: the pool goes with every cached buffer here)
+    mhs_csr& out = own.out;
     out.M = M;
     out.N = B->N;
     out.nnz = (int)total;
@@ -571,7 +601,6 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
         hipError_t e = pool_get(ctx, (void**)&out.ptr, (size_t)(M + 1) * 4);
         if (e == hipSuccess) e = alloc_c(ctx, &out, total);
         if (e != hipSuccess) {
-            pool_put(ctx, out.ptr);
             free_cached(ctx);
             (void)hipGetLastError();
             return e == hipErrorOutOfMemory ? fail(ctx, MHS_ERR_OOM, "C itself does not fit the device")
@@ -581,25 +610,19 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
     ctx->c_held = (size_t)(M + 1) * 4 + (size_t)total * 12;
     rc = fit_workspace(Mc1);  // (pass 1 fitted Mc1 rows alone; C now sits beside it)
     ctx->c_held = 0;
-    if (rc) {
-        mhs_csr_free(&out);
-        return rc;
-    }
+    if (rc) return rc;
     nch = (M + Mc - 1) / Mc;
     // pass 2: every chunk's rows at their offset
     long long off = 0;
     int sym[NBINS] = {}, num[NBINS] = {};
+    own.queued = true;
     for (int c = 0; c < nch; ++c) {
         const Csr a = view(c);
         const int r0 = c * Mc;
-        Work w = make_work(ctx, L, a.M, a.nnz, B->nnz, B->N, mc_list);
+        Work w = make_work(ctx, L, a.M, a.nnz, B->nnz, mc_list);
         rc = front_pass(ctx, a, b, w, out.ptr + r0, c == 0, h);
         if (rc == MHS_OK) rc = ensure_gscratch(ctx, w, h);
-        if (rc) {
-            (void)hipStreamSynchronize(s);
-            mhs_csr_free(&out);
-            return rc;
-        }
+        if (rc) return rc;
         if (h.nnzC > 0)
             launch_numeric(a, b, w, h, out.ptr + r0, out.col + off, out.val + off, &s, 1, NUM_GLOBAL_GRID,
                            ctx->dense_span_max, false);
@@ -612,27 +635,434 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
         }
     }
     MHS_HIP(hipStreamSynchronize(s));
-    *C = out;
+    own.commit(C);
     ++ctx->chunked_calls;
     if (t) {
         mhs_timing tm{};
         tm.total_e2e = tm.total_ref = ms_since(T0);
         tm.flop = flop;
         tm.nnzC = total;
-        long long ns = 0, nn = 0;
-        for (int i = 1; i < 16; ++i) {
-            tm.sym_bins[i] = i < NBINS ? sym[i] : 0;
-            tm.num_bins[i] = i < NBINS ? num[i] : 0;
-            ns += tm.sym_bins[i];
-            nn += tm.num_bins[i];
-        }
-        tm.sym_bins[0] = (int)(M - ns);
-        tm.num_bins[0] = (int)(M - nn);
+        fill_bins(tm, M, sym, num);
         *t = tm;
     }
     return MHS_OK;
 }
 
+// What the hand-off says about a speculated plan: none launched, the call's own Stats are the
+// plan's, or they are not (the plan's kernels returned at once: k_scan wrote go = 0).
+enum PlanVerdict { PLAN_NONE, PLAN_HIT, PLAN_MISS };
+
+// Phase results beside the MHS_* codes: the row-chunked path has completed the call; the call
+// runs again without speculation.
+enum : int { CALL_DONE = -1, CALL_RERUN = -2 };
+
+// One attempt at C = A * B: the state its phases hand on to each other, in the order they run.
+struct Call {
+    mhs_ctx* const ctx;
+    const mhs_csr *const A, *const B;
+    mhs_csr* const C;
+    mhs_timing* const t;  // (null: no per-phase events)
+    const hipStream_t s;
+    const std::chrono::steady_clock::time_point T0 = std::chrono::steady_clock::now();
+    const Csr a, b;
+    const int M;
+    int mc_list = 0;
+    Layout L{};
+    Work w{};
+    // numeric-first tiny rows: decided by a hand-off of k_analyze's counts (big M), or without one
+    bool probe = false, nft_auto = false;
+    unsigned long long other = 0;  // the probe's count of rows past the tiny classes
+    bool fork_sym = false;   // the rare symbolic bins run on an aux stream
+    bool plannable = false;  // this call's Stats may serve the next call as its plan
+    bool spec = false;       // the previous call's plan is queued ahead of this call's Stats
+    mhs_ctx::PlanKey key{};
+    Stats ph{};  // the plan (a copy: this call replaces the context's)
+    Stats h{};   // this call's own Stats, after the hand-off
+    int seq = 0;            // k_scan's publication
+    bool launched = false;  // the plan's phase A went out
+    PlanVerdict verdict = PLAN_NONE;
+    hipEvent_t nev0 = nullptr, nev1 = nullptr;  // this call's slot of the numeric event ring
+    double t_alloc = 0, t_malloc = 0;
+    hipError_t alloc_err = hipSuccess;  // alloc_c's, from prepare_numeric
+    Owner own;
+
+    Call(mhs_ctx* x, const mhs_csr* A_, const mhs_csr* B_, mhs_csr* C_, mhs_timing* t_)
+        : ctx(x), A(A_), B(B_), C(C_), t(t_), s(x->stream), a{A_->M, A_->N, A_->nnz, A_->ptr, A_->col, A_->val},
+          b{B_->M, B_->N, B_->nnz, B_->ptr, B_->col, B_->val}, M(A_->M), own(x, true) {
+        own.out.M = M;
+        own.out.N = b.N;
+        if (const int nring = (int)ctx->nev.size() / 2) {
+            nev0 = ctx->nev[2 * (ctx->ncalls % nring)];
+            nev1 = ctx->nev[2 * (ctx->ncalls % nring) + 1];
+        }
+    }
+    // the phases, in the order spgemm_attempt runs them
+    int plan_workspace();
+    int analyze_rows();
+    void choose_plan();
+    int launch_symbolic();
+    int launch_scan();
+    int speculate_numeric();
+    int handoff();
+    int finish_speculated();
+    int numeric_after_handoff();
+    int finish_call();
+    // their helpers
+    int go_chunked();
+    int prepare_numeric(const Stats& of, bool* no_room);
+    int run_or_stamp(const Stats& of, int phase);
+    int fill_timing(mhs_timing& tm);
+};
+
+int check_args(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!A || !B || !C) return fail(ctx, MHS_ERR_INVALID, "null argument");
+    if (A->M < 0 || A->N < 0 || A->nnz < 0 || B->M < 0 || B->N < 0 || B->nnz < 0)
+        return fail(ctx, MHS_ERR_INVALID, "negative dimension");
+    if (A->N != B->M)
+        return fail(ctx, MHS_ERR_INVALID, "A.N != B.M (C = A*B needs matching inner dimension)");
+    if ((A->M > 0 && !A->ptr) || (B->M > 0 && !B->ptr) || (A->nnz > 0 && (!A->col || !A->val)) ||
+        (B->nnz > 0 && (!B->col || !B->val)))
+        return fail(ctx, MHS_ERR_INVALID, "null device array");
+    return MHS_OK;
+}
+
+// The call goes on row-chunked (its own C arrays, if any, have been handed back).
+int Call::go_chunked() {
+    const int rc = spgemm_chunked(ctx, A, B, C, t, T0);
+    return rc == MHS_OK ? CALL_DONE : rc;
+}
+
+// ---- mem_alloc: workspace (cached across calls) + C.ptr; zeroed device Stats
+int Call::plan_workspace() {
+    mc_list = ctx->mc_list > 0 ? ctx->mc_list : mc_list_for(M);
+    probe = ctx->tiny_num && ctx->nft_min_m >= 0 && M >= ctx->nft_min_m && M > 0;
+    // numeric-first without the probe (short-row matrices below nft_min_m rows): every tiny row
+    // is sorted once, in symbolic, into slots sized by the per-row bound
+    nft_auto = !probe && M > 0 && ctx->nft_min_m >= 0 && M < ctx->nft_min_m && ctx->tiny_num && ctx->nft_slots &&
+               ctx->nft_auto_avg > 0 && A->nnz < (long long)ctx->nft_auto_avg * M;
+    // near row groups: with the row cache (their C patterns are compared there), not with
+    // the numeric-first probe (big M), and union rows of at most 3 x 32 M values
+    const bool near = ctx->near && ctx->groups && ctx->use_mcache && !probe && !nft_auto && A->nnz <= (1 << 25);
+    const bool same_ab = A->ptr == B->ptr && A->col == B->col && A->val == B->val;
+    L = plan(M, b.M, A->nnz, B->nnz, mc_list, -1, near, near && same_ab);
+    const char* ws_before = ctx->ws;
+    int rc = ensure(ctx, &ctx->ws, &ctx->ws_bytes, L.total);
+    if (rc == MHS_ERR_OOM && near) {  // near groups are an optimisation: drop them before chunking
+        (void)hipGetLastError();
+        L = plan(M, b.M, A->nnz, B->nnz, mc_list, -1, false);
+        rc = ensure(ctx, &ctx->ws, &ctx->ws_bytes, L.total);
+    }
+    if (rc == MHS_ERR_OOM && M > 1) return go_chunked();
+    if (rc) return rc;
+    if (ctx->ws != ws_before) ctx->stats_zero = false;
+    const hipError_t e = pool_get(ctx, (void**)&own.out.ptr, (size_t)(M + 1) * 4);
+    if (e == hipErrorOutOfMemory && M > 1) {
+        (void)hipGetLastError();
+        return go_chunked();
+    }
+    if (e != hipSuccess) return fail_hip(ctx, e, "allocating C.ptr");
+    own.queued = true;  // (every step from here on queues work on C's arrays)
+    w = make_work(ctx, L, M, A->nnz, B->nnz, mc_list);
+    w.near_b = L.near && same_ab;
+    if (L.near) {
+        w.vcheck = B->val;
+        w.vcheck_n = B->nnz;
+    }
+    // device Stats start zeroed: the previous call's k_scan left them so, else a memset
+    if (!ctx->stats_zero) MHS_HIP(hipMemsetAsync(w.stats, 0, sizeof(Stats), s));
+    ctx->stats_zero = false;  // until this call's k_scan has published and cleared them
+    if (M == 0) MHS_HIP(hipMemsetAsync(own.out.ptr, 0, 4, s));
+    t_alloc = ms_since(T0);
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[0], s));
+    return MHS_OK;
+}
+
+// ---- Form_mask_matrix_B, symbolic_binning: the mask of B and k_analyze.  Numeric-first tiny
+// rows (big M): k_analyze also bins the rows that way and counts them (the probe); the host
+// picks the bin lists and sizes the candidates' value slots
+int Call::analyze_rows() {
+    launch_mask_b(b, w, s);
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[1], s));
+    auto slots = [&](size_t n) {  // the value slots of n entries, if they fit
+        if (ensure(ctx, &ctx->slots, &ctx->slots_bytes, n * 12) != MHS_OK) return false;
+        w.nft = 1;
+        w.sc_val = (double*)ctx->slots;
+        w.sc_col = (int*)(ctx->slots + n * 8);
+        return true;
+    };
+    if (probe) w.nft_bin = (unsigned char*)(ctx->ws + L.nft_bin);
+    if (nft_auto) {
+        if (slots((size_t)M * TINY_SLOT_MAX)) w.nft_bin = (unsigned char*)(ctx->ws + L.nft_bin);
+        else (void)hipGetLastError();
+    }
+    const int seq_probe = probe ? ++ctx->seq : 0;
+    launch_analyze(a, w, b.M, s, own.out.ptr, probe ? ctx->d_pub : nullptr, seq_probe);
+    if (probe) {
+        MHS_HIP(hipGetLastError());
+        const int rc = wait_published(ctx, s, ctx->pub, seq_probe);
+        if (rc) return rc;
+        const unsigned long long n = ctx->pub->stats.an_slots;
+        other = ctx->pub->stats.an_other;
+        w.sym_big = other >= (1ull << 21);
+        // slots pay where the tiny rows are (nearly) the whole product: elsewhere numeric's
+        // tiny classes run beside the long rows' kernels anyway (measured: wb-edu-like +10%
+        // with slots, 19% of its rows past the tiny classes; GAP-road- / delaunay-like -12% / -17%)
+        if (!(n > 0 && ctx->nft_slots && other * 100 <= (unsigned long long)M * ctx->nft_other_pct && slots((size_t)n)))
+            (void)hipGetLastError();
+        launch_bin_list(a, w, s);
+    }
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[2], s));
+    return MHS_OK;
+}
+
+// ---- launch plan speculation (SpecArgs): the previous call's numeric plan on the same
+// operands goes out right behind k_scan, checked on the device; not with the numeric-first
+// probe (its own hand-off) or a forked symbolic pass
+void Call::choose_plan() {
+    const bool fork_big = ctx->sym_fork_min_m >= 0 && M >= ctx->sym_fork_min_m;
+    fork_sym = ((w.nft && other > 0) || ctx->sym_fork || fork_big) && ctx->num_streams > 1 && ctx->aux[0];
+    key = {{A->ptr, A->col, A->val, B->ptr, B->col, B->val}, M, b.N, b.M, A->nnz, B->nnz, ctx->gen,
+           L.near, w.nft, mc_list, 0};
+    plannable = ctx->spec && M > 0 && !probe && (!fork_sym || ctx->spec_fork);
+    // (a plan dealt over several streams queues only its call-stream launches ahead of k_scan: see
+    // NumPhase)
+    spec = plannable && ctx->plan_valid && ctx->plan_key == key;
+    ph = ctx->plan_h;
+    // a speculated call whose plan has rows in the rare symbolic bins runs them on an aux stream
+    // beside k_sym_common (their 38 us ran after it on scircuit-like); the plan left them out where
+    // they were empty
+    if (spec && !fork_sym && ctx->spec_fork_rare && ctx->num_streams > 1 && ctx->aux[0] &&
+        (ph.sym_count[SYM_WM] > 0 || ph.sym_count[SYM_B1024] > 0 || ph.sym_count[SYM_GLOBAL] > 0))
+        fork_sym = true;
+    ctx->plan_valid = false;  // (set again by this call's success)
+}
+
+// ---- Calculate_C_nnz: persistent grids that read their bins' sizes on the device: no host
+// round trip.  Forked: rows of the rare bins (long, few) run on an aux stream beside the
+// common bins -- their tail no longer idles the chip
+int Call::launch_symbolic() {
+    int* Cptr = own.out.ptr;
+    const int N = b.N;
+    const Stats* plan_h = spec ? &ph : nullptr;
+    if (fork_sym) {
+        ++ctx->stat[MHS_STAT_SYM_FORK];
+        MHS_HIP(hipEventRecord(ctx->fork_ev, s));
+        if (ctx->fork_common_first) {  // (the call stream's launch first: no host launch ahead of it)
+            launch_symbolic_common(a, b, w, M, N, Cptr, s, plan_h);
+            MHS_HIP(hipStreamWaitEvent(ctx->aux[0], ctx->fork_ev, 0));
+            launch_symbolic_rare(a, w, M, N, Cptr, ctx->aux[0], false);
+        } else {
+            MHS_HIP(hipStreamWaitEvent(ctx->aux[0], ctx->fork_ev, 0));
+            launch_symbolic_rare(a, w, M, N, Cptr, ctx->aux[0], false);
+            launch_symbolic_common(a, b, w, M, N, Cptr, s, plan_h);
+        }
+        launch_symbolic_b256(a, w, M, N, Cptr, s);
+        MHS_HIP(hipEventRecord(ctx->join_ev[0], ctx->aux[0]));
+        MHS_HIP(hipStreamWaitEvent(s, ctx->join_ev[0], 0));
+        launch_near(a, w, Cptr, s);
+    } else {
+        launch_symbolic_common(a, b, w, M, N, Cptr, s, plan_h);
+        // a speculated plan leaves out the rare bins' launches where the plan's bins are empty
+        // (a row in one of them changes the Stats: k_scan rejects the plan, the call reruns)
+        const bool rare = !spec || ph.sym_count[SYM_WM] > 0 || ph.sym_count[SYM_B1024] > 0 ||
+                          ph.sym_count[SYM_GLOBAL] > 0 || (L.near && ph.near_heads > 0);
+        if (rare) launch_symbolic_rare(a, w, M, N, Cptr, s, true);  // (+ near row groups)
+        if (!spec || ph.sym_count[SYM_B256] > 0) launch_symbolic_b256(a, w, M, N, Cptr, s);
+        ctx->stat[MHS_STAT_SPEC_SKIPPED] += (!rare) + (spec && ph.sym_count[SYM_B256] == 0);
+    }
+    MHS_HIP(hipGetLastError());
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[3], s));
+    return MHS_OK;
+}
+
+// ---- numeric_binning: scan, classify, bins.  k_scan publishes the Stats to pinned host
+// memory (no rows: nothing to scan, the zeroed Stats are read back)
+int Call::launch_scan() {
+    if (M > 0) {
+        seq = ++ctx->seq;
+        launch_scan_classify(M, w, own.out.ptr, a.ptr, s, ctx->dense_span_max, ctx->d_pub, seq,
+                             spec ? SpecArgs{ctx->d_go, ph} : SpecArgs{});
+        MHS_HIP(hipGetLastError());
+    } else {
+        MHS_HIP(hipGetLastError());
+        MHS_HIP(hipMemcpyAsync(ctx->h_stats, w.stats, sizeof(Stats), hipMemcpyDeviceToHost, s));
+    }
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[4], s));
+    return MHS_OK;
+}
+
+// ---- Malloc_C_col_val for the numeric pass of `of` (this call's Stats, or the plan's): C.col /
+// C.val, the global-bin scratch, and for near union runs of B (A*A, near groups verified) B's
+// arrays copied in front of the union rows (in the near check instead, for every call with
+// candidates: cant-perturbed-like -1.5 %, cant-s1-like symbolic +5 % -- candidates, no groups).
+// *no_room: C's arrays (alloc_err says why; no message yet: the call may still succeed) or the
+// scratch could not be had, and nothing was queued.
+int Call::prepare_numeric(const Stats& of, bool* no_room) {
+    *no_room = true;
+    alloc_err = alloc_c(ctx, &own.out, of.nnzC);
+    if (alloc_err != hipSuccess) return alloc_err == hipErrorOutOfMemory ? MHS_ERR_OOM : MHS_ERR_HIP;
+    const int rc = ensure_gscratch(ctx, w, of);
+    if (rc) return rc;
+    *no_room = false;
+    if (w.near_b && of.near_verified > 0 && B->nnz > 0) {
+        MHS_HIP(hipMemcpyAsync(w.bx_col, B->col, (size_t)B->nnz * 4, hipMemcpyDeviceToDevice, s));
+        MHS_HIP(hipMemcpyAsync(w.bx_val, B->val, (size_t)B->nnz * 8, hipMemcpyDeviceToDevice, s));
+        w.bx_on = 1;
+    }
+    return MHS_OK;
+}
+
+// ---- Numeric: the launches of `of` in `phase`, or (an empty C) the ring's two events alone
+int Call::run_or_stamp(const Stats& of, int phase) {
+    own.out.nnz = (int)of.nnzC;
+    if (of.nnzC > 0) return run_numeric(ctx, a, b, w, of, own.out, nev0, nev1, phase);
+    if (nev0) {
+        MHS_HIP(hipEventRecord(nev0, s));
+        MHS_HIP(hipEventRecord(nev1, s));
+    }
+    return MHS_OK;
+}
+
+// Phase A of the previous call's plan, queued behind k_scan before its Stats are known.
+int Call::speculate_numeric() {
+    if (!spec) return MHS_OK;
+    const auto T5 = std::chrono::steady_clock::now();
+    bool no_room = false;
+    int rc = prepare_numeric(ph, &no_room);
+    if (no_room) {  // (no room for the plan's C: the hand-off path decides)
+        own.give_back_cols();
+        (void)hipGetLastError();
+        return MHS_OK;
+    }
+    if (rc) return rc;
+    t_malloc = ms_since(T5);
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[5], s));
+    w.go = ctx->d_go;
+    rc = run_or_stamp(ph, NUM_SPEC_A);
+    if (rc) return rc;
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[6], s));
+    launched = true;
+    ++ctx->stat[MHS_STAT_SPEC];
+    return MHS_OK;
+}
+
+// The one host round trip: the host spins on k_scan's sequence number (no stream sync, no
+// interrupt wake-up) and copies the published Stats.
+int Call::handoff() {
+    if (M > 0) {
+        const int rc = wait_published(ctx, s, ctx->pub, seq);
+        if (rc) return rc;
+        memcpy(&h, (const void*)&ctx->pub->stats, sizeof(Stats));
+        ctx->stats_zero = true;  // k_scan's last block cleared them after publishing
+    } else {
+        MHS_HIP(hipStreamSynchronize(s));
+        h = *ctx->h_stats;
+    }
+    return MHS_OK;
+}
+
+// The plan's verdict, decided here and nowhere else.  A hit: the plan's aux-stream launches and
+// joins (phase B).  A miss: every array is rewritten by a call without speculation -- unless the
+// Stats carry an error, which is then the call's result.
+int Call::finish_speculated() {
+    verdict = !launched ? PLAN_NONE : !h.err && stats_same_plan(h, ph) ? PLAN_HIT : PLAN_MISS;
+    if (verdict == PLAN_NONE) return MHS_OK;
+    if (verdict == PLAN_HIT)
+        return ph.nnzC > 0 ? run_numeric(ctx, a, b, w, ph, own.out, nev0, nev1, NUM_SPEC_B) : MHS_OK;
+    MHS_HIP(hipStreamSynchronize(s));
+    own.give_back_cols();
+    ++ctx->stat[MHS_STAT_SPEC_MISS];
+    if (h.err) return MHS_OK;  // (numeric_after_handoff reports it)
+    own.give_back();
+    return CALL_RERUN;  // (plan_valid is false: no speculation)
+}
+
+// The call's own Stats are final: the device-side checks, C's size, the path counters.  Then,
+// unless a plan hit, the ordinary numeric phase sized by them; C beside the full workspace may
+// not fit: the call then goes on with a row-chunked workspace.
+int Call::numeric_after_handoff() {
+    if (h.err) return fail_stats(ctx, h.err);
+    own.out.nnz = (int)h.nnzC;
+    ctx->stat[MHS_STAT_NFT] += w.nft != 0;
+    ctx->stat[MHS_STAT_NEAR] += L.near && h.near_verified > 0;
+    if (verdict == PLAN_HIT) return MHS_OK;
+    const auto T5 = std::chrono::steady_clock::now();
+    bool no_room = false;
+    int rc = prepare_numeric(h, &no_room);
+    if (no_room) {
+        own.give_back();
+        (void)hipGetLastError();
+        if (rc == MHS_ERR_OOM && M > 1) return go_chunked();
+        return alloc_err != hipSuccess ? fail_hip(ctx, alloc_err, "allocating C.col/C.val") : rc;
+    }
+    if (rc) return rc;
+    t_malloc = ms_since(T5);
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[5], s));
+    w.go = nullptr;
+    rc = run_or_stamp(h, NUM_ALL);
+    if (rc) return rc;
+    MHS_HIP(hipGetLastError());
+    if (t) MHS_HIP(hipEventRecord(ctx->ev[6], s));
+    return MHS_OK;
+}
+
+// The reference's per-phase times from the call's events (the stream has been synchronised).
+int Call::fill_timing(mhs_timing& tm) {
+    const int span[5] = {0, 1, 2, 3, 5};  // ev[i] .. ev[i + 1]
+    float ms[5] = {};
+    for (int i = 0; i < 5; ++i) MHS_HIP(hipEventElapsedTime(&ms[i], ctx->ev[span[i]], ctx->ev[span[i] + 1]));
+    tm.mem_alloc = t_alloc;
+    tm.Form_mask_matrix_B = ms[0];
+    tm.symbolic_binning = ms[1];
+    tm.Calculate_C_nnz = ms[2];
+    tm.numeric_binning = ms[3];
+    tm.Malloc_C_col_val = t_malloc;
+    tm.Numeric = ms[4];
+    tm.total_e2e = ms_since(T0);
+    tm.total_ref = tm.total_e2e - tm.Form_mask_matrix_B;
+    tm.flop = h.flop;
+    tm.nnzC = h.nnzC;
+    fill_bins(tm, M, h.sym_count, h.num_count);
+    return MHS_OK;
+}
+
+// Stream sync (unless pipelined), the timing read-out, and only then the commit: C is the
+// caller's and this call's Stats are the next call's plan.
+int Call::finish_call() {
+    ++ctx->ncalls;
+    if (t || ctx->sync) MHS_HIP(hipStreamSynchronize(s));
+    mhs_timing tm{};
+    if (t) {
+        const int rc = fill_timing(tm);
+        if (rc) return rc;
+        *t = tm;
+    }
+    own.commit(C);
+    if (plannable) {  // the next call on these operands may speculate on this call's plan
+        ctx->plan_key = key;
+        ctx->plan_h = h;
+        ctx->plan_valid = true;
+    }
+    return MHS_OK;
+}
+
+// One attempt at the call; CALL_RERUN after a speculation miss.
+int spgemm_attempt(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C, mhs_timing* t) {
+    MHS_HIP(hipSetDevice(ctx->device));
+    Call c(ctx, A, B, C, t);
+    int rc = c.plan_workspace();
+    if (rc == MHS_OK) rc = c.analyze_rows();
+    if (rc == MHS_OK) c.choose_plan();
+    if (rc == MHS_OK) rc = c.launch_symbolic();
+    if (rc == MHS_OK) rc = c.launch_scan();
+    if (rc == MHS_OK) rc = c.speculate_numeric();
+    if (rc == MHS_OK) rc = c.handoff();
+    if (rc == MHS_OK) rc = c.finish_speculated();
+    if (rc == MHS_OK) rc = c.numeric_after_handoff();
+    if (rc == MHS_OK) rc = c.finish_call();
+    return rc == CALL_DONE ? MHS_OK : rc;
+}
 
 }  // namespace
 
@@ -771,367 +1201,11 @@ void mhs_ctx_recycle(mhs_ctx* ctx, mhs_csr* C) {
 }
 
 int mhs_spgemm(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C, mhs_timing* t) {
-    if (!ctx) return MHS_ERR_INVALID;
-    if (!A || !B || !C) return fail(ctx, MHS_ERR_INVALID, "null argument");
-    if (A->M < 0 || A->N < 0 || A->nnz < 0 || B->M < 0 || B->N < 0 || B->nnz < 0)
-        return fail(ctx, MHS_ERR_INVALID, "negative dimension");
-    if (A->N != B->M)
-        return fail(ctx, MHS_ERR_INVALID, "A.N != B.M (C = A*B needs matching inner dimension)");
-    if ((A->M > 0 && !A->ptr) || (B->M > 0 && !B->ptr) || (A->nnz > 0 && (!A->col || !A->val)) ||
-        (B->nnz > 0 && (!B->col || !B->val)))
-        return fail(ctx, MHS_ERR_INVALID, "null device array");
-    MHS_HIP(hipSetDevice(ctx->device));
-    const auto T0 = std::chrono::steady_clock::now();
-    hipStream_t s = ctx->stream;
-    const bool timed = t != nullptr;
-    mhs_timing tm{};
-
-    const int M = A->M, N = B->N, MB = B->M;
-    mhs_csr out{};
-    out.M = M;
-    out.N = N;
-
-    // ---- mem_alloc: workspace (cached across calls) + C.ptr --------------------
-    const int mc_list = ctx->mc_list > 0 ? ctx->mc_list : mc_list_for(M);
-    const bool probe = ctx->tiny_num && ctx->nft_min_m >= 0 && M >= ctx->nft_min_m && M > 0;
-    // numeric-first without the probe (short-row matrices below nft_min_m rows): every tiny row
-    // is sorted once, in symbolic, into slots sized by the per-row bound
-    const bool nft_auto = !probe && M > 0 && ctx->nft_min_m >= 0 && M < ctx->nft_min_m && ctx->tiny_num &&
-                          ctx->nft_slots && ctx->nft_auto_avg > 0 && A->nnz < (long long)ctx->nft_auto_avg * M;
-    // near row groups: with the row cache (their C patterns are compared there), not with
-    // the numeric-first probe (big M), and union rows of at most 3 x 32 M values
-    bool near = ctx->near && ctx->groups && ctx->use_mcache && !probe && !nft_auto && A->nnz <= (1 << 25);
-    const bool same_ab = A->ptr == B->ptr && A->col == B->col && A->val == B->val;
-    Layout L = plan(M, MB, A->nnz, B->nnz, mc_list, -1, near, near && same_ab);
-    const char* ws_before = ctx->ws;
-    int rc = ensure(ctx, &ctx->ws, &ctx->ws_bytes, L.total);
-    if (rc == MHS_ERR_OOM && near) {  // near groups are an optimisation: drop them before chunking
-        (void)hipGetLastError();
-        near = false;
-        L = plan(M, MB, A->nnz, B->nnz, mc_list, -1, false);
-        rc = ensure(ctx, &ctx->ws, &ctx->ws_bytes, L.total);
+    if (const int rc = check_args(ctx, A, B, C)) return rc;
+    for (;;) {  // (a rerun finds plan_valid false: it cannot speculate, so cannot miss again)
+        const int rc = spgemm_attempt(ctx, A, B, C, t);
+        if (rc != CALL_RERUN) return rc;
     }
-    if (rc == MHS_ERR_OOM && M > 1) return spgemm_chunked(ctx, A, B, C, t, T0);
-    if (rc) return rc;
-    if (ctx->ws != ws_before) ctx->stats_zero = false;
-    {
-        const hipError_t e = pool_get(ctx, (void**)&out.ptr, (size_t)(M + 1) * 4);
-        if (e == hipErrorOutOfMemory && M > 1) {
-            (void)hipGetLastError();
-            return spgemm_chunked(ctx, A, B, C, t, T0);
-        }
-        if (e != hipSuccess) return fail_hip(ctx, e, "allocating C.ptr");
-    }
-    Work w = make_work(ctx, L, M, A->nnz, B->nnz, B->N, mc_list);
-    w.near_b = L.near && same_ab;
-    if (L.near) {
-        w.vcheck = B->val;
-        w.vcheck_n = B->nnz;
-    }
-    // device Stats start zeroed: the previous call's k_scan left them so, else a memset
-    if (!ctx->stats_zero) MHS_HIP(hipMemsetAsync(w.stats, 0, sizeof(Stats), s));
-    ctx->stats_zero = false;  // until this call's k_scan has published and cleared them
-    if (M == 0) {
-        MHS_HIP(hipMemsetAsync(out.ptr, 0, 4, s));
-    }
-    const double t_alloc = ms_since(T0);
-    if (timed) MHS_HIP(hipEventRecord(ctx->ev[0], s));
-
-    const Csr a{A->M, A->N, A->nnz, A->ptr, A->col, A->val};
-    const Csr b{B->M, B->N, B->nnz, B->ptr, B->col, B->val};
-
-    // ---- Form_mask_matrix_B ------------------------------------------------------
-    launch_mask_b(b, w, s);
-    if (timed) MHS_HIP(hipEventRecord(ctx->ev[1], s));
-    // ---- symbolic_binning ---------------------------------------------------------
-    // numeric-first tiny rows (big M): k_analyze also bins the rows that way and counts
-    // them; the host picks the bin lists and sizes the candidates' value slots
-    unsigned long long other = 0;
-    if (probe) w.nft_bin = (unsigned char*)(ctx->ws + L.nft_bin);
-    if (nft_auto) {
-        const size_t n = (size_t)M * TINY_SLOT_MAX;
-        if (ensure(ctx, &ctx->slots, &ctx->slots_bytes, n * 12) == MHS_OK) {
-            w.nft_bin = (unsigned char*)(ctx->ws + L.nft_bin);
-            w.nft = 1;
-            w.sc_val = (double*)ctx->slots;
-            w.sc_col = (int*)(ctx->slots + n * 8);
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    const int seq_probe = probe ? ++ctx->seq : 0;
-    launch_analyze(a, w, MB, s, out.ptr, probe ? ctx->d_pub : nullptr, seq_probe);
-    if (probe) {
-        MHS_HIP(hipGetLastError());
-        rc = wait_published(ctx, s, ctx->pub, seq_probe);
-        if (rc) {
-            pool_put(ctx, out.ptr);
-            return rc;
-        }
-        const unsigned long long n = ctx->pub->stats.an_slots;
-        other = ctx->pub->stats.an_other;
-        w.sym_big = other >= (1ull << 21);
-        // slots pay where the tiny rows are (nearly) the whole product: elsewhere numeric's
-        // tiny classes run beside the long rows' kernels anyway (measured: wb-edu-like +10%
-        // with slots, 19% of its rows past the tiny classes; GAP-road- / delaunay-like -12% / -17%)
-        if (n > 0 && ctx->nft_slots && other * 100 <= (unsigned long long)M * ctx->nft_other_pct &&
-            ensure(ctx, &ctx->slots, &ctx->slots_bytes, (size_t)n * 12) == MHS_OK) {
-            w.nft = 1;
-            w.sc_val = (double*)ctx->slots;
-            w.sc_col = (int*)(ctx->slots + (size_t)n * 8);
-        } else {
-            (void)hipGetLastError();
-        }
-        launch_bin_list(a, w, s);
-    }
-    if (timed) MHS_HIP(hipEventRecord(ctx->ev[2], s));
-    // ---- launch plan speculation (SpecArgs): the previous call's numeric plan on the same
-    // operands goes out right behind k_scan, checked on the device; not with the numeric-first
-    // probe (its own hand-off) or a forked symbolic pass
-    const bool fork_big = ctx->sym_fork_min_m >= 0 && M >= ctx->sym_fork_min_m;
-    bool fork_sym = ((w.nft && other > 0) || ctx->sym_fork || fork_big) && ctx->num_streams > 1 && ctx->aux[0];
-    mhs_ctx::PlanKey key{};
-    {
-        const void* ps[6] = {A->ptr, A->col, A->val, B->ptr, B->col, B->val};
-        for (int i = 0; i < 6; ++i) key.p[i] = ps[i];
-        key.M = M;
-        key.N = N;
-        key.MB = MB;
-        key.nnzA = A->nnz;
-        key.nnzB = B->nnz;
-        key.gen = ctx->gen;
-        key.near = L.near;
-        key.nft = w.nft;
-        key.mc_list = mc_list;
-    }
-    const bool plannable = ctx->spec && M > 0 && !probe && (!fork_sym || ctx->spec_fork);
-    // (a plan dealt over several streams queues only its call-stream launches ahead of k_scan: see
-    // NumPhase)
-    const bool spec = plannable && ctx->plan_valid && ctx->plan_key == key;
-    const Stats ph = ctx->plan_h;  // (a copy: this call replaces the plan)
-    // a speculated call whose plan has rows in the rare symbolic bins runs them on an aux stream
-    // beside k_sym_common (their 38 us ran after it on scircuit-like); the plan left them out where
-    // they were empty
-    if (spec && !fork_sym && ctx->spec_fork_rare && ctx->num_streams > 1 && ctx->aux[0] &&
-        (ph.sym_count[SYM_WM] > 0 || ph.sym_count[SYM_B1024] > 0 || ph.sym_count[SYM_GLOBAL] > 0))
-        fork_sym = true;
-    ctx->plan_valid = false;  // (set again by this call's success)
-    // ---- Calculate_C_nnz ------------------------------------------------------------
-    // persistent grids that read their bins' sizes on the device: no host round trip.
-    // Numeric-first: rows of the rare bins (long, few) run on an aux stream beside the
-    // common bins -- their tail no longer idles the chip
-    if (fork_sym) {
-        ++ctx->stat[MHS_STAT_SYM_FORK];
-        MHS_HIP(hipEventRecord(ctx->fork_ev, s));
-        if (ctx->fork_common_first) {  // (the call stream's launch first: no host launch ahead of it)
-            launch_symbolic_common(a, b, w, M, N, out.ptr, s, spec ? &ph : nullptr);
-            MHS_HIP(hipStreamWaitEvent(ctx->aux[0], ctx->fork_ev, 0));
-            launch_symbolic_rare(a, w, M, N, out.ptr, ctx->aux[0], false);
-        } else {
-            MHS_HIP(hipStreamWaitEvent(ctx->aux[0], ctx->fork_ev, 0));
-            launch_symbolic_rare(a, w, M, N, out.ptr, ctx->aux[0], false);
-            launch_symbolic_common(a, b, w, M, N, out.ptr, s, spec ? &ph : nullptr);
-        }
-        launch_symbolic_b256(a, w, M, N, out.ptr, s);
-        MHS_HIP(hipEventRecord(ctx->join_ev[0], ctx->aux[0]));
-        MHS_HIP(hipStreamWaitEvent(s, ctx->join_ev[0], 0));
-        launch_near(a, w, out.ptr, s);
-    } else {
-        launch_symbolic_common(a, b, w, M, N, out.ptr, s, spec ? &ph : nullptr);
-        // a speculated plan leaves out the rare bins' launches where the plan's bins are empty
-        // (a row in one of them changes the Stats: k_scan rejects the plan, the call reruns)
-        const bool rare = !spec || ph.sym_count[SYM_WM] > 0 || ph.sym_count[SYM_B1024] > 0 ||
-                          ph.sym_count[SYM_GLOBAL] > 0 || (L.near && ph.near_heads > 0);
-        if (rare) launch_symbolic_rare(a, w, M, N, out.ptr, s, true);  // (+ near row groups)
-        if (!spec || ph.sym_count[SYM_B256] > 0) launch_symbolic_b256(a, w, M, N, out.ptr, s);
-        ctx->stat[MHS_STAT_SPEC_SKIPPED] += (!rare) + (spec && ph.sym_count[SYM_B256] == 0);
-    }
-    MHS_HIP(hipGetLastError());
-    if (timed) MHS_HIP(hipEventRecord(ctx->ev[3], s));
-    // ---- numeric_binning: scan, classify, bins, one readback ------------------------
-    Stats h;
-    bool launched = false;  // the speculated numeric launches went out
-    double t_malloc = 0;
-    const int nring = (int)ctx->nev.size() / 2;
-    const int slot = nring ? (int)(ctx->ncalls % nring) : 0;
-    if (M > 0) {
-        // the numeric bin offsets kernel publishes Stats to pinned host memory; the
-        // host spins on the sequence number (no stream sync, no interrupt wake-up)
-        const int seq = ++ctx->seq;
-        launch_scan_classify(M, w, out.ptr, a.ptr, s, ctx->dense_span_max, ctx->d_pub, seq,
-                             spec ? SpecArgs{ctx->d_go, ph} : SpecArgs{});
-        MHS_HIP(hipGetLastError());
-        if (timed) MHS_HIP(hipEventRecord(ctx->ev[4], s));
-        if (spec) {
-            const auto T5 = std::chrono::steady_clock::now();
-            hipError_t e = alloc_c(ctx, &out, ph.nnzC);
-            if (e == hipSuccess) {
-                const int g = ensure_gscratch(ctx, w, ph);
-                e = g == MHS_OK ? hipSuccess : hipErrorOutOfMemory;
-                if (g != MHS_OK) mhs_ctx_recycle_cols(ctx, &out);
-            }
-            if (e == hipSuccess) {
-                if (w.near_b && ph.near_verified > 0 && B->nnz > 0) {
-                    MHS_HIP(hipMemcpyAsync(w.bx_col, B->col, (size_t)B->nnz * 4, hipMemcpyDeviceToDevice, s));
-                    MHS_HIP(hipMemcpyAsync(w.bx_val, B->val, (size_t)B->nnz * 8, hipMemcpyDeviceToDevice, s));
-                    w.bx_on = 1;
-                }
-                t_malloc = ms_since(T5);
-                if (timed) MHS_HIP(hipEventRecord(ctx->ev[5], s));
-                w.go = ctx->d_go;
-                if (ph.nnzC > 0) {
-                    out.nnz = (int)ph.nnzC;
-                    rc = run_numeric(ctx, a, b, w, ph, out, nring ? ctx->nev[2 * slot] : nullptr,
-                                     nring ? ctx->nev[2 * slot + 1] : nullptr, NUM_SPEC_A);
-                    if (rc) {
-                        (void)hipStreamSynchronize(s);
-                        mhs_ctx_recycle(ctx, &out);
-                        return rc;
-                    }
-                } else if (nring) {
-                    MHS_HIP(hipEventRecord(ctx->nev[2 * slot], s));
-                    MHS_HIP(hipEventRecord(ctx->nev[2 * slot + 1], s));
-                }
-                if (timed) MHS_HIP(hipEventRecord(ctx->ev[6], s));
-                launched = true;
-                ++ctx->stat[MHS_STAT_SPEC];
-            } else {
-                (void)hipGetLastError();  // (no room for the plan's C: the hand-off path decides)
-            }
-        }
-        rc = wait_published(ctx, s, ctx->pub, seq);
-        if (rc) {
-            if (launched) (void)hipStreamSynchronize(s);
-            if (launched) mhs_ctx_recycle_cols(ctx, &out);
-            pool_put(ctx, out.ptr);
-            return rc;
-        }
-        memcpy(&h, (const void*)&ctx->pub->stats, sizeof(Stats));
-        ctx->stats_zero = true;  // k_scan's last block cleared them after publishing
-        if (launched && !h.err && stats_same_plan(h, ph) && ph.nnzC > 0) {
-            // the plan holds: its aux-stream launches and joins (phase B)
-            rc = run_numeric(ctx, a, b, w, ph, out, nring ? ctx->nev[2 * slot] : nullptr,
-                             nring ? ctx->nev[2 * slot + 1] : nullptr, NUM_SPEC_B);
-            if (rc) {
-                (void)hipStreamSynchronize(s);
-                mhs_ctx_recycle(ctx, &out);
-                return rc;
-            }
-        }
-        if (launched && (h.err || !stats_same_plan(h, ph))) {
-            // the plan was not this call's: its kernels returned at once (k_scan wrote go = 0);
-            // every array is rewritten by a call without speculation
-            MHS_HIP(hipStreamSynchronize(s));
-            mhs_ctx_recycle_cols(ctx, &out);
-            ++ctx->stat[MHS_STAT_SPEC_MISS];
-            if (!h.err) {
-                pool_put(ctx, out.ptr);
-                return mhs_spgemm(ctx, A, B, C, t);  // (plan_valid is false: no speculation)
-            }
-            launched = false;
-        }
-    } else {
-        MHS_HIP(hipGetLastError());
-        MHS_HIP(hipMemcpyAsync(ctx->h_stats, w.stats, sizeof(Stats), hipMemcpyDeviceToHost, s));
-        if (timed) MHS_HIP(hipEventRecord(ctx->ev[4], s));
-        MHS_HIP(hipStreamSynchronize(s));
-        h = *ctx->h_stats;
-    }
-    if (h.err) {
-        pool_put(ctx, out.ptr);
-        return fail(ctx, (h.err & ERR_OVERFLOW) ? MHS_ERR_OVERFLOW : MHS_ERR_INVALID, err_text(h.err));
-    }
-    out.nnz = (int)h.nnzC;
-    ctx->stat[MHS_STAT_NFT] += w.nft != 0;
-    ctx->stat[MHS_STAT_NEAR] += L.near && h.near_verified > 0;
-
-    if (!launched) {
-        // ---- Malloc_C_col_val ---------------------------------------------------------------
-        const auto T5 = std::chrono::steady_clock::now();
-        {
-            const hipError_t e = alloc_c(ctx, &out, out.nnz);
-            if (e != hipSuccess) {
-                pool_put(ctx, out.ptr);
-                (void)hipGetLastError();
-                // C beside the full workspace does not fit: retry with a row-chunked workspace
-                if (e == hipErrorOutOfMemory && M > 1) return spgemm_chunked(ctx, A, B, C, t, T0);
-                return fail_hip(ctx, e, "allocating C.col/C.val");
-            }
-        }
-        rc = ensure_gscratch(ctx, w, h);
-        // near union runs of B (A*A, near groups verified): B's arrays copied in front of the union
-        // rows (in the near check instead, for every call with candidates: cant-perturbed-like -1.5 %,
-        // cant-s1-like symbolic +5 % -- candidates, no groups)
-        if (rc == MHS_OK && w.near_b && h.near_verified > 0 && B->nnz > 0) {
-            MHS_HIP(hipMemcpyAsync(w.bx_col, B->col, (size_t)B->nnz * 4, hipMemcpyDeviceToDevice, s));
-            MHS_HIP(hipMemcpyAsync(w.bx_val, B->val, (size_t)B->nnz * 8, hipMemcpyDeviceToDevice, s));
-            w.bx_on = 1;
-        }
-        if (rc) {
-            mhs_ctx_recycle(ctx, &out);
-            (void)hipGetLastError();
-            if (rc == MHS_ERR_OOM && M > 1) return spgemm_chunked(ctx, A, B, C, t, T0);
-            return rc;
-        }
-        t_malloc = ms_since(T5);
-
-        // ---- Numeric -------------------------------------------------------------------------
-        if (timed) MHS_HIP(hipEventRecord(ctx->ev[5], s));
-        w.go = nullptr;
-        if (out.nnz > 0) {
-            rc = run_numeric(ctx, a, b, w, h, out, nring ? ctx->nev[2 * slot] : nullptr,
-                             nring ? ctx->nev[2 * slot + 1] : nullptr);
-            if (rc) {
-                mhs_ctx_recycle(ctx, &out);
-                return rc;
-            }
-        } else if (nring) {
-            MHS_HIP(hipEventRecord(ctx->nev[2 * slot], s));
-            MHS_HIP(hipEventRecord(ctx->nev[2 * slot + 1], s));
-        }
-        MHS_HIP(hipGetLastError());
-        if (timed) MHS_HIP(hipEventRecord(ctx->ev[6], s));
-    }
-    ++ctx->ncalls;
-    if (timed || ctx->sync) MHS_HIP(hipStreamSynchronize(s));
-    *C = out;
-    if (plannable) {  // the next call on these operands may speculate on this call's plan
-        ctx->plan_key = key;
-        ctx->plan_h = h;
-        ctx->plan_valid = true;
-    }
-
-    if (timed) {
-        float f = 0;
-        tm.mem_alloc = t_alloc;
-        MHS_HIP(hipEventElapsedTime(&f, ctx->ev[0], ctx->ev[1]));
-        tm.Form_mask_matrix_B = f;
-        MHS_HIP(hipEventElapsedTime(&f, ctx->ev[1], ctx->ev[2]));
-        tm.symbolic_binning = f;
-        MHS_HIP(hipEventElapsedTime(&f, ctx->ev[2], ctx->ev[3]));
-        tm.Calculate_C_nnz = f;
-        MHS_HIP(hipEventElapsedTime(&f, ctx->ev[3], ctx->ev[4]));
-        tm.numeric_binning = f;
-        tm.Malloc_C_col_val = t_malloc;
-        MHS_HIP(hipEventElapsedTime(&f, ctx->ev[5], ctx->ev[6]));
-        tm.Numeric = f;
-        tm.total_e2e = ms_since(T0);
-        tm.total_ref = tm.total_e2e - tm.Form_mask_matrix_B;
-        tm.flop = h.flop;
-        tm.nnzC = h.nnzC;
-        for (int i = 0; i < 16; ++i) {
-            tm.sym_bins[i] = i < NBINS ? h.sym_count[i] : 0;
-            tm.num_bins[i] = i < NBINS ? h.num_count[i] : 0;
-        }
-        long long nonempty = 0;
-        for (int i = 1; i < NBINS; ++i) nonempty += h.sym_count[i];
-        tm.sym_bins[0] = (int)(M - nonempty);
-        nonempty = 0;
-        for (int i = 1; i < NBINS; ++i) nonempty += h.num_count[i];
-        tm.num_bins[0] = (int)(M - nonempty);
-        *t = tm;
-    }
-    return MHS_OK;
 }
 
 int mhs_transpose(mhs_ctx* ctx, const mhs_csr* A, mhs_csr* At) {

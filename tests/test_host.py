@@ -31,6 +31,18 @@ def test_library_exports_every_declared_symbol():
     assert L.mhs_abi_version() == 10
 
 
+def test_output_owner_under_sanitizers(tmp_path):
+    # the owner of a call's C arrays (csrc/mhs_owner.hpp) has no HIP in it: tests/owner_check.cpp runs
+    # commit, early exits with and without queued work, the miss hand-back and double release on the host
+    exe = tmp_path / "owner_check"
+    cc = subprocess.run(["c++", "-std=c++17", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                         "-fno-sanitize-recover=all", str(ROOT / "tests" / "owner_check.cpp"), "-o", str(exe)],
+                        capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout.strip() == "owner ok", run.stdout + run.stderr
+
+
 def test_vendor_library_exports_every_declared_symbol():
     # rocSPARSE comparison row (include/mhs_vendor.h): loads without a GPU, exports its two entries
     V = _lib.vendor_lib()
