@@ -89,8 +89,7 @@ struct mhs_ctx {
     hipStream_t aux[NAUX] = {};
     hipEvent_t fork_ev = nullptr, join_ev[NAUX] = {};
     hipEvent_t split_ev = nullptr;  // k_split_bins done (the split block launches wait for it)
-    bool split_on = false;          // a speculated plan's phase A split its block bins (phase B's launches)
-    // launch plan speculation (SpecArgs, mhs_internal.hpp): the last hand-off's Stats and the
+    // launch plan speculation (SpecArgs, mhs_shape.hpp): the last hand-off's Stats and the
     // operands they belong to; MHS_NO_SPEC=1 turns it off
     struct PlanKey {
         const void* p[6];
@@ -440,8 +439,13 @@ int numeric_streams(const mhs_ctx* ctx, const Stats& h) {
 // it complete -- waits on a pending one measured slower than the whole hand-off, r06b) and joins.
 enum NumPhase { NUM_ALL = 0, NUM_SPEC_A = 1, NUM_SPEC_B = 2 };
 
+NumShape num_shape(const Csr& a, const Csr& b, const Work& w, bool split) {
+    return NumShape{a.M, a.nnz, b.nnz, w.bx_on, w.sc_col != nullptr, split, NUM_GLOBAL_GRID};
+}
+
+// `plan`: built by the phase that runs first (ALL, SPEC_A) and kept by the caller for SPEC_B.
 int run_numeric(mhs_ctx* ctx, const Csr& a, const Csr& b, const Work& w, const Stats& h, const mhs_csr& out,
-                hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int phase = NUM_ALL) {
+                NumPlan& plan, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, int phase = NUM_ALL) {
     hipStream_t s = ctx->stream;
     // several heavy bins: deal them over the aux streams (fork/join costs ~10-20 us,
     // so only when there are at least 3 launches of a product worth it)
@@ -449,43 +453,55 @@ int run_numeric(mhs_ctx* ctx, const Csr& a, const Csr& b, const Work& w, const S
     int nss = numeric_streams(ctx, h);
     if (w.go) nss = std::min(nss, ctx->spec_nss);  // (MHS_SPEC_NSS: a speculated plan on fewer streams)
     for (int i = 1; i < nss; ++i) ss[i] = ctx->aux[i - 1];
-    hipError_t fe = hipSuccess;
     const bool first = phase != NUM_SPEC_B, last = phase != NUM_SPEC_A;
     if (phase == NUM_SPEC_B && nss == 1) return MHS_OK;  // (phase A launched everything)
     if (first && nss > 1 && ev0) MHS_HIP(hipEventRecord(ev0, s));  // (several streams: events of their own)
     if (first && nss > 1) MHS_HIP(hipEventRecord(ctx->fork_ev, s));
-    // the aux streams wait for the fork (everything before numeric) -- set up after the first
-    // numeric launch has gone out on the call's stream (launch_numeric)
-    auto fork = [&]() {
-        for (int i = 1; i < nss && fe == hipSuccess; ++i) fe = hipStreamWaitEvent(ss[i], ctx->fork_ev, 0);
-        return fe == hipSuccess;
-    };
     // block bins split by LDS need only where their two launches can run side by side (on
     // one stream the hub rows' launch would no longer overlap the others' bulk).  The partition
     // runs on the call's stream after the fork: only the split launches wait for it (split_ev),
     // the other bins start at once (wb-edu-like: 0.33 ms off the numeric phase's start)
     // (and only from 2^MHS_SPLIT_FLOP_LOG2 products: on scircuit-like the partition and its event
     // wait cost more than the split saves -- numeric 0.146 -> 0.119 ms unsplit)
-    const bool want_split = nss > 1 && ctx->split && h.flop >= (1ull << MHS_SPLIT_FLOP_LOG2);
-    bool split = false;
     if (first) {
-        split = want_split && launch_split_bins(w, h, a.M, out.ptr, s, ctx->dense_span_max);
+        const bool want_split = nss > 1 && ctx->split && h.flop >= (1ull << MHS_SPLIT_FLOP_LOG2);
+        const bool split = want_split && launch_split_bins(w, h, a.M, out.ptr, s, ctx->dense_span_max);
         if (split) MHS_HIP(hipEventRecord(ctx->split_ev, s));
-        ctx->split_on = split;
         ctx->stat[MHS_STAT_SPLIT] += split;
         ctx->stat[MHS_STAT_MULTI_STREAM] += nss > 1;
-    } else {
-        split = ctx->split_on;  // (phase A's decision)
+        plan = plan_numeric(h, num_shape(a, b, w, split));
     }
-    const int only = phase == NUM_SPEC_A ? 1 : phase == NUM_SPEC_B ? ~1 : ~0;
-    const int used = launch_numeric(a, b, w, h, out.ptr, out.col, out.val, ss, nss, NUM_GLOBAL_GRID,
-                                    ctx->dense_span_max, split, split ? ctx->split_ev : nullptr,
-                                    nss > 1 ? std::function<bool()>(fork) : std::function<bool()>(),
-                                    nss == 1 ? ev0 : nullptr, nss == 1 ? ev1 : nullptr, only);
-    if (nss == 1 && (used & (1 << 30))) {  // (no launch carried them)
+    // Launch i on ss[stream_of(i, nss)]; a speculated plan's phase A issues the call stream's share,
+    // phase B the rest.  The aux streams wait for the fork event (everything before numeric): waits
+    // set up once, right before the first launch that lands on an aux stream -- after launch 0 has
+    // gone out on the call's stream (host API calls that would otherwise sit between the hand-off and
+    // the first numeric kernel: round 5, scircuit-like's hand-off gap).  A failed wait sends every
+    // later launch to ss[0]: no aux-stream launch may run without its dependency on the pre-numeric
+    // work.  On one stream the timing events ride on the first and the last dispatch.
+    const NumPointers np{a, b, w, out.ptr, out.col, out.val, ctx->dense_span_max};
+    hipError_t fe = hipSuccess;
+    bool forked = false;
+    int used = 0;  // streams launched on (bit k: ss[k])
+    auto fork = [&]() {
+        forked = true;
+        for (int i = 1; i < nss && fe == hipSuccess; ++i) fe = hipStreamWaitEvent(ss[i], ctx->fork_ev, 0);
+    };
+    for (int i = 0; i < plan.n; ++i) {
+        const NumLaunch& l = plan.launch[i];
+        const int dealt = stream_of(i, nss);
+        if (phase == NUM_SPEC_A ? dealt != 0 : phase == NUM_SPEC_B && dealt == 0) continue;
+        if (dealt != 0 && !forked) fork();
+        const int k = fe == hipSuccess ? dealt : 0;
+        used |= 1 << k;
+        if (l.after_split && k != 0) (void)hipStreamWaitEvent(ss[k], ctx->split_ev, 0);  // (k_split_bins' lists)
+        issue_numeric(l, plan.o32, np, ss[k], nss == 1 && i == 0 ? ev0 : nullptr,
+                      nss == 1 && i + 1 == plan.n ? ev1 : nullptr);
+    }
+    if (nss == 1 && plan.n == 0) {  // (no launch to carry them)
         if (ev0) MHS_HIP(hipEventRecord(ev0, s));
         if (ev1) MHS_HIP(hipEventRecord(ev1, s));
     }
+    if (!forked && nss > 1 && last) fork();  // (nothing dealt to an aux stream: the error check below expects the waits)
     if (!last) {
         MHS_HIP(hipGetLastError());
         return MHS_OK;
@@ -623,9 +639,11 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
         rc = front_pass(ctx, a, b, w, out.ptr + r0, c == 0, h);
         if (rc == MHS_OK) rc = ensure_gscratch(ctx, w, h);
         if (rc) return rc;
-        if (h.nnzC > 0)
-            launch_numeric(a, b, w, h, out.ptr + r0, out.col + off, out.val + off, &s, 1, NUM_GLOBAL_GRID,
-                           ctx->dense_span_max, false);
+        if (h.nnzC > 0) {
+            const NumPlan p = plan_numeric(h, num_shape(a, b, w, false));
+            const NumPointers np{a, b, w, out.ptr + r0, out.col + off, out.val + off, ctx->dense_span_max};
+            for (int i = 0; i < p.n; ++i) issue_numeric(p.launch[i], p.o32, np, s, nullptr, nullptr);
+        }
         launch_add_offset(out.ptr + r0, a.M + (c == nch - 1 ? 1 : 0), (int)off, s);
         MHS_HIP(hipGetLastError());
         off += h.nnzC;
@@ -678,6 +696,7 @@ struct Call {
     mhs_ctx::PlanKey key{};
     Stats ph{};  // the plan (a copy: this call replaces the context's)
     Stats h{};   // this call's own Stats, after the hand-off
+    NumPlan nplan{};  // the numeric launches (a speculated call: built by phase A, finished by phase B)
     int seq = 0;            // k_scan's publication
     bool launched = false;  // the plan's phase A went out
     PlanVerdict verdict = PLAN_NONE;
@@ -916,7 +935,7 @@ int Call::prepare_numeric(const Stats& of, bool* no_room) {
 // ---- Numeric: the launches of `of` in `phase`, or (an empty C) the ring's two events alone
 int Call::run_or_stamp(const Stats& of, int phase) {
     own.out.nnz = (int)of.nnzC;
-    if (of.nnzC > 0) return run_numeric(ctx, a, b, w, of, own.out, nev0, nev1, phase);
+    if (of.nnzC > 0) return run_numeric(ctx, a, b, w, of, own.out, nplan, nev0, nev1, phase);
     if (nev0) {
         MHS_HIP(hipEventRecord(nev0, s));
         MHS_HIP(hipEventRecord(nev1, s));
@@ -969,7 +988,7 @@ int Call::finish_speculated() {
     verdict = !launched ? PLAN_NONE : !h.err && stats_same_plan(h, ph) ? PLAN_HIT : PLAN_MISS;
     if (verdict == PLAN_NONE) return MHS_OK;
     if (verdict == PLAN_HIT)
-        return ph.nnzC > 0 ? run_numeric(ctx, a, b, w, ph, own.out, nev0, nev1, NUM_SPEC_B) : MHS_OK;
+        return ph.nnzC > 0 ? run_numeric(ctx, a, b, w, ph, own.out, nplan, nev0, nev1, NUM_SPEC_B) : MHS_OK;
     MHS_HIP(hipStreamSynchronize(s));
     own.give_back_cols();
     ++ctx->stat[MHS_STAT_SPEC_MISS];

@@ -25,6 +25,8 @@
 // wave, no block barriers), block-per-row kernels (256 / 1024 threads, up to 160 KiB
 // of LDS) and a global-memory fallback; rows are walked in XCD-grouped order so that
 // neighbouring rows (which share B rows) run on one XCD's L2.
+// Which numeric kernels a call launches, with which grids and LDS, is plan_numeric
+// (mhs_numplan.hpp); issue_numeric, at the end of this file, launches one entry of that plan.
 #include "mhs_internal.hpp"
 
 #include <hip/hip_ext.h>
@@ -32,9 +34,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
-#include <functional>
 #include <type_traits>
-#include <vector>
 
 #ifndef MHS_ROW_STAMPS
 #define MHS_ROW_STAMPS 0  // 1: tools/diag/stamps*.py builds -- per-row, per-phase s_memtime cycles
@@ -44,21 +44,13 @@ constexpr int MHS_RUN_UNROLL = 2;  // B entries per lane issued together in a ru
 constexpr int MHS_TILE_UNROLL = 2;  // tiles per lane issued together in a tile walk
 constexpr int MHS_UNROLL = 4;  // B entries per lane issued together in the product walk
 constexpr int MHS_UNROLL_BLOCK = 8;  // ... in the block kernels (measured: S1-like rows -9%; the wave kernels keep 4)
-constexpr int MHS_NUM_WS_GRID = 4096;  // block cap of the small-row grouped numeric launch
-constexpr int MHS_TINY64_GRID = 4096;  // block cap of the 64-lane tiny numeric launches (8192: wb-edu-like +6 %)
-constexpr int MHS_NUM_W16H_GRID = 2048;  // block cap of the 10 KiB hash launch (4096: neutral at 16 KiB, profiles/r02za2_grid)
 // block cap of each numeric-first symbolic tiny class: 4096, 16384 from 4 M rows (r05ab17/18:
 // delaunay-like 10.26 -> 9.70 ms, GAP-road-like 4.53 -> 4.43 at 16384, but mac_econ-, scircuit-like
 // +5-6 %; 512-2048 slower on every huge matrix, delaunay-like up to 19 ms)
-constexpr int MHS_COPY_CAP_BIG = 65536;  // the slot copy's block cap from 4 M rows (16384 below; delaunay-like -1 %, r05ab19)
-constexpr int MHS_NFT_GRID = 4096, MHS_NFT_GRID_BIG = 16384, MHS_NFT_BIG_M = 1 << 22;
+constexpr int MHS_NFT_GRID = 4096, MHS_NFT_GRID_BIG = 16384;  // (from MHS_NFT_BIG_M rows)
 constexpr int MHS_TINY_PF = 1;  // tiny teams load their next row a round ahead (GAP-road-like -3 %, mac_econ-, scircuit-like -1 %)
 constexpr int MHS_SYM_WAVE_GRID = 2048;  // block cap of k_sym_common's wave rows (65536: cage15-like -3 %, cop20k-, webbase-, mac_econ-like +5 %)
 constexpr int MHS_SYM_WAVE_GRID_BIG = 65536;  // ... when the probe counted >= 2^21 table rows (Work::sym_big)
-constexpr int MHS_NUM_WSH_BIG = (1 << 21);  // small hash bins of at least this many rows: block cap MHS_NUM_WSH_BIG_GRID
-constexpr int MHS_NUM_WSH_BIG_GRID = 65536;  // (cage15-like -2.5 % over 16384; 65536 for every bin: offshore-, webbase-like +1.5 %)
-constexpr int MHS_NUM_WSX_GRID = 16384;  // ... of the small-row hash / direct launches (8192: cage15-like numeric +4.5 %, 4096: +13 %,
-                                         // cant-perturbed +5 %; the grouped launch: 8192 measured +1.4 % on cant-like)
 constexpr int MHS_VAL_GMIN = 4;  // narrowest lane group of a value walk
 constexpr int MHS_TILE_GMIN = 4;  // narrowest lane group of a tile walk
 constexpr int MHS_RUN_GMIN = 8;  // narrowest lane group of a chunk with merged runs (32 before: see DESIGN §8)
@@ -527,7 +519,6 @@ struct RowWalk {
 constexpr int MHS_GRP_CHUNK = 63;  // A entries staged per chunk in the grouped walk (<= 64)
 static_assert(MHS_GRP_CHUNK >= 1 && MHS_GRP_CHUNK <= 64, "a chunk is one entry per lane");
 constexpr int MHS_SYMWM_DYN_MAX = 32768;  // k_sym_rare's 10 KiB wave rows from the cursors up to this many rows
-constexpr int MHS_DYN16_MAX = 32768;  // hash 10 KiB bins of at most this many rows: all rows from the cursor
 constexpr int MHS_GUIDED_STATIC = 4;  // eighths of an XCD group's rows walked statically before the cursor
 // Dynamic XCD-grouped walk: group g = blockIdx % 8 (an XCD under round-robin dispatch) owns
 // the g-th eighth of the list; its waves take CH consecutive entries at a time from the
@@ -4167,12 +4158,6 @@ __global__ __launch_bounds__(256) MHS_WPE_ATTR(MHS_WPE_TINY) void k_tiny_num(Tin
 
 // The 32-lane-or-narrower numeric tiny classes in one launch: class f.c[k] takes blocks
 // [f.blk0[k], f.blk0[k+1]) (sizes known on the host; multiples of 8 keep the XCD walk).
-struct TinyFused {
-    int nclass;
-    int c[4];
-    int count[4];
-    int blk0[5];
-};
 __global__ __launch_bounds__(256) MHS_WPE_ATTR(8) void k_tiny_num_small(TinyArgs a, TinyFused f) {
     MHS_PLAN_GUARD(a);
     int k = 0;
@@ -4206,7 +4191,7 @@ __device__ __forceinline__ void tiny_sym_rows(TinyArgs a, int blk) {
     }
     static_assert(TINY_NC == 6 && TINY_SYM_NC == 4 && tiny_ws(3) <= 32 && tiny_w(3) <= 32 && tiny_w(4) == 64 &&
                       tiny_w(5) == 64 && tiny_ws(4) == 64,
-                  "k_tiny_sym / launch_tiny_num instantiate the classes of tiny_class()");
+                  "k_tiny_sym / issue_numeric instantiate the classes of tiny_class()");
     a.bin = SYM_TINY + c;
     a.list += (long long)c * a.M;
     if (c == 4) {  // the scattered class counts only, in either mode
@@ -4245,7 +4230,6 @@ struct CopyArgs {
     double* Cval;
     const int* go;
 };
-static int copy_lanes(int c) { return c == 0 ? 4 : c == 1 ? 8 : c == 2 ? 16 : 32; }
 
 // In row order: L lanes per row over every row of A, slot rows only (tslot >= 0; k_scan
 // marks the others): a wave's stores cover consecutive C rows and its loads consecutive
@@ -4319,12 +4303,6 @@ static int pick_group(long long nnz, int rows, int gmax = 64) {
     int g = MHS_ROW_GMIN;
     while (g < avg && g < gmax) g <<= 1;
     return g;
-}
-
-static int round8(long long x, int cap) {
-    long long g = x < cap ? x : cap;
-    if (g < 8) g = 8;
-    return (int)((g + 7) / 8 * 8);
 }
 
 // Must run on every call, even when B is unchanged: it rewrites all of bmeta, and k_scan
@@ -4480,37 +4458,6 @@ size_t sym_global_bytes_per_block(int N) {
     return (size_t)hash_slots(span_max) * 16;
 }
 
-// Numeric launches: the numeric-phase events (MHS_OPT_NUMERIC_EVENTS) ride on the first and last
-// dispatch packet of a single-stream numeric phase (hipExtLaunchKernel) instead of event records
-// of their own between the kernels -- each record measured ~5 us of idle before the next kernel
-// (pipelined cant-like steps, r06b timelines).  launch_numeric sets them for the launch at hand.
-namespace {
-thread_local hipEvent_t t_num_start = nullptr, t_num_stop = nullptr;
-}
-template <typename F, typename... Args>
-static void num_launch(F kernel, const dim3& g, const dim3& b, unsigned lds, hipStream_t s, Args... args) {
-    hipEvent_t e0 = t_num_start, e1 = t_num_stop;
-    t_num_start = t_num_stop = nullptr;
-    if (e0 || e1) hipExtLaunchKernelGGL(kernel, g, b, lds, s, e0, e1, 0u, args...);
-    else hipLaunchKernelGGL(kernel, g, b, lds, s, args...);
-}
-
-// Numeric tiny class c, `rows` rows.
-static void launch_tiny_num(int c, int rows, const TinyArgs& t, hipStream_t s) {
-#define MHS_TINY(WW, KK)                                                                                  \
-    num_launch((k_tiny_num<WW, KK>), dim3(round8((rows + 256 / (WW) - 1) / (256 / (WW)), MHS_TINY64_GRID)), \
-                       dim3(256), 256 * (KK) * 8, s, t)
-    switch (c) {
-    case 0: MHS_TINY(tiny_w(0), tiny_k(0)); break;
-    case 1: MHS_TINY(tiny_w(1), tiny_k(1)); break;
-    case 2: MHS_TINY(tiny_w(2), tiny_k(2)); break;
-    case 3: MHS_TINY(tiny_w(3), tiny_k(3)); break;
-    case 4: MHS_TINY(tiny_w(4), tiny_k(4)); break;
-    default: MHS_TINY(tiny_w(5), tiny_k(5)); break;
-    }
-#undef MHS_TINY
-}
-
 static SymArgs sym_args(const Csr& A, const Work& w, int M, int N, int* Cptr) {
     SymArgs a;
     a.M = M;
@@ -4661,30 +4608,6 @@ void launch_scan_classify(int M, const Work& w, int* Cptr, const int* Aptr, hipS
 #undef MHS_SCAN
 }
 
-// Dynamic LDS of a block-kernel launch: the header plus its largest row's tables, in
-// 2 KiB steps, at most the bin's budget.
-static int block_lds(int need, int budget, int T) {
-    if (need <= 0) return budget;
-    const int b = (block_hdr(T) + need + 2047) & ~2047;
-    return b < budget ? b : budget;
-}
-
-// A block bin runs as two launches when it holds rows on both sides of its LDS split.
-static bool block_split_on(const Stats& h, int k) {
-    const int bin = k ? NUM_B1024 : NUM_B256;
-    return h.num_block_big[k] > 0 && h.num_block_big[k] < h.num_count[bin];
-}
-
-int numeric_launches(const Stats& h) {
-    int n = 0, small = 0;
-    for (int b = 1; b < NUM_NB; ++b) {
-        if (h.num_count[b] <= 0) continue;
-        if (b >= NUM_TINY && b < NUM_TINY + 4) small = 1;
-        else ++n;
-    }
-    return n + small + block_split_on(h, 0) + block_split_on(h, 1);
-}
-
 // Partition of the split block bins' lists (one 1024-thread block per bin): rows at or below
 // the bin's LDS split from the front of its part of w.split_list, hub rows from the back
 // (a ballot and one LDS counter add per wave; order within a wave kept).
@@ -4768,36 +4691,41 @@ bool launch_split_bins(const Work& w, const Stats& h, int M, const int* Cptr, hi
     return true;
 }
 
-// Numeric launches of the non-empty bins, largest rows first, dealt round-robin over nss streams
-// (launch i on ss[(i + 1) % nss], so the last, bulk wave bins tend to stay on ss[0]): one bin's
-// tail overlaps the next bin's bulk (the reference runs its bins on 12 streams, src/Tool.cu:6-10).
-// Measured (round 4, profiles/r04): dealing by estimated work (LPT over products and the heaviest
-// row) put the hub rows' launch behind the bulk bins -- wb-edu-like +3 %, webbase-like +3 % --
-// concurrent launches share the CUs, and the hub rows' 1024-thread blocks, one per CU for their
-// LDS, progress only as CUs free up; started first, they hold their CUs from the start.
-// Returns the mask of streams used.
+// Numeric launches.  The numeric-phase events (MHS_OPT_NUMERIC_EVENTS) ride on the first and last
+// dispatch packet of a single-stream numeric phase (hipExtLaunchKernel) instead of event records
+// of their own between the kernels -- each record measured ~5 us of idle before the next kernel
+// (pipelined cant-like steps, r06b timelines).
 namespace {
-struct NumLaunch {
-    std::function<void(hipStream_t)> go;
+struct At {  // where and how one numeric kernel goes out
+    dim3 grid, block;
+    unsigned lds;
+    hipStream_t s;
+    hipEvent_t start, stop;
 };
-}  // namespace
+template <typename F, typename... Args>
+void num_launch(F kernel, const At& at, Args... args) {
+    if (at.start || at.stop)
+        hipExtLaunchKernelGGL(kernel, at.grid, at.block, at.lds, at.s, at.start, at.stop, 0u, args...);
+    else hipLaunchKernelGGL(kernel, at.grid, at.block, at.lds, at.s, args...);
+}
+// a kernel's two instantiations by the width of the B gathers' byte offsets
+template <typename F, typename... Args>
+void num_launch_o32(bool o32, F k32, F k64, const At& at, Args... args) {
+    num_launch(o32 ? k32 : k64, at, args...);
+}
 
-int launch_numeric(const Csr& A, const Csr& B, const Work& w, const Stats& h, int* Cptr, int* Ccol,
-                   double* Cval, const hipStream_t* ss, int nss, int global_grid, int dense_span_max, bool split,
-                   hipEvent_t split_ev, const std::function<bool()>& fork, hipEvent_t ev_start, hipEvent_t ev_stop,
-                   int only) {
-    std::vector<NumLaunch> L;
-    auto add = [&](std::function<void(hipStream_t)> go) { L.push_back(NumLaunch{std::move(go)}); };
+NumArgs num_args(const NumPointers& p, const NumLaunch& l) {
+    const Work& w = p.w;
     NumArgs a{};
-    a.dense_span_max = dense_span_max;
+    a.dense_span_max = p.dense_span_max;
     a.mcache = w.mcache;
     a.mc_list = w.mc_list;
     a.mc_stride = mc_stride(w.mc_list);
-    a.Aptr = A.ptr;
-    a.Acol = A.col;
-    a.Aval = A.val;
-    a.Bcol = B.col;
-    a.Bval = B.val;
+    a.Aptr = p.A.ptr;
+    a.Acol = p.A.col;
+    a.Aval = p.A.val;
+    a.Bcol = p.B.col;
+    a.Bval = p.B.val;
     a.bmeta = w.bmeta;
     a.btcol = w.btcol;
     a.btmask = w.btmask;
@@ -4806,13 +4734,11 @@ int launch_numeric(const Csr& A, const Csr& B, const Work& w, const Stats& h, in
     a.rlo = w.rlo;
     a.rhi = w.rhi;
     a.ctiles = w.ctiles;
-    a.Cptr = Cptr;
-    a.Ccol = Ccol;
-    a.Cval = Cval;
+    a.Cptr = p.Cptr;
+    a.Ccol = p.Ccol;
+    a.Cval = p.Cval;
     a.gscratch = (char*)w.gscratch;
-    a.gbytes = 0;
     a.grp = w.grp;
-    a.cursor = w.cursors;
     a.sp = w.spill;
     a.ucol = w.ucol;
     a.uval = w.uval;
@@ -4821,248 +4747,107 @@ int launch_numeric(const Csr& A, const Csr& B, const Work& w, const Stats& h, in
     // near union runs (B is A and near groups were verified): the value walks read B's arrays
     // extended by the union rows (bx_col / bx_val, filled by launch_union_b before numeric)
     if (w.bx_on) {
-        a.ubase = B.nnz;
+        a.ubase = p.B.nnz;
         a.Bcol = w.bx_col;
         a.Bval = w.bx_val;
     }
-    // 32-bit byte offsets for the B gathers when B's value array (extended by the union rows)
-    // stays below 4 GiB: nnz(B) + 3 nnz(A) < 2^29 (the reference's int32 CSR allows up to 2^31)
-    const bool o32 = (long long)B.nnz + (w.bx_on ? 3LL * A.nnz : 0) < (1LL << 29);
-    // a wave-bin launch over `bin`'s list (cursor slot = bin)
-    auto wave_args = [&](int bin) {
-        NumArgs x = a;
-        x.count = h.num_count[bin];
-        x.list = w.bin_list + (long long)(bin - 1) * A.M;
-        x.cursor = w.cursors + bin * 8 * CURSOR_STRIDE;
-        return x;
-    };
-
-    // Numeric-first rows: their copy of the slot values into C (short and HBM-bound).
-    const bool copy = w.sc_col != nullptr;  // numeric-first: tiny classes 0..3 hold slot rows
-    // ... fused with the small hash wave bin when those two are the whole phase (k_copy_hash)
-    // (r06fc: mac_econ-like numeric 45 -> 34 us, pipelined step -5 %)
-    bool fuse = copy && h.num_count[NUM_WSH] > 0;
-    for (int b = 1; b < NUM_NB && fuse; ++b)
-        fuse = b == NUM_WSH || (b >= NUM_TINY && b < NUM_TINY + 4) || h.num_count[b] <= 0;
-    if (copy) {
-        TinyFused f{};
-        int ncopy = 0, cmed = 0;
-        for (int c = 3; c >= 0; --c) {
-            const int count = h.num_count[NUM_TINY + c];
-            if (count <= 0) continue;
-            ncopy += count;
-            const int per = 256 / copy_lanes(c);
-            f.c[f.nclass] = c;
-            f.count[f.nclass] = count;
-            f.blk0[f.nclass + 1] = f.blk0[f.nclass] + round8((count + per - 1) / per, 4096);
-            ++f.nclass;
-        }
-        for (int c = 0, acc = 0; c < 4; ++c) {  // the class of the median slot row
-            acc += h.num_count[NUM_TINY + c];
-            if (2 * acc >= ncopy) {
-                cmed = c;
-                break;
-            }
-        }
-        if (f.nclass > 0) {
-            const CopyArgs ca{w.bin_list, A.M, Cptr, w.tslot, w.sc_col, w.sc_val, Ccol, Cval, w.go};
-            // lanes per row by the median row's class
-            const int Lw = copy_lanes(cmed) > 16 ? 16 : copy_lanes(cmed);
-            const dim3 grid(round8((A.M + 256 / Lw - 1) / (256 / Lw), A.M >= MHS_NFT_BIG_M ? MHS_COPY_CAP_BIG : 16384));
-            if (fuse) {
-                const NumArgs x = wave_args(NUM_WSH);
-                const int hb = round8((x.count + WPB - 1) / WPB, x.count >= MHS_NUM_WSH_BIG ? MHS_NUM_WSH_BIG_GRID : MHS_NUM_WSX_GRID);
-                const dim3 g2(hb + grid.x);
-                add([=](hipStream_t s) {
-#define MHS_COPY_HASH(LL)                                                                                           \
-    (o32 ? num_launch((k_copy_hash<LL, true>), g2, dim3(256), WPB * NUM_WS_BYTES, s, ca, x, hb)                      \
-         : num_launch((k_copy_hash<LL, false>), g2, dim3(256), WPB * NUM_WS_BYTES, s, ca, x, hb))
-                    if (Lw == 4) MHS_COPY_HASH(4);
-                    else if (Lw == 8) MHS_COPY_HASH(8);
-                    else MHS_COPY_HASH(16);
-#undef MHS_COPY_HASH
-                });
-            } else {
-                add([=](hipStream_t s) {
-                    if (Lw == 4) num_launch(k_tiny_copy_rows<4>, grid, dim3(256), 0, s, ca);
-                    else if (Lw == 8) num_launch(k_tiny_copy_rows<8>, grid, dim3(256), 0, s, ca);
-                    else num_launch(k_tiny_copy_rows<16>, grid, dim3(256), 0, s, ca);
-                });
-            }
-        } else {
-            fuse = false;
-        }
-    }
-    if (h.num_count[NUM_GLOBAL] > 0) {
-        NumArgs x = wave_args(NUM_GLOBAL);
-        x.gbytes = align16(h.num_global_need);
-        const int g = x.count < global_grid ? x.count : global_grid;
-        add([=](hipStream_t s) {
-            if (o32) num_launch((k_num_block<1024, true, true>), dim3(g), dim3(1024), BLOCK_HDR_1024, s, x);
-            else num_launch((k_num_block<1024, true, false>), dim3(g), dim3(1024), BLOCK_HDR_1024, s, x);
-        });
-    }
-    // block bins: rows past the bin's LDS split (hub rows) in a launch of their own, so the
-    // others run at the occupancy their own tables allow
-    auto block_bin = [&](int bin, int k, int T, int grid_cap, int budget, int big_slot) {
-        const int count = h.num_count[bin];
-        if (count <= 0) return;
-        auto go = [&](const int* list, int rows, int lds, int slot, hipEvent_t after) {
-            NumArgs x = a;
-            x.list = list;
-            x.count = rows;
-            x.cursor = w.cursors + slot * 8 * CURSOR_STRIDE;
-            const dim3 grid(round8(rows, grid_cap));
-            const hipStream_t s0 = ss[0];
-            add([=](hipStream_t s) {
-                if (after && s != s0) (void)hipStreamWaitEvent(s, after, 0);  // (k_split_bins' lists)
-                if (T == 1024 && o32) num_launch((k_num_block<1024, false, true>), grid, dim3(1024), lds, s, x);
-                else if (T == 1024) num_launch((k_num_block<1024, false, false>), grid, dim3(1024), lds, s, x);
-                else if (o32) num_launch((k_num_block<256, false, true>), grid, dim3(256), lds, s, x);
-                else num_launch((k_num_block<256, false, false>), grid, dim3(256), lds, s, x);
-            });
-        };
-        if (split && block_split_on(h, k)) {  // k_split_bins: small rows first, hub rows last
-            const int big = h.num_block_big[k];
-            const int* l = w.split_list + (k ? 0 : (h.num_count[NUM_B1024] > 0 ? h.num_count[NUM_B1024] : 0));
-            go(l + (count - big), big, block_lds(h.num_block_need[k], budget, T), big_slot, split_ev);
-            go(l, count - big, block_lds(h.num_block_small_need[k], budget, T), bin, split_ev);
-        } else {
-            go(w.bin_list + (long long)(bin - 1) * A.M, count, block_lds(h.num_block_need[k], budget, T), bin, nullptr);
-        }
-    };
-    block_bin(NUM_B1024, 1, 1024, 256, LDS_MAX - 1024, BLOCK_BIG_SLOT + 1);
-    block_bin(NUM_B256, 0, 256, 1024, NUM_B256_BYTES, BLOCK_BIG_SLOT);
-    if (h.num_count[NUM_W16H] > 0) {
-        NumArgs x = wave_args(NUM_W16H);
-        x.qall = x.count <= MHS_DYN16_MAX;  // a few rows per resident wave: the launch's end is one heavy row
-        const dim3 grid(round8((x.count + WPB - 1) / WPB, MHS_NUM_W16H_GRID));
-        add([=](hipStream_t s) {
-            if (o32) num_launch((k_num_wave_hash<NUM_W16_BYTES, true>), grid, dim3(256), WPB * NUM_W16_BYTES, s, x);
-            else num_launch((k_num_wave_hash<NUM_W16_BYTES, false>), grid, dim3(256), WPB * NUM_W16_BYTES, s, x);
-        });
-    }
-    if (h.num_count[NUM_WSH] > 0 && !fuse) {
-        const NumArgs x = wave_args(NUM_WSH);
-        const dim3 grid(round8((x.count + WPB - 1) / WPB, x.count >= MHS_NUM_WSH_BIG ? MHS_NUM_WSH_BIG_GRID : MHS_NUM_WSX_GRID));
-        add([=](hipStream_t s) {
-            if (o32) num_launch((k_num_wave_hash<NUM_WS_BYTES, true>), grid, dim3(256), WPB * NUM_WS_BYTES, s, x);
-            else num_launch((k_num_wave_hash<NUM_WS_BYTES, false>), grid, dim3(256), WPB * NUM_WS_BYTES, s, x);
-        });
-    }
-    if (h.num_count[NUM_W16] > 0) {
-        const NumArgs x = wave_args(NUM_W16);
-        const dim3 grid(round8((x.count + WPB - 1) / WPB, 2048));
-        add([=](hipStream_t s) {
-            if (o32) num_launch((k_num_wave_direct<NUM_W16_BYTES, true>), grid, dim3(256), WPB * NUM_W16_BYTES, s, x);
-            else num_launch((k_num_wave_direct<NUM_W16_BYTES, false>), grid, dim3(256), WPB * NUM_W16_BYTES, s, x);
-        });
-    }
-    {
-        TinyArgs t{};
-        t.M = A.M;
-        t.Aptr = A.ptr;
-        t.Acol = A.col;
-        t.Aval = A.val;
-        t.bmeta = w.bmeta;
-        t.Bcol = B.col;
-        t.Bval = B.val;
-        t.Cptr = Cptr;
-        t.Ccol = Ccol;
-        t.Cval = Cval;
-        t.rlo = w.rlo;
-        t.go = w.go;
-        for (int c = TINY_NC - 1; c >= 4; --c) {  // 64-lane classes: kernels of their own (registers)
-            const int count = h.num_count[NUM_TINY + c];
-            if (count <= 0) continue;
-            TinyArgs tc = t;
-            tc.count = count;
-            tc.bin = NUM_TINY + c;
-            tc.list = w.bin_list + (long long)(tc.bin - 1) * A.M;
-            add([=](hipStream_t s) { launch_tiny_num(c, count, tc, s); });
-        }
-        TinyFused f{};
-        static_assert(tiny_w(3) <= 32 && tiny_k(0) <= TINY_FUSED_KMAX && tiny_k(1) <= TINY_FUSED_KMAX &&
-                          tiny_k(2) <= TINY_FUSED_KMAX && tiny_k(3) <= TINY_FUSED_KMAX && tiny_w(4) == 64,
-                      "classes 0..3 fuse (W <= 32, K <= TINY_FUSED_KMAX)");
-        for (int c = 3; c >= 0 && !copy; --c) {  // (numeric-first: copied above)
-            const int count = h.num_count[NUM_TINY + c];
-            if (count <= 0) continue;
-            const int per = 256 / tiny_w(c);
-            f.c[f.nclass] = c;
-            f.count[f.nclass] = count;
-            f.blk0[f.nclass + 1] = f.blk0[f.nclass] + round8((count + per - 1) / per, 4096);
-            ++f.nclass;
-        }
-        if (f.nclass > 0) {
-            t.list = w.bin_list;
-            add([=](hipStream_t s) {
-                num_launch(k_tiny_num_small, dim3(f.blk0[f.nclass]), dim3(256), 256 * TINY_FUSED_KMAX * 8, s, t,
-                                   f);
-            });
-        }
-    }
-    // grouped bins: LDS regions of their largest group's need, 256-byte steps (k_scan's num_wave_need)
-    auto wave_region = [](int need, int cap) {
-        const int b = (need + 255) & ~255;
-        return need <= 0 || b > cap ? cap : b;
-    };
-    if (h.num_count[NUM_W16G] > 0) {
-        NumArgs x = wave_args(NUM_W16G);
-        x.wave_bytes = wave_region(h.num_wave_need[1], NUM_W16_BYTES);
-        const dim3 grid(round8((x.count + WPB - 1) / WPB, 2048));
-        add([=](hipStream_t s) {
-            if (o32) num_launch((k_num_wave<NUM_W16_BYTES, true, false, true>), grid, dim3(256), WPB * x.wave_bytes, s, x);
-            else num_launch((k_num_wave<NUM_W16_BYTES, true, false, false>), grid, dim3(256), WPB * x.wave_bytes, s, x);
-        });
-    }
-    if (h.num_count[NUM_WSG] > 0) {
-        NumArgs x = wave_args(NUM_WSG);
-        x.wave_bytes = wave_region(h.num_wave_need[0], NUM_WSG_BYTES);
-        const dim3 grid(round8((x.count + WPB - 1) / WPB, MHS_NUM_WS_GRID));
-        add([=](hipStream_t s) {
-            if (o32) num_launch((k_num_wave<NUM_WSG_BYTES, true, false, true>), grid, dim3(256), WPB * x.wave_bytes, s, x);
-            else num_launch((k_num_wave<NUM_WSG_BYTES, true, false, false>), grid, dim3(256), WPB * x.wave_bytes, s, x);
-        });
-    }
-    if (h.num_count[NUM_WS] > 0) {
-        const NumArgs x = wave_args(NUM_WS);
-        const dim3 grid(round8((x.count + WPB - 1) / WPB, MHS_NUM_WSX_GRID));
-        add([=](hipStream_t s) {
-            if (o32) num_launch((k_num_wave_direct<NUM_WS_BYTES, true>), grid, dim3(256), WPB * NUM_WS_BYTES, s, x);
-            else num_launch((k_num_wave_direct<NUM_WS_BYTES, false>), grid, dim3(256), WPB * NUM_WS_BYTES, s, x);
-        });
-    }
-    // launch i on ss[i % n]: the first (largest rows) goes out on the call's stream at once, and the
-    // aux streams' waits on the fork event are set up after it (`fork`, host API calls that would
-    // otherwise sit between the hand-off and the first numeric kernel: round 5, scircuit-like's
-    // hand-off gap 46 -> ? us)
-    // (a failed fork -- the aux streams' wait on the fork event -- sends every later launch to
-    // ss[0]: no aux-stream launch may run without its dependency on the pre-numeric work)
-    // `only`: the streams (bit k: ss[k]) whose launches go out in this call -- a speculated plan
-    // deals the same list twice, the call stream's share first (see NumPhase in mhs_api.cpp)
-    int used = 0;
-    int n = nss < 1 ? 1 : (nss > 8 ? 8 : nss);
-    const bool evs = n == 1 && !L.empty() && (ev_start || ev_stop) && (only & 1);  // (single stream only: see num_launch)
-    bool forked = false;
-    for (size_t i = 0; i < L.size(); ++i) {
-        int k = n > 1 ? (int)(i % n) : 0;
-        if (!((only >> k) & 1)) continue;
-        if (k != 0 && !forked) {  // the aux streams' waits, before their first launch
-            forked = true;
-            if (fork && !fork()) {
-                n = 1;  // (a failed fork: the rest on ss[0])
-                k = 0;
-            }
-        }
-        used |= 1 << k;
-        if (evs && i == 0) t_num_start = ev_start;
-        if (evs && i + 1 == L.size()) t_num_stop = ev_stop;
-        L[i].go(ss[k]);
-    }
-    t_num_start = t_num_stop = nullptr;
-    if (!evs && (ev_start || ev_stop)) used |= 1 << 30;  // the caller records the events itself
-    if (!forked && n > 1 && fork && (only & ~1)) (void)fork();  // (the caller's error check expects the fork)
-    return used;
+    a.list = l.list_bin == LIST_SPLIT ? w.split_list + l.list_off : w.bin_list + (long long)(l.list_bin - 1) * p.A.M;
+    a.count = l.count;
+    a.cursor = w.cursors + l.slot * 8 * CURSOR_STRIDE;
+    a.gbytes = l.gbytes;
+    a.qall = l.qall;
+    a.wave_bytes = l.wave_bytes;
+    return a;
 }
+
+TinyArgs tiny_args(const NumPointers& p, const NumLaunch& l) {
+    TinyArgs t{};
+    t.M = p.A.M;
+    t.Aptr = p.A.ptr;
+    t.Acol = p.A.col;
+    t.Aval = p.A.val;
+    t.bmeta = p.w.bmeta;
+    t.Bcol = p.B.col;
+    t.Bval = p.B.val;
+    t.Cptr = p.Cptr;
+    t.Ccol = p.Ccol;
+    t.Cval = p.Cval;
+    t.rlo = p.w.rlo;
+    t.go = p.w.go;
+    if (l.list_bin == LIST_CLASSES) {  // (k_tiny_num_small finds its classes' lists itself)
+        t.list = p.w.bin_list;
+    } else {
+        t.count = l.count;
+        t.bin = l.list_bin;
+        t.list = p.w.bin_list + (long long)(l.list_bin - 1) * p.A.M;
+    }
+    return t;
+}
+}  // namespace
+
+void issue_numeric(const NumLaunch& l, bool o32, const NumPointers& p, hipStream_t s, hipEvent_t start,
+                   hipEvent_t stop) {
+    const At at{dim3(l.grid), dim3(l.block), (unsigned)l.lds, s, start, stop};
+    const Work& w = p.w;
+    const CopyArgs ca{w.bin_list, p.A.M, p.Cptr, w.tslot, w.sc_col, w.sc_val, p.Ccol, p.Cval, w.go};
+    switch (l.kernel) {
+    case NK_COPY:
+        if (l.variant == 4) num_launch(k_tiny_copy_rows<4>, at, ca);
+        else if (l.variant == 8) num_launch(k_tiny_copy_rows<8>, at, ca);
+        else num_launch(k_tiny_copy_rows<16>, at, ca);
+        break;
+    case NK_COPY_HASH: {
+        const NumArgs x = num_args(p, l);
+        if (l.variant == 4) num_launch_o32(o32, k_copy_hash<4, true>, k_copy_hash<4, false>, at, ca, x, l.hash_blocks);
+        else if (l.variant == 8) num_launch_o32(o32, k_copy_hash<8, true>, k_copy_hash<8, false>, at, ca, x, l.hash_blocks);
+        else num_launch_o32(o32, k_copy_hash<16, true>, k_copy_hash<16, false>, at, ca, x, l.hash_blocks);
+        break;
+    }
+    case NK_GLOBAL:
+        num_launch_o32(o32, k_num_block<1024, true, true>, k_num_block<1024, true, false>, at, num_args(p, l));
+        break;
+    case NK_BLOCK1024:
+        num_launch_o32(o32, k_num_block<1024, false, true>, k_num_block<1024, false, false>, at, num_args(p, l));
+        break;
+    case NK_BLOCK256:
+        num_launch_o32(o32, k_num_block<256, false, true>, k_num_block<256, false, false>, at, num_args(p, l));
+        break;
+    case NK_HASH16:
+        num_launch_o32(o32, k_num_wave_hash<NUM_W16_BYTES, true>, k_num_wave_hash<NUM_W16_BYTES, false>, at, num_args(p, l));
+        break;
+    case NK_HASH:
+        num_launch_o32(o32, k_num_wave_hash<NUM_WS_BYTES, true>, k_num_wave_hash<NUM_WS_BYTES, false>, at, num_args(p, l));
+        break;
+    case NK_DIRECT16:
+        num_launch_o32(o32, k_num_wave_direct<NUM_W16_BYTES, true>, k_num_wave_direct<NUM_W16_BYTES, false>, at, num_args(p, l));
+        break;
+    case NK_DIRECT:
+        num_launch_o32(o32, k_num_wave_direct<NUM_WS_BYTES, true>, k_num_wave_direct<NUM_WS_BYTES, false>, at, num_args(p, l));
+        break;
+    case NK_GROUP16:
+        num_launch_o32(o32, k_num_wave<NUM_W16_BYTES, true, false, true>, k_num_wave<NUM_W16_BYTES, true, false, false>, at,
+                       num_args(p, l));
+        break;
+    case NK_GROUP:
+        num_launch_o32(o32, k_num_wave<NUM_WSG_BYTES, true, false, true>, k_num_wave<NUM_WSG_BYTES, true, false, false>, at,
+                       num_args(p, l));
+        break;
+    case NK_TINY64: {  // (k_tiny_num is instantiated for every class; the plan launches 4 and 5 through it)
+        const TinyArgs t = tiny_args(p, l);
+        switch (l.variant) {
+        case 0: num_launch(k_tiny_num<tiny_w(0), tiny_k(0)>, at, t); break;
+        case 1: num_launch(k_tiny_num<tiny_w(1), tiny_k(1)>, at, t); break;
+        case 2: num_launch(k_tiny_num<tiny_w(2), tiny_k(2)>, at, t); break;
+        case 3: num_launch(k_tiny_num<tiny_w(3), tiny_k(3)>, at, t); break;
+        case 4: num_launch(k_tiny_num<tiny_w(4), tiny_k(4)>, at, t); break;
+        default: num_launch(k_tiny_num<tiny_w(5), tiny_k(5)>, at, t); break;
+        }
+        break;
+    }
+    case NK_TINY_SMALL:
+        num_launch(k_tiny_num_small, at, tiny_args(p, l), l.fused);
+        break;
+    }
+}
+
 }  // namespace mhs

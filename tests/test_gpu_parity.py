@@ -792,7 +792,7 @@ def test_symbolic_scattered_sort_class(tool, mode, monkeypatch):
         t2.close()
 
 
-# ---- round 6: launch plan speculation (MHS_OPT_SPECULATE, SpecArgs in mhs_internal.hpp) -------
+# ---- round 6: launch plan speculation (MHS_OPT_SPECULATE, SpecArgs in mhs_shape.hpp) -------
 
 def _host_c(C):
     try:

@@ -43,6 +43,19 @@ def test_output_owner_under_sanitizers(tmp_path):
     assert run.returncode == 0 and run.stdout.strip() == "owner ok", run.stdout + run.stderr
 
 
+def test_numeric_plan_under_sanitizers(tmp_path):
+    # the numeric launch plan (csrc/mhs_numplan.hpp) is a HIP-free function of the published Stats:
+    # tests/numplan_check.cpp checks every bin's launch, the split and fused cases, the thresholds, the
+    # speculation premise and the dealing rule against hand-computed literals on the host
+    exe = tmp_path / "numplan_check"
+    cc = subprocess.run(["c++", "-std=c++17", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                         "-fno-sanitize-recover=all", str(ROOT / "tests" / "numplan_check.cpp"), "-o", str(exe)],
+                        capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout.strip() == "numplan ok", run.stdout + run.stderr
+
+
 def test_vendor_library_exports_every_declared_symbol():
     # rocSPARSE comparison row (include/mhs_vendor.h): loads without a GPU, exports its two entries
     V = _lib.vendor_lib()
