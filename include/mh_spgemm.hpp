@@ -7,6 +7,9 @@
 //   class Tool     (inc/Tool.h, src/Tool.cu)            here: owns the mhs_ctx
 //   void MH_spgemm(const CSR&, CSR&, CSR&, Timing&, Tool&)   (src/main.cu:12-72)
 //   int  readMtxFile(CSR&, const char*)                      (inc/mmio_read.h:34)
+// and, beyond the reference, the values-only call on a kept pattern:
+//   class mhs_shim::ValuesPlan                               owns an mhs_values_plan
+//   void MH_spgemm_values(const CSR&, const CSR&, CSR&, mhs_shim::ValuesPlan&)
 //
 // Errors: the C-ABI returns codes; this shim rethrows as std::runtime_error so a
 // caller's try { MH_spgemm(...) } catch (...) { "MH-SpGEMM failed!!!" } behaves as
@@ -225,6 +228,46 @@ inline void MH_spgemm(const CSR& A, CSR& B, CSR& C, Timing& timing, Tool& tools)
     timing.Numeric = t.Numeric;
     timing.total_e2e = t.total_e2e;
     timing.flop = t.flop;
+}
+
+namespace mhs_shim {
+// A values plan over the patterns of A, B and C (mhs_values_plan_create): C.d_ptr / C.d_col hold a
+// pattern containing the product's, normally C of MH_spgemm.  The six pattern arrays are borrowed:
+// they stay alive and unchanged while the plan lives.  Throws where the C-ABI returns an error.
+class ValuesPlan {
+public:
+    mhs_ctx* ctx = nullptr;
+    mhs_values_plan* plan = nullptr;
+    ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C) : ctx(tools.ctx) {
+        mhs_csr a{A.M, A.N, A.nnz, A.d_ptr, A.d_col, A.d_val};
+        mhs_csr b{B.M, B.N, B.nnz, B.d_ptr, B.d_col, B.d_val};
+        mhs_csr c{C.M, C.N, C.nnz, C.d_ptr, C.d_col, C.d_val};
+        if (mhs_values_plan_create(ctx, &a, &b, &c, &plan) != MHS_OK) {
+            std::printf("%s\n", mhs_last_error(ctx));
+            throw std::runtime_error(mhs_last_error(ctx));
+        }
+    }
+    ValuesPlan(const ValuesPlan&) = delete;
+    ValuesPlan& operator=(const ValuesPlan&) = delete;
+    ~ValuesPlan() { mhs_values_plan_destroy(ctx, plan); }
+    mhs_values_info info() const {
+        mhs_values_info i{};
+        mhs_values_plan_info(plan, &i);
+        return i;
+    }
+    // the hipEvent time of the last MH_spgemm_values call through this plan (ms)
+    double last_ms = 0;
+};
+}  // namespace mhs_shim
+
+// C.d_val = the values of A * B at C's pattern, from A.d_val and B.d_val (mhs_spgemm_values); the
+// patterns are the plan's.  Rethrows on error like MH_spgemm.
+inline void MH_spgemm_values(const CSR& A, const CSR& B, CSR& C, mhs_shim::ValuesPlan& plan) {
+    const int rc = mhs_spgemm_values(plan.ctx, plan.plan, A.d_val, B.d_val, C.d_val, &plan.last_ms);
+    if (rc != MHS_OK) {
+        std::printf("%s\n", mhs_last_error(plan.ctx));
+        throw std::runtime_error(mhs_last_error(plan.ctx));
+    }
 }
 
 // src/utils.cpp:20-46 (B = A^T for AAT, src/main.cu:98-99) on the device: A must be

@@ -158,6 +158,46 @@ int mhs_probe_conflicts(mhs_ctx *ctx, uint64_t *count);
  * MHS_OPT_SYNC is 0.  t may be NULL. */
 int mhs_spgemm(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, mhs_csr *C, mhs_timing *t);
 
+/* ---- values-only SpGEMM: recompute C's values on a kept pattern -----------
+ * (the "reuse" / compute stage of the vendor libraries' SpGEMM).  For callers that repeat one
+ * product on fixed patterns with new values (time steppers, Newton loops, AMG set-up): the
+ * pattern phases of mhs_spgemm, the allocation of C and the host hand-off are paid once, at
+ * plan creation.  These entry points are additions to ABI version 10: nothing declared above
+ * changes, so MHS_ABI_VERSION stays 10 and binaries built against the earlier header keep
+ * working; callers that may meet an older library look the symbols up before use. */
+typedef struct mhs_values_plan mhs_values_plan;
+
+/* Build once per pattern.  A, B, C: device CSR; C->ptr / C->col hold a pattern that
+ * contains the pattern of A*B (normally C from mhs_spgemm on operands of this pattern).
+ * The plan borrows the six pattern arrays (A/B/C ptr and col): the caller keeps them alive
+ * and unchanged until the plan is destroyed.  No val array is read.  Synchronous.
+ * Validated here, on the device, once: A.N == B.M, C.M == A.M, C.N == B.N; the three row_ptr
+ * arrays monotone from 0 to nnz; A's columns < B.M; C's columns strictly ascending and in
+ * range within each row; every product's column present in its C row.  A violation returns
+ * MHS_ERR_INVALID with a message naming the first bad row, and no plan.
+ * The plan owns its device memory (row lists of about M ints, counters, a status word), not
+ * the context workspace: mhs_spgemm calls and mhs_ctx_trim on the same context leave it alone. */
+int mhs_values_plan_create(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
+                           mhs_values_plan **plan);
+/* Cval[Cptr[i]..Cptr[i+1]) = values of row i of A*B at C's columns; entries of C's pattern
+ * that no product reaches get 0.0.  Aval/Bval/Cval: device arrays of nnz(A)/nnz(B)/nnz(C)
+ * doubles, any buffers (Cval may be C->val or another array).  ms == NULL: follows
+ * MHS_OPT_SYNC like mhs_spgemm (0: returns once queued on the context stream).  ms != NULL:
+ * synchronises and writes the hipEvent time of the call.
+ * Hot calls do not re-validate: the pattern arrays must not have changed since plan creation.
+ * A call with ms == NULL and MHS_OPT_SYNC 0 allocates nothing, reads nothing back and does not
+ * synchronise; it only launches on the context stream (mhs_ctx_set_stream's, when set). */
+int mhs_spgemm_values(mhs_ctx *ctx, mhs_values_plan *plan, const double *Aval, const double *Bval,
+                      double *Cval, double *ms);
+typedef struct mhs_values_info {
+    int32_t rows[8];              /* rows per class, index = class id (0: nothing to compute; 1 team, 2 wave-direct,
+                                   * 3 wave-search, 4 block-direct, 5 block-search, 6 global) */
+    int64_t products, nnzC, plan_bytes;
+} mhs_values_info;
+int mhs_values_plan_info(const mhs_values_plan *plan, mhs_values_info *info);
+/* Frees the plan's device memory (waits for the context stream first).  NULL plan: no-op. */
+void mhs_values_plan_destroy(mhs_ctx *ctx, mhs_values_plan *plan);
+
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).
  * At->M = A->N, At->N = A->M; rows of At list their columns ascending; arrays are

@@ -114,6 +114,26 @@ struct mhs_ctx {
     int spec_nss = mhs_ctx::NAUX + 1;  // streams of a speculated numeric phase (MHS_SPEC_NSS: a cap, A/B)
 };
 
+// A values plan (mhs_values_plan_create): the six borrowed pattern arrays, the class lists and the
+// launch plan.  Its device memory is its own (not the context workspace): mhs_spgemm calls and
+// mhs_ctx_trim on the same context leave it alone.
+struct mhs_values_plan {
+    int device = 0;
+    ValPattern pat{};
+    long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
+    char* mem = nullptr;   // lists (M ints), counters (VAL_CNT_INTS), status (VAL_STATUS_INTS)
+    size_t mem_bytes = 0;
+    int* lists = nullptr;
+    int list_off[VAL_NCLASS] = {};
+    ValCounts counts{};
+    ValPlan plan{};
+    hipEvent_t ev[2] = {};  // timed calls
+};
+
+namespace {
+constexpr int VAL_STATUS_INTS = 8;  // first bad row of: A.ptr, B.ptr, C.ptr, A's columns, C's columns, the products
+}
+
 namespace {
 
 int fail(mhs_ctx* ctx, int code, const std::string& what) {
@@ -1225,6 +1245,141 @@ int mhs_spgemm(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C, mhs
         const int rc = spgemm_attempt(ctx, A, B, C, t);
         if (rc != CALL_RERUN) return rc;
     }
+}
+
+int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
+    *out = nullptr;
+    if (A->M < 0 || A->N < 0 || A->nnz < 0 || B->M < 0 || B->N < 0 || B->nnz < 0 || C->M < 0 || C->N < 0 || C->nnz < 0)
+        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: negative dimension");
+    if (A->N != B->M) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: A.N != B.M");
+    if (C->M != A->M) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: C.M != A.M");
+    if (C->N != B->N) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: C.N != B.N");
+    if ((A->M > 0 && (!A->ptr || !C->ptr)) || (B->M > 0 && !B->ptr) || (A->nnz > 0 && !A->col) || (B->nnz > 0 && !B->col) ||
+        (C->nnz > 0 && !C->col))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null device array");
+    MHS_HIP(hipSetDevice(ctx->device));
+    mhs_values_plan* p = new mhs_values_plan();
+    p->device = ctx->device;
+    p->pat = ValPattern{A->M, A->ptr, A->col, B->ptr, B->col, C->ptr, C->col};
+    p->nnzA = A->nnz, p->nnzB = B->nnz, p->nnzC = C->nnz;
+    const int M = A->M;
+    hipStream_t s = ctx->stream;
+    const size_t lists_bytes = al((size_t)(M > 0 ? M : 1) * 4);
+    p->mem_bytes = lists_bytes + al((size_t)VAL_CNT_INTS * 4) + al((size_t)VAL_STATUS_INTS * 4);
+    int status[VAL_STATUS_INTS];
+    int h_cnt[VAL_CNT_INTS];
+    auto bail = [&](int rc) {
+        mhs_values_plan_destroy(ctx, p);
+        return rc;
+    };
+    auto bail_hip = [&](hipError_t e, const char* what) { return bail(fail_hip(ctx, e, what)); };
+    hipError_t e = hipMalloc((void**)&p->mem, p->mem_bytes);
+    if (e != hipSuccess) return bail_hip(e, "mhs_values_plan_create: plan memory");
+    for (hipEvent_t& ev : p->ev)
+        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: events");
+    p->lists = (int*)p->mem;
+    int* d_cnt = (int*)(p->mem + lists_bytes);
+    int* d_status = d_cnt + al((size_t)VAL_CNT_INTS * 4) / 4;
+    // status words start at INT_MAX (0x7f7f7f7f is as good: any row index is below it)
+    if ((e = hipMemsetAsync(d_cnt, 0, (size_t)VAL_CNT_INTS * 4, s)) != hipSuccess) return bail_hip(e, "plan counters");
+    if ((e = hipMemsetAsync(d_status, 0x7f, (size_t)VAL_STATUS_INTS * 4, s)) != hipSuccess) return bail_hip(e, "plan status");
+    constexpr int NONE = 0x7f7f7f7f;
+    auto read_status = [&]() -> hipError_t {
+        hipError_t r = hipGetLastError();
+        if (r == hipSuccess) r = hipMemcpyAsync(status, d_status, sizeof status, hipMemcpyDeviceToHost, s);
+        if (r == hipSuccess) r = hipStreamSynchronize(s);
+        return r;
+    };
+    auto bad_row = [&](int k, const char* what) {
+        return bail(fail(ctx, MHS_ERR_INVALID, std::string("mhs_values_plan_create: ") + what + " (first at row " +
+                                                   std::to_string(status[k]) + ")"));
+    };
+    // 1. the three row_ptr arrays: everything after this indexes through them
+    launch_val_check_ptr(A->ptr, A->M, A->nnz, d_status + 0, s);
+    launch_val_check_ptr(B->ptr, B->M, B->nnz, d_status + 1, s);
+    launch_val_check_ptr(C->ptr, C->M, C->nnz, d_status + 2, s);
+    if ((e = read_status()) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: row_ptr check");
+    if (status[0] != NONE) return bad_row(0, "A.ptr is not a row_ptr of nnz(A) entries");
+    if (status[1] != NONE) return bad_row(1, "B.ptr is not a row_ptr of nnz(B) entries");
+    if (status[2] != NONE) return bad_row(2, "C.ptr is not monotone from 0 to C.nnz");
+    if ((A->M == 0 && A->nnz != 0) || (B->M == 0 && B->nnz != 0) || (C->M == 0 && C->nnz != 0))
+        return bail(fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: entries without rows"));
+    // 2. A's columns index B's rows; C's columns ascend strictly within [0, C.N)
+    launch_val_check_cols(A->ptr, A->col, A->M, B->M, false, d_status + 3, s);
+    launch_val_check_cols(C->ptr, C->col, C->M, C->N, true, d_status + 4, s);
+    if ((e = read_status()) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: column check");
+    if (status[3] != NONE) return bad_row(3, "a column of A is outside [0, B.M)");
+    if (status[4] != NONE) return bad_row(4, "C's columns are not strictly ascending within [0, C.N)");
+    // 3. classes, lists, and every product's column looked up in its C row
+    launch_val_classify(p->pat, d_cnt, p->lists, s);
+    launch_val_verify(p->pat, d_status + 5, s);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = read_status();
+    if (e != hipSuccess) return bail_hip(e, "mhs_values_plan_create: classify");
+    if (status[5] != NONE) return bad_row(5, "C's pattern misses a column of the product A*B");
+    int off = 0;
+    for (int c = 0; c < VAL_NCLASS; ++c) {
+        p->counts.rows[c] = h_cnt[c * BINCNT_STRIDE];
+        p->counts.need[c] = h_cnt[(2 * VAL_NCLASS + c) * BINCNT_STRIDE];
+        p->list_off[c] = off;
+        off += p->counts.rows[c];
+    }
+    memcpy(&p->products, &h_cnt[3 * VAL_NCLASS * BINCNT_STRIDE], sizeof p->products);
+    p->plan = plan_values(p->counts);
+    *out = p;
+    return MHS_OK;
+}
+
+int mhs_spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, double* Cval, double* ms) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: null plan");
+    if ((p->nnzA > 0 && !Aval) || (p->nnzB > 0 && !Bval) || (p->nnzC > 0 && !Cval))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: null value array");
+    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: the plan belongs to another device");
+    MHS_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const ValArgs a{p->pat.Aptr, p->pat.Acol, Aval, p->pat.Bptr, p->pat.Bcol, Bval, p->pat.Cptr, p->pat.Ccol, Cval};
+    if (ms) MHS_HIP(hipEventRecord(p->ev[0], s));
+    for (int i = 0; i < p->plan.n; ++i) {
+        const ValLaunch& l = p->plan.launch[i];
+        issue_values(l, a, p->lists + p->list_off[l.cls], s);
+    }
+    MHS_HIP(hipGetLastError());
+    if (ms) {
+        float f = 0;
+        MHS_HIP(hipEventRecord(p->ev[1], s));
+        MHS_HIP(hipEventSynchronize(p->ev[1]));
+        MHS_HIP(hipEventElapsedTime(&f, p->ev[0], p->ev[1]));
+        *ms = f;
+    } else if (ctx->sync) {
+        MHS_HIP(hipStreamSynchronize(s));
+    }
+    return MHS_OK;
+}
+
+int mhs_values_plan_info(const mhs_values_plan* p, mhs_values_info* info) {
+    if (!p || !info) return MHS_ERR_INVALID;
+    memset(info, 0, sizeof *info);
+    for (int c = 0; c < VAL_NCLASS; ++c) info->rows[c] = p->counts.rows[c];
+    info->products = p->products;
+    info->nnzC = p->nnzC;
+    info->plan_bytes = (int64_t)p->mem_bytes;
+    return MHS_OK;
+}
+
+void mhs_values_plan_destroy(mhs_ctx* ctx, mhs_values_plan* p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);  // calls still queued read the lists
+    else (void)hipDeviceSynchronize();
+    for (hipEvent_t ev : p->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    if (p->mem) (void)hipFree(p->mem);
+    (void)hipGetLastError();
+    delete p;
 }
 
 int mhs_transpose(mhs_ctx* ctx, const mhs_csr* A, mhs_csr* At) {

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mhs_numplan.hpp"
+#include "mhs_valplan.hpp"
 
 namespace mhs {
 
@@ -149,6 +150,32 @@ void launch_add_offset(int* p, int n, int off, hipStream_t s);
 hipError_t transpose_csr(const Csr& A, int* tptr, int* tcol, double* tval, void* tmp, size_t* tmp_bytes,
                          hipStream_t s);
 hipError_t init_kernel_attributes();
+// mhs_values.hip: values-only SpGEMM on a kept pattern (mhs_spgemm_values; classes and plan in mhs_valplan.hpp).
+// The six pattern arrays a values plan borrows ...
+struct ValPattern {
+    int M;
+    const int *Aptr, *Acol, *Bptr, *Bcol, *Cptr, *Ccol;
+};
+// ... and what a hot call's kernels take: the patterns and the call's three value arrays.
+struct ValArgs {
+    const int *Aptr, *Acol;
+    const double* Aval;
+    const int *Bptr, *Bcol;
+    const double* Bval;
+    const int *Cptr, *Ccol;
+    double* Cval;
+};
+constexpr int VAL_CNT_INTS = (3 * VAL_NCLASS + 1) * BINCNT_STRIDE;
+hipError_t init_values_attributes();  // (called by init_kernel_attributes)
+// Plan creation.  bad: a device int holding the first offending row (atomicMin; INT_MAX: none).
+void launch_val_check_ptr(const int* ptr, int M, int nnz, int* bad, hipStream_t s);
+void launch_val_check_cols(const int* ptr, const int* col, int M, int ncols, bool strict, int* bad, hipStream_t s);
+// cnt: VAL_CNT_INTS ints zeroed by the caller -- 3 * VAL_NCLASS counters BINCNT_STRIDE ints apart (rows, list
+// cursors, LDS need per class), then the 64-bit product count; lists: M ints, class c's rows at the prefix of the counts before it
+void launch_val_classify(const ValPattern& p, int* cnt, int* lists, hipStream_t s);
+void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s);
+// One launch of a values plan (plan_values) over its class's row list, on `s`.
+void issue_values(const ValLaunch& l, const ValArgs& a, const int* list, hipStream_t s);
 // device address of the probe-conflict counter (nullptr unless built with MHS_PROBE_STATS=1)
 hipError_t probe_counter(unsigned long long** dev);
 // mhs_hbm.hip: the streaming kernels of mhs_hbm_peak on the current device (gbps[3]: copy, read, write)

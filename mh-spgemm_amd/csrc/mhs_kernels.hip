@@ -4442,6 +4442,7 @@ hipError_t init_kernel_attributes() {
                           (const void*)k_num_wave<NUM_W16_BYTES, true, false, true>};
     for (const void* k : wave)
         if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    if (e == hipSuccess) e = init_values_attributes();  // the values-only block kernels (mhs_values.hip)
     return e;
 }
 

@@ -1,0 +1,183 @@
+// mhs_valplan.hpp -- values-only SpGEMM (mhs_spgemm_values): row classes and the launch plan, as data.
+//
+// A values plan recomputes C.val on a kept pattern: every row of C is told its sorted columns and
+// only has to find each product's slot.  How a row finds it is its class, a function of the row's
+// C length n, its C column span (last - first + 1) and its product count:
+//
+//   VC_NONE          n == 0: nothing to compute
+//   VC_TEAM          short rows: a team of VAL_TEAM_LANES lanes per row, 8 rows per wave64; the row's
+//                    columns staged in the team's LDS slice, slot by binary search, FP64 sums beside them
+//   VC_WAVE_DIRECT   one wave64 per row, span-indexed sums acc[col - first] in the wave's LDS slice:
+//   VC_BLOCK_DIRECT  ... or one block per row with up to the whole 160 KiB.  No search; the sums are
+//                    gathered through C.col afterwards
+//   VC_WAVE_SEARCH   span too wide: the row's C.col staged in LDS once, slot by binary search,
+//   VC_BLOCK_SEARCH  position-indexed sums (12 bytes per C entry)
+//   VC_GLOBAL        rows past one workgroup's 160 KiB (and long rows without products): the row's
+//                    Cval segment zeroed, C.col searched in HBM, sums by HBM atomics
+//
+// LDS arithmetic (gfx950: 160 KiB per CU and per workgroup, 32 waves per CU):
+//   team    12 B x n <= 768 B per row, 32 rows per 256-thread block: <= 24 KiB, 6 blocks per CU
+//   wave    VAL_WAVE_BYTES = 8 KiB per wave, 4 waves per block: span <= 1024 direct, n <= 682 searched;
+//           at the cap 4 blocks (16 waves) per CU
+//   block   VAL_BLOCK_BYTES = 159,744: span <= 19,968 direct, n <= 13,312 searched
+//   The wave and block kernels also hold a stage of A entries in static LDS (walk_staged): 1 KiB per
+//   wave, 4 KiB (VAL_STAGE_BYTES) per block -- what the block classes' dynamic LDS leaves of the 160 KiB.
+// A launch declares what its class's largest row needs (ValCounts::need, k_val_classify's maximum),
+// not the cap, so banded matrices run at the occupancy their own spans allow.
+//
+// plan_values(counts) is the whole launch plan of a hot call; issue_values (mhs_values.hip) turns one
+// ValLaunch and the call's arrays into a kernel launch.  No pointer and no HIP type in here:
+// tests/valplan_check.cpp runs it on the host.
+#pragma once
+#include "mhs_shape.hpp"
+
+namespace mhs {
+
+enum ValClass : int {
+    VC_NONE = 0,
+    VC_TEAM = 1,
+    VC_WAVE_DIRECT = 2,
+    VC_WAVE_SEARCH = 3,
+    VC_BLOCK_DIRECT = 4,
+    VC_BLOCK_SEARCH = 5,
+    VC_GLOBAL = 6,
+    VC_COUNT = 7,
+};
+constexpr int VAL_NCLASS = 8;  // capacity of the per-class arrays (mhs_values_info::rows)
+
+constexpr int VAL_TEAM_LANES = 8;      // lanes per team row
+constexpr int VAL_TEAM_ROWS = 256 / VAL_TEAM_LANES;  // rows per 256-thread block
+constexpr int VAL_TEAM_NMAX = 64;      // C entries of a team row (6 search steps)
+constexpr int VAL_TEAM_PMAX = 512;     // products of a team row (64 per lane)
+constexpr int VAL_WAVE_BYTES = 8192;   // LDS per wave of the wave classes
+constexpr int VAL_WAVE_PMAX = 2048;    // products of a wave row (32 per lane, half a team lane's 64); past it a block's 4x lanes
+constexpr int VAL_STAGE = 256;          // A entries a block stages at a time (16 B each, static LDS)
+constexpr int VAL_STAGE_BYTES = VAL_STAGE * 16;
+constexpr int VAL_BLOCK_BYTES = LDS_MAX_C - VAL_STAGE_BYTES;  // dynamic LDS of the block classes
+constexpr int VAL_DENSE_RATIO = 16;    // span <= 16 n: zeroing and gathering the span costs less than searching
+constexpr int VAL_BLOCK_SMALL = 32768; // block launches of at most this much LDS run 256 threads, else 1024
+constexpr int VAL_GROUP = 16;          // lanes that share one A entry in the wave / block / global walks
+
+// LDS bytes of one row, per method
+__host__ __device__ constexpr long long val_lds_search(long long n) { return 12 * ((n + 1) & ~1LL); }  // sums, then columns
+__host__ __device__ constexpr long long val_lds_direct(long long span) { return 8 * span; }
+
+constexpr int VAL_WAVE_DIRECT_SPAN = VAL_WAVE_BYTES / 8;      // 1024
+constexpr int VAL_WAVE_SEARCH_N = VAL_WAVE_BYTES / 12 & ~1;   // 682
+constexpr int VAL_BLOCK_DIRECT_SPAN = VAL_BLOCK_BYTES / 8;    // 19968
+constexpr int VAL_BLOCK_SEARCH_N = VAL_BLOCK_BYTES / 12 & ~1; // 13312
+static_assert(val_lds_search(VAL_TEAM_NMAX) * VAL_TEAM_ROWS <= 65536, "team launch below the attribute threshold");
+static_assert(val_lds_direct(VAL_WAVE_DIRECT_SPAN) <= VAL_WAVE_BYTES && val_lds_search(VAL_WAVE_SEARCH_N) <= VAL_WAVE_BYTES,
+              "wave rows fit the wave slice");
+static_assert(val_lds_direct(VAL_BLOCK_DIRECT_SPAN) <= VAL_BLOCK_BYTES &&
+                  val_lds_search(VAL_BLOCK_SEARCH_N) <= VAL_BLOCK_BYTES && VAL_BLOCK_BYTES + VAL_STAGE_BYTES <= 163840,
+              "block rows fit one workgroup");
+
+// The class of a row: n C entries over `span` columns, `products` products (saturated).
+__host__ __device__ inline int val_class(int n, long long span, long long products) {
+    if (n <= 0) return VC_NONE;
+    if (n <= VAL_TEAM_NMAX && products <= VAL_TEAM_PMAX) return VC_TEAM;
+    if (products <= 0) return VC_GLOBAL;  // zero fill only: no LDS, nothing staged
+    const bool wave = products <= VAL_WAVE_PMAX;
+    if (wave && span <= VAL_WAVE_DIRECT_SPAN) return VC_WAVE_DIRECT;
+    if (span <= VAL_BLOCK_DIRECT_SPAN && span <= (long long)VAL_DENSE_RATIO * n) return VC_BLOCK_DIRECT;
+    if (wave && n <= VAL_WAVE_SEARCH_N) return VC_WAVE_SEARCH;
+    if (span <= VAL_BLOCK_DIRECT_SPAN) return VC_BLOCK_DIRECT;
+    if (n <= VAL_BLOCK_SEARCH_N) return VC_BLOCK_SEARCH;
+    return VC_GLOBAL;
+}
+// LDS bytes a row needs in its class (0: none)
+__host__ __device__ inline int val_row_need(int cls, int n, long long span) {
+    switch (cls) {
+    case VC_TEAM:
+    case VC_WAVE_SEARCH:
+    case VC_BLOCK_SEARCH: return (int)val_lds_search(n);
+    case VC_WAVE_DIRECT:
+    case VC_BLOCK_DIRECT: return (int)val_lds_direct(span);
+    default: return 0;
+    }
+}
+// The most a row of the class can need
+constexpr int val_class_cap(int cls) {
+    return cls == VC_TEAM ? (int)val_lds_search(VAL_TEAM_NMAX)
+           : cls == VC_WAVE_DIRECT || cls == VC_WAVE_SEARCH ? VAL_WAVE_BYTES
+           : cls == VC_BLOCK_DIRECT || cls == VC_BLOCK_SEARCH ? VAL_BLOCK_BYTES
+                                                              : 0;
+}
+
+// What k_val_classify counts: rows per class and the largest row's LDS need per class.
+struct ValCounts {
+    int rows[VAL_NCLASS];
+    int need[VAL_NCLASS];
+};
+
+enum ValKernel : int {
+    VK_TEAM,          // k_val_team
+    VK_WAVE_DIRECT,   // k_val_wave<direct>
+    VK_WAVE_SEARCH,   // k_val_wave<search>
+    VK_BLOCK_DIRECT,  // k_val_block<T, direct>
+    VK_BLOCK_SEARCH,  // k_val_block<T, search>
+    VK_GLOBAL,        // k_val_global
+};
+
+// One launch.  `region`: LDS bytes per row in flight (team slice, wave slice, or the block's all).
+struct ValLaunch {
+    int kernel;  // ValKernel
+    int cls;     // the class whose list it walks
+    int grid, block, lds;
+    int region;
+    int count;
+};
+constexpr int VAL_PLAN_MAX = 8;
+struct ValPlan {
+    int n;
+    ValLaunch launch[VAL_PLAN_MAX];
+};
+
+constexpr int VAL_TEAM_GRID = 16384;   // block caps (rows past them are walked grid-stride)
+constexpr int VAL_WAVE_GRID = 16384;
+constexpr int VAL_BLOCK_GRID = 4096;
+constexpr int VAL_GLOBAL_GRID = 1024;
+
+inline int val_round(int need, int step, int cap) {
+    const int b = (need + step - 1) / step * step;
+    return need <= 0 || b > cap ? cap : b;
+}
+
+// The launches of a hot call, heaviest rows first (they all go on the call's stream).
+inline ValPlan plan_values(const ValCounts& c) {
+    ValPlan p{};
+    auto add = [&](int kernel, int cls, long long blocks, int cap, int threads, int lds, int region) {
+        if (p.n >= VAL_PLAN_MAX) return;
+        ValLaunch& l = p.launch[p.n++];
+        l.kernel = kernel;
+        l.cls = cls;
+        l.grid = (int)(blocks < cap ? blocks : cap);
+        l.block = threads;
+        l.lds = lds;
+        l.region = region;
+        l.count = c.rows[cls];
+    };
+    if (c.rows[VC_GLOBAL] > 0) add(VK_GLOBAL, VC_GLOBAL, c.rows[VC_GLOBAL], VAL_GLOBAL_GRID, 1024, 0, 0);
+    for (int k = 0; k < 2; ++k) {
+        const int cls = k ? VC_BLOCK_DIRECT : VC_BLOCK_SEARCH;
+        if (c.rows[cls] <= 0) continue;
+        const int lds = val_round(c.need[cls], 2048, VAL_BLOCK_BYTES);
+        add(k ? VK_BLOCK_DIRECT : VK_BLOCK_SEARCH, cls, c.rows[cls], VAL_BLOCK_GRID, lds <= VAL_BLOCK_SMALL ? 256 : 1024, lds, lds);
+    }
+    for (int k = 0; k < 2; ++k) {
+        const int cls = k ? VC_WAVE_DIRECT : VC_WAVE_SEARCH;
+        if (c.rows[cls] <= 0) continue;
+        const int region = val_round(c.need[cls], 256, VAL_WAVE_BYTES);
+        add(k ? VK_WAVE_DIRECT : VK_WAVE_SEARCH, cls, ((long long)c.rows[cls] + WPB - 1) / WPB, VAL_WAVE_GRID, 64 * WPB, WPB * region,
+            region);
+    }
+    if (c.rows[VC_TEAM] > 0) {
+        const int region = val_round(c.need[VC_TEAM], 24, val_class_cap(VC_TEAM));
+        add(VK_TEAM, VC_TEAM, ((long long)c.rows[VC_TEAM] + VAL_TEAM_ROWS - 1) / VAL_TEAM_ROWS, VAL_TEAM_GRID, 256,
+            VAL_TEAM_ROWS * region, region);
+    }
+    return p;
+}
+
+}  // namespace mhs

@@ -1,0 +1,413 @@
+// mhs_values.hip -- values-only SpGEMM: recompute C.val on a kept pattern (mhs_spgemm_values).
+//
+// Plan creation (once per pattern): k_val_check_ptr and k_val_check_cols validate the three
+// patterns, k_val_classify puts every row of C into its class list (mhs_valplan.hpp),
+// k_val_verify walks every product's column once and looks it up in its C row.
+// Hot call: one value kernel per non-empty class.  Each walks A's row, then B's rows, reads
+// Aval / Bval only for values, and -- told the row's sorted columns -- only finds each product's
+// slot: by subtraction (direct classes) or by binary search (team, search and global classes).
+// Sums are FP64 atomics: ds_add_f64 in LDS, global_atomic_add_f64 in the global class.
+#include "mhs_internal.hpp"
+
+#include <climits>
+
+namespace mhs {
+namespace {
+
+// Ordering point for LDS traffic between lanes of one wave (a wave's LDS operations are
+// performed in issue order; only the compiler must not move accesses across it).
+__device__ __forceinline__ void vwave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Position of column c in the ascending cols[0, n), or -1.
+__device__ __forceinline__ int find_slot(const int* cols, int n, int c) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cols[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < n && cols[lo] == c ? lo : -1;
+}
+
+// The products of row `row`: group g of ng groups takes A entries g, g + ng, ...; its G lanes
+// stride over the B row.  add(column, value) per product.
+template <int G, class F>
+__device__ __forceinline__ void walk_products(const ValArgs& a, int row, int g, int ng, int t, F add) {
+    const int ae = a.Aptr[row + 1];
+    for (int k = a.Aptr[row] + g; k < ae; k += ng) {
+        const int ac = a.Acol[k];
+        const double av = a.Aval[k];
+        const int be = a.Bptr[ac + 1];
+        for (int j = a.Bptr[ac] + t; j < be; j += G) add(a.Bcol[j], av * a.Bval[j]);
+    }
+}
+// The same products for a wave's or a block's row, with memory-level parallelism: the row's `lanes`
+// lanes first stage up to CH of its A entries as (B row start, length, A value) in LDS -- one
+// dependent load chain (A.col -> B.ptr) per CH entries, not one per entry -- then each group of G
+// lanes takes staged entries g, g + ng, ... and reads its B row VAL_PIECES G-wide pieces at a time,
+// every load issued before the first sum.  pre() runs once, between the first stage's loads and the
+// sync that publishes them (the row's zero fill rides on that sync).
+template <int CH>
+struct ValStage {
+    int bs[CH], len[CH];
+    double av[CH];
+};
+constexpr int VAL_PIECES = 8;
+template <int G, int CH, class Sync, class Pre, class F>
+__device__ __forceinline__ void walk_staged(const ValArgs& a, int row, int t, int lanes, ValStage<CH>& d, Sync sync, Pre pre,
+                                            F add) {
+    const int g = t / G, ng = lanes / G, tl = t % G;
+    const int ae = a.Aptr[row + 1], a0 = a.Aptr[row];
+    if (a0 >= ae) {
+        pre();
+        sync();
+        return;
+    }
+    for (int k0 = a0; k0 < ae; k0 += CH) {
+        const int cnt = ae - k0 < CH ? ae - k0 : CH;
+        if (t < cnt) {
+            const int ac = a.Acol[k0 + t];
+            const int bs = a.Bptr[ac];
+            d.bs[t] = bs;
+            d.len[t] = a.Bptr[ac + 1] - bs;
+            d.av[t] = a.Aval[k0 + t];
+        }
+        if (k0 == a0) pre();
+        sync();
+        for (int e = g; e < cnt; e += ng) {
+            const int bs = d.bs[e], len = d.len[e];
+            const double av = d.av[e];
+            for (int j = tl; j < len; j += VAL_PIECES * G) {
+                int c[VAL_PIECES];
+                double v[VAL_PIECES];
+#pragma unroll
+                for (int u = 0; u < VAL_PIECES; ++u) {
+                    const int jj = j + u * G;
+                    const bool in = jj < len;
+                    c[u] = in ? a.Bcol[bs + jj] : -1;
+                    v[u] = in ? a.Bval[bs + jj] : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < VAL_PIECES; ++u)
+                    if (c[u] >= 0) add(c[u], av * v[u]);
+            }
+        }
+        sync();
+    }
+}
+// ... without values (plan creation)
+template <int G, class F>
+__device__ __forceinline__ void walk_columns(const ValPattern& p, int row, int g, int ng, int t, F see) {
+    const int ae = p.Aptr[row + 1];
+    for (int k = p.Aptr[row] + g; k < ae; k += ng) {
+        const int ac = p.Acol[k];
+        const int be = p.Bptr[ac + 1];
+        for (int j = p.Bptr[ac] + t; j < be; j += G) see(p.Bcol[j]);
+    }
+}
+
+// ------------------------------------------------------------- validation ---
+// ptr[0] == 0, ptr monotone, ptr[M] == nnz, for A, B and C (which = 0, 1, 2): first bad row per matrix.
+__global__ __launch_bounds__(256) void k_val_check_ptr(const int* __restrict__ ptr, int M, int nnz, int* __restrict__ bad) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < M; i += gridDim.x * 256) {
+        const int s = ptr[i], e = ptr[i + 1];
+        bool ok = s >= 0 && s <= e && e <= nnz;
+        if (i == 0) ok = ok && s == 0;
+        if (i == M - 1) ok = ok && e == nnz;
+        if (!ok) atomicMin(bad, i);
+    }
+}
+// One wave per row: columns in [0, ncols); strict: ascending without duplicates.
+__global__ __launch_bounds__(256) void k_val_check_cols(const int* __restrict__ ptr, const int* __restrict__ col, int M,
+                                                        int ncols, int strict, int* __restrict__ bad) {
+    const int lane = threadIdx.x & 63;
+    for (int i = blockIdx.x * WPB + (threadIdx.x >> 6); i < M; i += gridDim.x * WPB) {
+        const int s = ptr[i], e = ptr[i + 1];
+        bool ok = true;
+        for (int p = s + lane; p < e; p += 64) {
+            const int c = col[p];
+            ok = ok && c >= 0 && c < ncols;
+            if (strict && p > s) ok = ok && col[p - 1] < c;
+        }
+        if (!ok) atomicMin(bad, i);
+    }
+}
+
+// --------------------------------------------------------------- classify ---
+// One thread per row of C.  FILL false: count the rows and the largest LDS need per class (one
+// reservation per block and class, counters one per 128-byte line).  FILL true: write the rows into
+// their class lists, class c's list at the prefix of the counts before it.
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_val_classify(ValPattern p, int* __restrict__ cnt, int* __restrict__ lists) {
+    __shared__ int s_cnt[VAL_NCLASS], s_need[VAL_NCLASS], s_base[VAL_NCLASS];
+    __shared__ unsigned long long s_prod;
+    for (int base = blockIdx.x * 256; base < p.M; base += gridDim.x * 256) {
+        if (threadIdx.x < VAL_NCLASS) s_cnt[threadIdx.x] = s_need[threadIdx.x] = 0;
+        if (threadIdx.x == 0) s_prod = 0;
+        __syncthreads();
+        const int i = base + threadIdx.x;
+        int cls = -1, rank = 0;
+        if (i < p.M) {
+            const int s = p.Cptr[i], e = p.Cptr[i + 1];
+            const int n = e - s;
+            long long span = 0, products = 0;
+            if (n > 0) {
+                span = (long long)p.Ccol[e - 1] - p.Ccol[s] + 1;
+                for (int k = p.Aptr[i]; k < p.Aptr[i + 1]; ++k) {
+                    const int ac = p.Acol[k];
+                    products += p.Bptr[ac + 1] - p.Bptr[ac];
+                }
+            }
+            cls = val_class(n, span, products);
+            rank = atomicAdd(&s_cnt[cls], 1);
+            if (!FILL) {
+                atomicMax(&s_need[cls], val_row_need(cls, n, span));
+                if (products > 0) atomicAdd(&s_prod, (unsigned long long)products);
+            }
+        }
+        __syncthreads();
+        if (!FILL && threadIdx.x == 0 && s_prod > 0)  // the pattern's product count (mhs_values_info)
+            atomicAdd((unsigned long long*)(cnt + 3 * VAL_NCLASS * BINCNT_STRIDE), s_prod);
+        if (threadIdx.x < VAL_NCLASS && s_cnt[threadIdx.x] > 0) {
+            const int c = threadIdx.x;
+            if (FILL) {
+                int off = 0;
+                for (int b = 0; b < c; ++b) off += cnt[b * BINCNT_STRIDE];
+                s_base[c] = off + atomicAdd(&cnt[(VAL_NCLASS + c) * BINCNT_STRIDE], s_cnt[c]);
+            } else {
+                atomicAdd(&cnt[c * BINCNT_STRIDE], s_cnt[c]);
+                atomicMax(&cnt[(2 * VAL_NCLASS + c) * BINCNT_STRIDE], s_need[c]);
+            }
+        }
+        __syncthreads();
+        if (FILL && cls >= 0) lists[s_base[cls] + rank] = i;
+        __syncthreads();
+    }
+}
+
+// ----------------------------------------------------------------- verify ---
+// Pattern-only walk of the shape of the value kernels: one wave per row, every product's column
+// must be in the row's C columns.
+__global__ __launch_bounds__(256) void k_val_verify(ValPattern p, int* __restrict__ bad) {
+    const int lane = threadIdx.x & 63;
+    for (int i = blockIdx.x * WPB + (threadIdx.x >> 6); i < p.M; i += gridDim.x * WPB) {
+        const int s = p.Cptr[i], n = p.Cptr[i + 1] - s;
+        bool ok = true;
+        walk_columns<VAL_GROUP>(p, i, lane / VAL_GROUP, 64 / VAL_GROUP, lane % VAL_GROUP,
+                                [&](int c) { ok = ok && find_slot(p.Ccol + s, n, c) >= 0; });
+        if (!ok) atomicMin(bad, i);
+    }
+}
+
+// ---------------------------------------------------------- value kernels ---
+// Searched sums of one row by `lanes` lanes (lane t): cols / acc are the row's LDS slice.
+// walk(pre, add) runs pre() and a sync, then add(column, value) per product; sync orders the steps
+// (a wave's or a block's).
+template <class Sync, class Walk>
+__device__ __forceinline__ void row_search(const ValArgs& a, int s, int n, double* acc, int* cols, int t, int lanes, Sync sync,
+                                           Walk walk) {
+    walk(
+        [&] {
+            for (int p = t; p < n; p += lanes) {
+                cols[p] = a.Ccol[s + p];
+                acc[p] = 0.0;
+            }
+        },
+        [&](int c, double v) {
+            const int slot = find_slot(cols, n, c);
+            if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64
+        });
+    sync();
+    for (int p = t; p < n; p += lanes) a.Cval[s + p] = acc[p];
+    sync();
+}
+// Span-indexed sums of one row: acc[col - first], gathered through C.col afterwards.
+template <class Sync, class Walk>
+__device__ __forceinline__ void row_direct(const ValArgs& a, int s, int n, int first, int span, double* acc, int t, int lanes,
+                                           Sync sync, Walk walk) {
+    walk(
+        [&] {
+            for (int p = t; p < span; p += lanes) acc[p] = 0.0;
+        },
+        [&](int c, double v) {
+            const unsigned slot = (unsigned)(c - first);
+            if (slot < (unsigned)span) atomicAdd(&acc[slot], v);  // ds_add_f64
+        });
+    sync();
+    for (int p = t; p < n; p += lanes) a.Cval[s + p] = acc[a.Ccol[s + p] - first];
+    sync();
+}
+
+// Team class: VAL_TEAM_LANES lanes per row, the teams of a wave in step (wave-level ordering).
+__global__ __launch_bounds__(256) void k_val_team(ValArgs a, const int* __restrict__ list, int count, int region) {
+    extern __shared__ __align__(16) char lds[];
+    const int team = threadIdx.x / VAL_TEAM_LANES, t = threadIdx.x % VAL_TEAM_LANES;
+    const int ne = region / 12;
+    double* acc = (double*)(lds + (size_t)team * region);
+    int* cols = (int*)(acc + ne);
+    for (int base = blockIdx.x * VAL_TEAM_ROWS; base < count; base += gridDim.x * VAL_TEAM_ROWS) {
+        const int idx = base + team;
+        const int row = idx < count ? list[idx] : -1;
+        int s = 0, n = 0;
+        if (row >= 0) {
+            s = a.Cptr[row];
+            n = a.Cptr[row + 1] - s;
+            if (n > ne) n = 0;  // (not this plan's pattern: leave the row alone rather than overrun the slice)
+        }
+        for (int p = t; p < n; p += VAL_TEAM_LANES) {
+            cols[p] = a.Ccol[s + p];
+            acc[p] = 0.0;
+        }
+        vwave_sync();
+        if (n > 0)
+            walk_products<VAL_TEAM_LANES>(a, row, 0, 1, t, [&](int c, double v) {
+                const int slot = find_slot(cols, n, c);
+                if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64
+            });
+        vwave_sync();
+        for (int p = t; p < n; p += VAL_TEAM_LANES) a.Cval[s + p] = acc[p];
+        vwave_sync();
+    }
+}
+
+// Wave classes: one wave64 per row, WPB rows per block.
+template <bool DIRECT>
+__global__ __launch_bounds__(256) void k_val_wave(ValArgs a, const int* __restrict__ list, int count, int region) {
+    extern __shared__ __align__(16) char lds[];
+    __shared__ ValStage<64> stage[WPB];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double* acc = (double*)(lds + (size_t)wave * region);
+    auto sync = [] { vwave_sync(); };
+    for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB) {
+        const int row = list[idx];
+        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP>(a, row, lane, 64, stage[wave], sync, pre, add); };
+        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
+        if (n <= 0) continue;
+        if constexpr (DIRECT) {
+            const int first = a.Ccol[s];
+            const long long span = (long long)a.Ccol[s + n - 1] - first + 1;
+            if (span <= 0 || span * 8 > region) continue;  // (not this plan's pattern)
+            row_direct(a, s, n, first, (int)span, acc, lane, 64, sync, walk);
+        } else {
+            const int ne = region / 12;
+            if (n > ne) continue;
+            row_search(a, s, n, acc, (int*)(acc + ne), lane, 64, sync, walk);
+        }
+    }
+}
+
+// Block classes: one block of T threads per row, up to the whole 160 KiB (VAL_BLOCK_BYTES dynamic + the stage).
+template <int T, bool DIRECT>
+__global__ __launch_bounds__(T) void k_val_block(ValArgs a, const int* __restrict__ list, int count, int region) {
+    extern __shared__ __align__(16) char lds[];
+    __shared__ ValStage<VAL_STAGE> stage;
+    double* acc = (double*)lds;
+    const int t = threadIdx.x;
+    auto sync = [] { __syncthreads(); };
+    // Consecutive rows read the same B rows, and blocks go to the 8 XCDs in turn: XCD x (blocks x, x + 8, ...)
+    // walks its own stretch of the list, in proportion to its blocks, so neighbours meet in one L2.
+    int lo = 0, hi = count, first_j = blockIdx.x, step = gridDim.x;
+    if (gridDim.x >= 8) {
+        const int xcd = blockIdx.x & 7;
+        int before = 0;
+        for (int y = 0; y < xcd; ++y) before += (gridDim.x - y + 7) >> 3;
+        step = (gridDim.x - xcd + 7) >> 3;
+        first_j = blockIdx.x >> 3;
+        lo = (int)((long long)count * before / gridDim.x);
+        hi = (int)((long long)count * (before + step) / gridDim.x);
+    }
+    for (int idx = lo + first_j; idx < hi; idx += step) {
+        const int row = list[idx];
+        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP>(a, row, t, T, stage, sync, pre, add); };
+        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
+        if (n <= 0) continue;
+        if constexpr (DIRECT) {
+            const int first = a.Ccol[s];
+            const long long span = (long long)a.Ccol[s + n - 1] - first + 1;
+            if (span <= 0 || span * 8 > region) continue;
+            row_direct(a, s, n, first, (int)span, acc, t, T, sync, walk);
+        } else {
+            const int ne = region / 12;
+            if (n > ne) continue;
+            row_search(a, s, n, acc, (int*)(acc + ne), t, T, sync, walk);
+        }
+    }
+}
+
+// Global class: the row's Cval segment is the accumulator.
+__global__ __launch_bounds__(1024) void k_val_global(ValArgs a, const int* __restrict__ list, int count) {
+    const int t = threadIdx.x;
+    for (int idx = blockIdx.x; idx < count; idx += gridDim.x) {
+        const int row = list[idx];
+        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
+        for (int p = t; p < n; p += 1024) a.Cval[s + p] = 0.0;
+        __threadfence();
+        __syncthreads();
+        walk_products<VAL_GROUP>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, double v) {
+            const int slot = find_slot(a.Ccol + s, n, c);
+            if (slot >= 0) unsafeAtomicAdd(&a.Cval[s + slot], v);  // global_atomic_add_f64
+        });
+    }
+}
+
+int blocks_for(long long items, int per, int cap) {
+    long long b = (items + per - 1) / per;
+    if (b < 1) b = 1;
+    return (int)(b < cap ? b : cap);
+}
+
+}  // namespace
+
+hipError_t init_values_attributes() {
+    // the 1024-thread block kernels may take the whole 160 KiB (the 256-thread ones run at most VAL_BLOCK_SMALL)
+    hipError_t e = hipFuncSetAttribute((const void*)k_val_block<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       VAL_BLOCK_BYTES);
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)k_val_block<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                VAL_BLOCK_BYTES);
+    return e;
+}
+
+void launch_val_check_ptr(const int* ptr, int M, int nnz, int* bad, hipStream_t s) {
+    if (M <= 0) return;
+    hipLaunchKernelGGL(k_val_check_ptr, dim3(blocks_for(M, 256, 4096)), dim3(256), 0, s, ptr, M, nnz, bad);
+}
+void launch_val_check_cols(const int* ptr, const int* col, int M, int ncols, bool strict, int* bad, hipStream_t s) {
+    if (M <= 0) return;
+    hipLaunchKernelGGL(k_val_check_cols, dim3(blocks_for(M, WPB, 16384)), dim3(256), 0, s, ptr, col, M, ncols, strict ? 1 : 0,
+                       bad);
+}
+void launch_val_classify(const ValPattern& p, int* cnt, int* lists, hipStream_t s) {
+    if (p.M <= 0) return;
+    const int grid = blocks_for(p.M, 256, 16384);
+    hipLaunchKernelGGL(k_val_classify<false>, dim3(grid), dim3(256), 0, s, p, cnt, lists);
+    hipLaunchKernelGGL(k_val_classify<true>, dim3(grid), dim3(256), 0, s, p, cnt, lists);
+}
+void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s) {
+    if (p.M <= 0) return;
+    hipLaunchKernelGGL(k_val_verify, dim3(blocks_for(p.M, WPB, 16384)), dim3(256), 0, s, p, bad);
+}
+
+void issue_values(const ValLaunch& l, const ValArgs& a, const int* list, hipStream_t s) {
+    const dim3 g(l.grid), b(l.block);
+    switch (l.kernel) {
+    case VK_TEAM: hipLaunchKernelGGL(k_val_team, g, b, l.lds, s, a, list, l.count, l.region); break;
+    case VK_WAVE_DIRECT: hipLaunchKernelGGL(k_val_wave<true>, g, b, l.lds, s, a, list, l.count, l.region); break;
+    case VK_WAVE_SEARCH: hipLaunchKernelGGL(k_val_wave<false>, g, b, l.lds, s, a, list, l.count, l.region); break;
+    case VK_BLOCK_DIRECT:
+        if (l.block == 1024) hipLaunchKernelGGL((k_val_block<1024, true>), g, b, l.lds, s, a, list, l.count, l.region);
+        else hipLaunchKernelGGL((k_val_block<256, true>), g, b, l.lds, s, a, list, l.count, l.region);
+        break;
+    case VK_BLOCK_SEARCH:
+        if (l.block == 1024) hipLaunchKernelGGL((k_val_block<1024, false>), g, b, l.lds, s, a, list, l.count, l.region);
+        else hipLaunchKernelGGL((k_val_block<256, false>), g, b, l.lds, s, a, list, l.count, l.region);
+        break;
+    case VK_GLOBAL: hipLaunchKernelGGL(k_val_global, g, b, 0, s, a, list, l.count); break;
+    }
+}
+
+}  // namespace mhs

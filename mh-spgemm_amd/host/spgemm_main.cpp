@@ -1,7 +1,7 @@
 // spgemm_main.cpp -- the `spgemm <file.mtx>` driver (reference src/main.cu:74-217)
 // on top of the C-ABI, printing the reference's stdout lines.
 //
-//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] <file.mtx>
+//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -16,6 +16,9 @@
 //             DIR/Gflops_rocsparse.csv (:173-184, :201-213; the reference's data/)
 //   --cache   read <file.mtx>.mhscsr (binary CSR, stamped with the .mtx's size and
 //             mtime) instead of parsing the text; written on the first run
+//   --reuse N after the product, a values plan on C's pattern (mhs_values_plan_create) and N values-only
+//             calls on the same A and B (mhs_spgemm_values); their mean time on a line of its own, and
+//             with --check the recomputed values against the product's own by CSR::operator==
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -56,7 +59,7 @@ static void recycle(Tool& tools, CSR& C) {
 }
 
 int main(int argc, char** argv) {
-    int iters = 1, warmup = 1;
+    int iters = 1, warmup = 1, reuse = 0;
     bool aat = false, vendor = false, check = false, cache = false;
     std::string csv;
     const char* filename = nullptr;
@@ -69,12 +72,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--check")) check = vendor = true;
         else if (!std::strcmp(argv[i], "--csv") && i + 1 < argc) csv = argv[++i];
         else if (!std::strcmp(argv[i], "--cache")) cache = true;
+        else if (!std::strcmp(argv[i], "--reuse") && i + 1 < argc) reuse = std::atoi(argv[++i]);
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
-    if (bad || !filename || iters < 1 || warmup < 0) {
+    if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -156,6 +160,31 @@ int main(int argc, char** argv) {
                 mhs_vendor_free(&v);
             } else {
                 std::printf("rocSPARSE failed!!! (%s)\n", err);
+            }
+        }
+        if (reuse > 0) {
+            CSR full;  // the product's own values, before the values calls overwrite C.d_val
+            if (check) {
+                C.D2H();
+                full = C;
+            }
+            {
+                mhs_shim::ValuesPlan plan(tools, A, B, C);
+                double sum = 0;
+                for (int i = 0; i < reuse; ++i) {
+                    MH_spgemm_values(A, B, C, plan);
+                    sum += plan.last_ms;
+                }
+                std::printf("MH-SpGEMM values-only (pattern reused) mean of %d calls is %.3lfms, Gflops is %.2lf\n", reuse,
+                            sum / reuse, 2.0 * (double)int_result / (sum / reuse * 1e6));
+            }
+            if (check) {
+                C.D2H();
+                try {
+                    std::puts(full == C ? "values pass" : "values error");
+                } catch (const std::exception&) {
+                    std::puts("values error");
+                }
             }
         }
         C.d_release_csr();

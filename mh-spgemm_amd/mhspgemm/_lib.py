@@ -52,6 +52,11 @@ class mhs_host_csr(ctypes.Structure):
                 ("is_symmetric", ctypes.c_int32)]
 
 
+class mhs_values_info(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_int32 * 8), ("products", ctypes.c_int64), ("nnzC", ctypes.c_int64),
+                ("plan_bytes", ctypes.c_int64)]
+
+
 def declared_functions(header: Path | None = None) -> list[str]:
     """Names of the functions include/mhspgemm.h (or `header`) declares."""
     text = (header or HEADER).read_text()
@@ -133,6 +138,15 @@ def lib() -> ctypes.CDLL:
     if hasattr(L, "mhs_hbm_peak"):  # (older A/B variant libraries lack the diagnostic)
         L.mhs_hbm_peak.argtypes = [c_void_p, c_size_t, c_int, P(ctypes.c_double)]
         L.mhs_hbm_peak.restype = c_int
+    if hasattr(L, "mhs_values_plan_create"):  # (values-only SpGEMM: an addition to ABI 10)
+        L.mhs_values_plan_create.argtypes = [c_void_p, P(mhs_csr), P(mhs_csr), P(mhs_csr), P(c_void_p)]
+        L.mhs_values_plan_create.restype = c_int
+        L.mhs_spgemm_values.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(ctypes.c_double)]
+        L.mhs_spgemm_values.restype = c_int
+        L.mhs_values_plan_info.argtypes = [c_void_p, P(mhs_values_info)]
+        L.mhs_values_plan_info.restype = c_int
+        L.mhs_values_plan_destroy.argtypes = [c_void_p, c_void_p]
+        L.mhs_values_plan_destroy.restype = None
     _lib = L
     return L
 

@@ -360,6 +360,82 @@ def spgemm(tool: Tool, A: CSR, B: CSR, timing: bool = True):
     return DeviceCSR(tool, c), (Timing.from_c(t) if t is not None else None)
 
 
+VALUES_CLASSES = ("none", "team", "wave_direct", "wave_search", "block_direct", "block_search", "global")
+
+
+class ValuesPlan:
+    """Values-only SpGEMM on a kept pattern (mhs_values_plan_create / mhs_spgemm_values).
+
+    ``A`` and ``B`` are device-resident ``CSR``; ``C`` is a ``DeviceCSR`` (what ``spgemm``
+    returns) or a ``CSR`` with device arrays, whose ``ptr`` / ``col`` hold a pattern containing
+    the pattern of A*B.  The plan borrows the six pattern arrays and keeps Python references
+    to their owners, so they cannot be collected under it; they must not change while the
+    plan lives.  Creation validates the patterns on the device (``MHSpGEMMError`` with status
+    3 otherwise); ``run`` does not validate again."""
+
+    def __init__(self, tool: Tool, A: CSR, B: CSR, C):
+        if not hasattr(L.lib(), "mhs_values_plan_create"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no values-only entry points")
+        self.tool, self.A, self.B, self.C = tool, A, B, C
+        # (tensors can be rebound on the CSR objects: hold the arrays themselves too)
+        self._keep = (A.d_ptr, A.d_col, A.dev, B.d_ptr, B.d_col, B.dev,
+                      getattr(C, "d_ptr", None), getattr(C, "d_col", None), getattr(C, "dev", None))
+        a, b = A.c_view(), B.c_view()
+        c = C.c if isinstance(C, DeviceCSR) else C.c_view()
+        self._c = c
+        self.nnzA, self.nnzB, self.nnzC = int(a.nnz), int(b.nnz), int(c.nnz)
+        self.plan = ctypes.c_void_p()
+        rc = L.lib().mhs_values_plan_create(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                            ctypes.byref(self.plan))
+        _check(tool.ctx, rc, "mhs_values_plan_create")
+
+    @staticmethod
+    def _ptr(t, n, what):
+        if t is None:
+            return None
+        torch = _torch()
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                and t.numel() == n):
+            raise ValueError(f"{what}: needs a contiguous float64 device tensor of {n} entries")
+        return t.data_ptr() if n else None
+
+    def run(self, Aval=None, Bval=None, out=None, timed: bool = False):
+        """C's values of A*B for the values ``Aval`` / ``Bval`` (torch FP64 device tensors of
+        nnz(A) / nnz(B) entries; default: the operands' own ``d_val``) into ``out`` (nnz(C)
+        entries; default: C's own ``val``).  Returns the call's hipEvent time in ms when
+        ``timed``, else None (the call then follows MHS_OPT_SYNC)."""
+        if not self.plan:
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "ValuesPlan.run: the plan is closed")
+        av = self.A.c_view().val if Aval is None else self._ptr(Aval, self.nnzA, "Aval")
+        bv = self.B.c_view().val if Bval is None else self._ptr(Bval, self.nnzB, "Bval")
+        cv = self._c.val if out is None else self._ptr(out, self.nnzC, "out")
+        ms = ctypes.c_double(0.0)
+        rc = L.lib().mhs_spgemm_values(self.tool.ctx, self.plan, av, bv, cv, ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, "mhs_spgemm_values")
+        return float(ms.value) if timed else None
+
+    def info(self) -> dict:
+        """Rows per class (by name and as the ``rows`` list indexed by class id), products, nnzC, plan_bytes."""
+        i = L.mhs_values_info()
+        _check(self.tool.ctx, L.lib().mhs_values_plan_info(self.plan, ctypes.byref(i)), "mhs_values_plan_info")
+        rows = [int(x) for x in i.rows]
+        d = {"rows": rows, "products": int(i.products), "nnzC": int(i.nnzC), "plan_bytes": int(i.plan_bytes)}
+        d.update({name: rows[k] for k, name in enumerate(VALUES_CLASSES)})
+        return d
+
+    def close(self):
+        if self.plan:
+            L.lib().mhs_values_plan_destroy(self.tool.ctx, self.plan)
+            self.plan = ctypes.c_void_p()
+        self._keep = ()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def transpose(tool: Tool, A: CSR) -> CSR:
     """A^T on the device (mhs_transpose): the AAT operand B = transpose(A)
     (src/main.cu:98-99, host version src/utils.cpp:20-46).  A must be device-

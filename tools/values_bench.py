@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""values_bench.py -- the repeated full call against the values-only call, one config per run.
+
+    python tools/values_bench.py [--config cant] [--blocks 5] [--window 0.4] [--full-only]
+
+(a) the repeated full call, timed as bench.py times its steps: mhs_spgemm on one pair of
+    operands, speculation on, MHS_OPT_SYNC 0 on torch's current stream, each C handed back to
+    the pool before the next call;
+(b) mhs_spgemm_values through a ValuesPlan on C's pattern, on value arrays other than the ones
+    the pattern came from (two sets, alternating), into C's own val.
+
+Before timing, (b)'s output is checked against the full product of the same new operands:
+pattern equal, values by the reference 1e-9 rule.  After warm-up the two are timed in
+alternating blocks; a block is enough calls for its window to last `--window` seconds, between a
+host clock read after a device synchronise and one after the next.  Reported per kind: the median
+of the blocks' per-call times and the spread (max - min) between blocks of that kind.  (b) counts
+as faster only when it is below (a) by more than the larger spread.
+
+--full-only times (a) alone and needs nothing of the values-only entry points, so it also runs
+against an older library (MHS_LIB=/path/to/libmhspgemm.so).  Prints one JSON line."""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (ROOT, ROOT / "mh-spgemm_amd"):
+    if str(p) not in sys.path:
+        sys.path.insert(0, str(p))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import mhspgemm  # noqa: E402
+from mhspgemm import _lib as L  # noqa: E402
+from mhspgemm import synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", default="cant", help="a BASELINE matrix name (mhspgemm.synth.SYNTH); default cant")
+    ap.add_argument("--blocks", type=int, default=5, help="timed blocks per kind")
+    ap.add_argument("--window", type=float, default=0.4, help="seconds a timed block should last")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full-only", action="store_true", help="time the repeated full call alone")
+    args = ap.parse_args()
+
+    dev = 0
+    torch.cuda.set_device(dev)
+    A, source = synth.load_or_synth(args.config)
+    flop = mhspgemm.flop_count_np(A.col, A.ptr)
+    A.H2D(dev)
+    tool = mhspgemm.Tool(dev)
+    tool.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+
+    def sync():
+        torch.cuda.synchronize(dev)
+
+    out = {"config": args.config, "source": source, "M": A.M, "nnzA": A.nnz, "flop": int(flop), "blocks": args.blocks,
+           "lib": L.lib_path()}
+
+    # ---- the pattern, and (b)'s check against the full product of the same new operands
+    C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
+    out["nnzC"] = C.nnz
+    plan = None
+    vals = []
+    if not args.full_only:
+        plan = mhspgemm.ValuesPlan(tool, A, A, C)
+        info = plan.info()
+        out["classes"] = {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}
+        out["plan_bytes"] = info["plan_bytes"]
+        rng = np.random.default_rng(17)
+        for _ in range(2):  # two sets of new values for A's and B's roles
+            vals.append(tuple(torch.from_numpy(rng.uniform(0.1, 1.0, A.nnz)).to(f"cuda:{dev}") for _ in range(2)))
+        sync()
+        p0, c0, _ = C.to_host()
+        for av, bv in vals:
+            A1 = mhspgemm.CSR(A.M, A.N, A.ptr, A.col, av.cpu().numpy())
+            B1 = mhspgemm.CSR(A.M, A.N, A.ptr, A.col, bv.cpu().numpy())
+            A1.H2D(dev)
+            B1.H2D(dev)
+            F, _ = mhspgemm.spgemm(tool, A1, B1, timing=False)
+            fp, fc, fv = F.to_host()
+            F.release()
+            plan.run(av, bv)
+            sync()
+            _, _, gv = C.to_host()
+            assert np.array_equal(fp, p0) and np.array_equal(fc, c0), "pattern of the full product changed"
+            assert mhspgemm.compare_ref(fp, fc, fv, p0, c0, gv), "values outside the reference 1e-9 rule"
+        out["checked"] = "pattern equal, values within the reference 1e-9 rule (2 value sets)"
+
+    # ---- timing
+    tool.set_option(L.MHS_OPT_SYNC, 0)
+    state = {"C": None}
+
+    def full_calls(n):
+        for _ in range(n):
+            if state["C"] is not None:
+                state["C"].release()
+            state["C"], _ = mhspgemm.spgemm(tool, A, A, timing=False)
+
+    def values_calls(n):
+        for i in range(n):
+            av, bv = vals[i & 1]
+            plan.run(av, bv)
+
+    def timed(fn, n):
+        sync()
+        t0 = time.perf_counter()
+        fn(n)
+        sync()
+        return (time.perf_counter() - t0) / n * 1e3  # ms per call
+
+    kinds = [("full", full_calls)] + ([] if args.full_only else [("values", values_calls)])
+    calls = {}
+    for name, fn in kinds:
+        fn(args.warmup)
+        per = timed(fn, 20)
+        calls[name] = max(20, int(args.window * 1e3 / per) + 1)
+    res = {name: [] for name, _ in kinds}
+    for _ in range(args.blocks):
+        for name, fn in kinds:
+            res[name].append(timed(fn, calls[name]))
+    tool.set_option(L.MHS_OPT_SYNC, 1)
+    for name, _ in kinds:
+        r = res[name]
+        out[name] = {"ms_median": round(statistics.median(r), 5), "ms_min": round(min(r), 5), "ms_max": round(max(r), 5),
+                     "spread_ms": round(max(r) - min(r), 5), "calls_per_block": calls[name],
+                     "gflops_median": round(2.0 * flop / (statistics.median(r) * 1e6), 2),
+                     "blocks_ms": [round(x, 5) for x in r]}
+    if not args.full_only:
+        spread = max(out["full"]["spread_ms"], out["values"]["spread_ms"])
+        gain = out["full"]["ms_median"] - out["values"]["ms_median"]
+        out["values_vs_full"] = {"gain_ms": round(gain, 5), "spread_ms": spread, "ratio": round(
+            out["values"]["ms_median"] / out["full"]["ms_median"], 4), "faster_beyond_spread": bool(gain > spread)}
+    if state["C"] is not None:
+        state["C"].release()
+    if plan is not None:
+        plan.close()
+    C.release()
+    tool.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
