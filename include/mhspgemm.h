@@ -111,6 +111,15 @@ int mhs_ctx_trim(mhs_ctx *ctx);
  *     statistics equal the plan's, the numeric kernels run only then, and a
  *     mismatch reruns the call without speculation (MHS_STAT_SPEC_MISS).  Every
  *     phase runs on every call either way.
+ *   MHS_OPT_GROUP_GRID (default 0 = derived; env MHS_GROUP_GRID): block cap of the
+ *     grouped numeric launch (rows of one column pattern, three FEM dofs of a node,
+ *     processed together).  By default a bin of more row groups than the device's
+ *     resident waves launches that resident set (compute units x 4 blocks) and its
+ *     waves loop over the groups -- static rounds, the last ones drawn from row
+ *     cursors -- while smaller bins launch a wave a group.  A value > 0 makes every
+ *     grouped launch loop on at most `value` blocks (rounded up to a multiple of 8):
+ *     for tests, so that a small matrix exercises the loop.  Results do not depend
+ *     on it.  An ABI addition: MHS_ABI_VERSION stays 10.
  * Out of memory: when the workspace, C.ptr, the global-bin scratch or C beside them does
  * not fit, mhs_spgemm gives back every cached buffer and retries row-chunked: a counting
  * pass with the largest chunk workspace that fits sizes C; C is allocated before the
@@ -118,7 +127,7 @@ int mhs_ctx_trim(mhs_ctx *ctx);
  * returns MHS_ERR_OOM right after the counting pass when C itself does not fit, or when
  * a one-row workspace does not fit. */
 typedef enum mhs_option { MHS_OPT_SYNC = 1, MHS_OPT_NUMERIC_EVENTS = 2, MHS_OPT_MEM_BUDGET = 3,
-                           MHS_OPT_TINY_FIRST_ROWS = 4, MHS_OPT_SPECULATE = 5 } mhs_option;
+                           MHS_OPT_TINY_FIRST_ROWS = 4, MHS_OPT_SPECULATE = 5, MHS_OPT_GROUP_GRID = 6 } mhs_option;
 int mhs_ctx_set_option(mhs_ctx *ctx, int option, int value);
 /* Calls of this context that ran row-chunked (the out-of-memory fallback). */
 long long mhs_ctx_chunked_calls(const mhs_ctx *ctx);

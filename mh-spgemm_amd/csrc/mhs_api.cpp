@@ -112,6 +112,10 @@ struct mhs_ctx {
     // MHS_FORK_ORDER=0: the rare rows first
     bool fork_common_first = true;
     int spec_nss = mhs_ctx::NAUX + 1;  // streams of a speculated numeric phase (MHS_SPEC_NSS: a cap, A/B)
+    // the grouped numeric bin's cursor walk (plan_numeric): the device's compute units size its
+    // resident set (MHS_GROUP_WALK=0: cus stays 0, the static walk); MHS_OPT_GROUP_GRID caps its blocks
+    int cus = 0;
+    int group_cap = 0;
 };
 
 // A values plan (mhs_values_plan_create): the six borrowed pattern arrays, the class lists and the
@@ -459,8 +463,8 @@ int numeric_streams(const mhs_ctx* ctx, const Stats& h) {
 // it complete -- waits on a pending one measured slower than the whole hand-off, r06b) and joins.
 enum NumPhase { NUM_ALL = 0, NUM_SPEC_A = 1, NUM_SPEC_B = 2 };
 
-NumShape num_shape(const Csr& a, const Csr& b, const Work& w, bool split) {
-    return NumShape{a.M, a.nnz, b.nnz, w.bx_on, w.sc_col != nullptr, split, NUM_GLOBAL_GRID};
+NumShape num_shape(const mhs_ctx* ctx, const Csr& a, const Csr& b, const Work& w, bool split) {
+    return NumShape{a.M, a.nnz, b.nnz, w.bx_on, w.sc_col != nullptr, split, NUM_GLOBAL_GRID, ctx->cus, ctx->group_cap};
 }
 
 // `plan`: built by the phase that runs first (ALL, SPEC_A) and kept by the caller for SPEC_B.
@@ -489,7 +493,7 @@ int run_numeric(mhs_ctx* ctx, const Csr& a, const Csr& b, const Work& w, const S
         if (split) MHS_HIP(hipEventRecord(ctx->split_ev, s));
         ctx->stat[MHS_STAT_SPLIT] += split;
         ctx->stat[MHS_STAT_MULTI_STREAM] += nss > 1;
-        plan = plan_numeric(h, num_shape(a, b, w, split));
+        plan = plan_numeric(h, num_shape(ctx, a, b, w, split));
     }
     // Launch i on ss[stream_of(i, nss)]; a speculated plan's phase A issues the call stream's share,
     // phase B the rest.  The aux streams wait for the fork event (everything before numeric): waits
@@ -660,7 +664,7 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
         if (rc == MHS_OK) rc = ensure_gscratch(ctx, w, h);
         if (rc) return rc;
         if (h.nnzC > 0) {
-            const NumPlan p = plan_numeric(h, num_shape(a, b, w, false));
+            const NumPlan p = plan_numeric(h, num_shape(ctx, a, b, w, false));
             const NumPointers np{a, b, w, out.ptr + r0, out.col + off, out.val + off, ctx->dense_span_max};
             for (int i = 0; i < p.n; ++i) issue_numeric(p.launch[i], p.o32, np, s, nullptr, nullptr);
         }
@@ -1132,6 +1136,7 @@ int mhs_ctx_create(mhs_ctx** out, int device) {
     }
     if (e == hipSuccess) e = hipMalloc((void**)&ctx->d_go, 256);
     if (e == hipSuccess) e = init_kernel_attributes();
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) {
         fprintf(stderr, "mhs_ctx_create: %s\n", hipGetErrorString(e));
         delete ctx;
@@ -1157,6 +1162,9 @@ int mhs_ctx_create(mhs_ctx** out, int device) {
         ctx->spec_fork = atoi(e) == 1;
         ctx->spec_fork_rare = atoi(e) == 2;
     }
+    if (const char* e = getenv("MHS_GROUP_WALK"))
+        if (atoi(e) == 0) ctx->cus = 0;
+    if (const char* e = getenv("MHS_GROUP_GRID")) ctx->group_cap = std::max(0, atoi(e));  // (MHS_OPT_GROUP_GRID, A/B)
     if (const char* e = getenv("MHS_SPEC_NSS")) ctx->spec_nss = std::max(1, std::min(atoi(e), mhs_ctx::NAUX + 1));
     *out = ctx;
     return MHS_OK;
@@ -1436,6 +1444,11 @@ int mhs_ctx_set_option(mhs_ctx* ctx, int option, int value) {
         return MHS_OK;
     case MHS_OPT_TINY_FIRST_ROWS:
         ctx->nft_min_m = value;
+        ++ctx->gen;
+        return MHS_OK;
+    case MHS_OPT_GROUP_GRID:
+        if (value < 0) return fail(ctx, MHS_ERR_INVALID, "grouped grid cap must be >= 0 blocks");
+        ctx->group_cap = value;
         ++ctx->gen;
         return MHS_OK;
     default:

@@ -3281,10 +3281,98 @@ struct NumArgs {
                              // Bval are then B's arrays extended by the union rows at ubase
     int wave_bytes;          // grouped wave launches: LDS bytes per wave (0: the template's)
     const int* go;           // speculated plan: run only when *go == 1 (k_scan's verdict); nullptr: always
+    int cursor_walk;         // grouped wave launches: groups from the XCD groups' cursors (mhs_groupwalk.hpp)
 };
 // A speculated launch whose plan k_scan rejected returns before touching anything.
 #define MHS_PLAN_GUARD(args) \
     if ((args).go && *(args).go != 1) return
+
+struct NumRow {
+    int row, lo, hi, t, c0, n, a0, a1;
+};
+// Row walks without a next group to fetch: every row's scalars are loaded in front of its body.
+struct NoNext {
+    static constexpr bool kOn = false;
+    int tflop, rflop, grp, gna;
+    __device__ __forceinline__ void take() {}
+    __device__ __forceinline__ void head() {}
+    __device__ __forceinline__ void scalars() {}
+};
+// The next group of a grouped wave walk, fetched while the wave works on the current one: the
+// body calls take / head / scalars at three of its phase ends, each a point where it has just
+// waited for loads of its own, and each consumes what the one before issued a phase earlier --
+//   take:    past the wave's static rounds, the next ticket (one atomic on the XCD group's cursor),
+//   head:    the next list index -- of the static rounds, else the ticket's (group_take: "none"
+//            past the eighth's end) -- and the load of its list entry, the group's head row,
+//   scalars: the head row's scalars, one a lane: lane k of `v` loads scalar k below.
+// So between a group's last C store and the next group's first A load lies no dependent global
+// round trip: advance() only reads lanes of `v`.  The fetched state is the one VGPR `v` (loads
+// into SGPRs would be spilled, and waited for, across the body).  A "none" ticket reads no list
+// entry and no row: v stays -1 in every lane, the walk ends.
+struct GroupNext {
+    enum : int { K_LO, K_HI, K_T, K_C0, K_C1, K_A0, K_A1, K_TFLOP, K_RFLOP, K_GNA, K_GRP, K_ROW };
+    static constexpr bool kOn = true;
+    const NumArgs& a;
+    int* cur;         // cursor walk: the XCD group's cursor; static walk: nullptr
+    GroupWalk gw;     // static rounds [.., split) of stride `waves`, then tickets for [split, end)
+    int li;           // the list index head() gave last (before the first: one stride in front)
+    bool dyn;         // past the static rounds
+    int v;
+    NumRow r;         // the current group, set by advance()
+    int tflop, rflop, grp, gna;
+    __device__ __forceinline__ bool static_left() const { return !dyn && group_static_next(gw, li) != GROUP_NONE; }
+    __device__ __forceinline__ void take() {
+        if (cur && !static_left()) {
+            v = 0;
+            if (lane_id() == 0) v = atomicAdd(cur, 1);
+        }
+    }
+    __device__ __forceinline__ void head() {
+        int nli = GROUP_NONE;
+        if (static_left()) {
+            nli = group_static_next(gw, li);
+        } else if (cur) {
+            dyn = true;
+            nli = group_take(gw, __builtin_amdgcn_readfirstlane(v));
+            MHS_FLIGHT_TAKE(nli);
+        }
+        li = nli;
+        v = -1;
+        if (nli != GROUP_NONE) {
+            int z;  // a lane-private zero the compiler cannot see through: a vector load into v
+            asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+            v = a.list[nli + z];
+        }
+    }
+    __device__ __forceinline__ void scalars() {
+        const int row = __builtin_amdgcn_readfirstlane(v);
+        if (row < 0) return;
+        const int k = lane_id();
+        const int* p = k == K_LO ? a.rlo : k == K_HI ? a.rhi : k == K_T ? a.ctiles : k <= K_C1 ? a.Cptr
+                     : k <= K_A1 ? a.Aptr : k == K_TFLOP ? a.rtflop : k == K_RFLOP ? a.rflop : a.gna;
+        int x = row;  // (lanes from K_ROW on keep the row)
+        if (k < K_GNA || (k == K_GNA && a.gna)) x = p[row + (k == K_C1 || k == K_A1)];
+        if (k == K_GRP) x = a.grp[row];
+        v = x;
+    }
+    // the fetched group becomes the current one; false: there is none
+    __device__ __forceinline__ bool advance() {
+        r.row = __builtin_amdgcn_readlane(v, K_ROW);
+        if (r.row < 0) return false;
+        r.lo = __builtin_amdgcn_readlane(v, K_LO);
+        r.hi = __builtin_amdgcn_readlane(v, K_HI);
+        r.t = __builtin_amdgcn_readlane(v, K_T);
+        r.c0 = __builtin_amdgcn_readlane(v, K_C0);
+        r.n = __builtin_amdgcn_readlane(v, K_C1) - r.c0;
+        r.a0 = __builtin_amdgcn_readlane(v, K_A0);
+        r.a1 = __builtin_amdgcn_readlane(v, K_A1);
+        tflop = __builtin_amdgcn_readlane(v, K_TFLOP);
+        rflop = __builtin_amdgcn_readlane(v, K_RFLOP);
+        gna = __builtin_amdgcn_readlane(v, K_GNA);
+        grp = __builtin_amdgcn_readlane(v, K_GRP);
+        return true;
+    }
+};
 
 // C output of a row (num_row_body, num_row_bitmap): values two a lane, columns four a lane, in
 // 16-byte stores (8-byte aligned doubles and 4-byte aligned ints: gfx950 stores them unaligned);
@@ -3346,17 +3434,19 @@ __device__ __forceinline__ void stage_cols(const TileEntry* E, int H, int lo, in
 // (forced inline, as num_row: left to the inliner, a grown grouped kernel called them out of
 // line, and the kernel argument they take by reference went to scratch -- 304 bytes a lane,
 // every field read a scratch load)
-template <class Team, bool GLOBALMEM, int MODE, bool GROUPED, bool O32>
+template <class Team, bool GLOBALMEM, int MODE, bool GROUPED, bool O32, class NX = NoNext>
 __device__ __forceinline__ void num_row_body(const Team& tm, const NumArgs& a, int row, int lo, int span, int t,
                              int c0, int n, int a0, int a1, char* region, int* counter,
-                             int4* stage, int R) {
+                             int4* stage, int R, NX* nx = nullptr) {
     MHS_BSTAMP0();
     const int H = MODE == NM_HASH ? hash_slots(t) : span;
     const int colbase = lo << TILE_SHIFT;
     TileEntry* E = (TileEntry*)region;
     double* acc = (double*)(region + (long long)H * 16);
     const int nacc = MODE == NM_DENSE ? span * TILE_BITS : n;
-    const int tflop = __builtin_amdgcn_readfirstlane(a.rtflop[row]);
+    // (a grouped wave walk fetched the row's scalars with the previous group: GroupNext)
+    const int tflop = NX::kOn ? nx->tflop : __builtin_amdgcn_readfirstlane(a.rtflop[row]);
+    auto rflop = [&]() { return NX::kOn ? nx->rflop : __builtin_amdgcn_readfirstlane(a.rflop[row]); };
     // row group: R accumulator slices `stride` doubles apart; C row r at c0 + r*n
     const int stride = GROUPED ? (int)(num_acc_bytes(MODE, span, t, n) / 8) : 0;
     const int nclear = GROUPED ? (R - 1) * stride + nacc : nacc;
@@ -3370,21 +3460,22 @@ __device__ __forceinline__ void num_row_body(const Team& tm, const NumArgs& a, i
     const int* gcol = a.Acol;
     const double* gval = a.Aval;
     if constexpr (GROUPED) {
-        gnear = (__builtin_amdgcn_readfirstlane((int)a.grp[row]) & GRP_NEAR) != 0;
+        gnear = ((NX::kOn ? nx->grp : __builtin_amdgcn_readfirstlane((int)a.grp[row])) & GRP_NEAR) != 0;
         if (gnear) {
-            gnw = __builtin_amdgcn_readfirstlane(a.gna[row]);
+            gnw = NX::kOn ? nx->gna : __builtin_amdgcn_readfirstlane(a.gna[row]);
             gcol = a.ucol;
             gval = a.uval + 2LL * a0;
         }
         group_pair_a(gp, a0, a0 + gnw, gcol, gval, R, gnw);
     }
+    if constexpr (NX::kOn) nx->take();
     // 1. the C row's tile table: the symbolic pass's masks when it kept them,
     //    else rebuilt (same OR pass as symbolic)
     MHS_BSTAMP(0);
     // symbolic kept the masks unless it sorted the row as a tiny one (numeric runs those
     // with tables when the tiny classes are off: N beyond the packed keys' 23 bits)
     // (symbolic's class 4 rows never come here: k_scan sorts them in numeric too)
-    const bool sym_tiny = tiny_class_sym(__builtin_amdgcn_readfirstlane(a.rflop[row]), a1 - a0) >= 0;
+    const bool sym_tiny = tiny_class_sym(rflop(), a1 - a0) >= 0;
     const int lofs = (a.mcache && !sym_tiny && spill_row(span, tflop, t, a.mc_list))
                          ? __builtin_amdgcn_readfirstlane(a.sp.lofs[row])
                          : -1;
@@ -3447,6 +3538,7 @@ __device__ __forceinline__ void num_row_body(const Team& tm, const NumArgs& a, i
     }
     MHS_BSTAMP(1);
 
+    if constexpr (NX::kOn) nx->head();
     if constexpr (GROUPED) group_pair_meta(gp, a.bmeta);
     // 2. rank of every tile's first column = prefix popcount in tile order
     if constexpr (MODE != NM_HASH) {
@@ -3547,13 +3639,14 @@ __device__ __forceinline__ void num_row_body(const Team& tm, const NumArgs& a, i
     for (int r = tm.rank(); r < nclear; r += Team::size) acc[r] = 0.0;
     tm.sync();
     MHS_BSTAMP(3);
+    if constexpr (NX::kOn) nx->scalars();
 
     // 3. accumulate every product of the row (of the group's rows)
     {
         const Accum<GLOBALMEM, MODE, O32> f{E, acc, lo, H, colbase, a.Bcol, a.Bval, a.ubase};
         if constexpr (GROUPED) {
             const int nAr = a1 - a0;
-            const int avg = nAr > 0 ? (__builtin_amdgcn_readfirstlane(a.rflop[row]) + nAr - 1) / nAr : 1;
+            const int avg = nAr > 0 ? (rflop() + nAr - 1) / nAr : 1;
             // a near group walks its union row (columns at the head's A offset, R value slices
             // nU apart from 3 * Aptr[head]): row r's value of union entry j at uv[a0 + j + r * nU]
             // with uv = uval + 2 * a0 (gcol / gval above).  (One call site: two inlined walks
@@ -3804,14 +3897,11 @@ __device__ void num_row_bitmap(const BlockTeam<T, false>& tm, const NumArgs& a, 
 // register budget -- and the occupancy -- of the direct-mapped wave kernels too.
 enum NumModes : int { MODES_ALL = 0, MODES_NOHASH = 1, MODES_HASH = 2 };
 
-// Row-level scalars are made provably wave-uniform (readfirstlane) so that the
+// Row-level scalars (NumRow) are made provably wave-uniform (readfirstlane) so that the
 // mode dispatch and every per-row loop bound compile to scalar control flow.
-struct NumRow {
-    int row, lo, hi, t, c0, n, a0, a1;
-};
-template <class Team, bool GLOBALMEM, bool GROUPED = false, int MODES = MODES_ALL, bool O32 = false>
+template <class Team, bool GLOBALMEM, bool GROUPED = false, int MODES = MODES_ALL, bool O32 = false, class NX = NoNext>
 __device__ __forceinline__ void num_row_s(const Team& tm, const NumArgs& a, const NumRow& r, char* region,
-                                          int* counter, int4* stage, int R = 1);
+                                          int* counter, int4* stage, int R = 1, NX* nx = nullptr);
 template <class Team, bool GLOBALMEM, bool GROUPED = false, int MODES = MODES_ALL, bool O32 = false>
 __device__ __forceinline__ void num_row(const Team& tm, const NumArgs& a, int row, char* region, int* counter,
                         int4* stage, int R = 1) {
@@ -3826,22 +3916,22 @@ __device__ __forceinline__ void num_row(const Team& tm, const NumArgs& a, int ro
     r.a1 = __builtin_amdgcn_readfirstlane(a.Aptr[row + 1]);
     num_row_s<Team, GLOBALMEM, GROUPED, MODES, O32>(tm, a, r, region, counter, stage, R);
 }
-template <class Team, bool GLOBALMEM, bool GROUPED, int MODES, bool O32>
+template <class Team, bool GLOBALMEM, bool GROUPED, int MODES, bool O32, class NX>
 __device__ __forceinline__ void num_row_s(const Team& tm, const NumArgs& a, const NumRow& r, char* region,
-                                          int* counter, int4* stage, int R) {
+                                          int* counter, int4* stage, int R, NX* nx) {
     const int row = r.row, lo = r.lo, hi = r.hi, t = r.t, c0 = r.c0, n = r.n, a0 = r.a0, a1 = r.a1;
     const int span = hi - lo + 1;
     const int mode = num_mode(span, t, n, a.dense_span_max);
     if constexpr (MODES == MODES_HASH) {
-        num_row_body<Team, GLOBALMEM, NM_HASH, GROUPED, O32>(tm, a, row, lo, span, t, c0, n, a0, a1, region, counter, stage, R);
+        num_row_body<Team, GLOBALMEM, NM_HASH, GROUPED, O32>(tm, a, row, lo, span, t, c0, n, a0, a1, region, counter, stage, R, nx);
         return;
     }
     if (mode == NM_DENSE)
-        num_row_body<Team, GLOBALMEM, NM_DENSE, GROUPED, O32>(tm, a, row, lo, span, t, c0, n, a0, a1, region, counter, stage, R);
+        num_row_body<Team, GLOBALMEM, NM_DENSE, GROUPED, O32>(tm, a, row, lo, span, t, c0, n, a0, a1, region, counter, stage, R, nx);
     else if (MODES == MODES_NOHASH || mode == NM_DIRECT)
-        num_row_body<Team, GLOBALMEM, NM_DIRECT, GROUPED, O32>(tm, a, row, lo, span, t, c0, n, a0, a1, region, counter, stage, R);
+        num_row_body<Team, GLOBALMEM, NM_DIRECT, GROUPED, O32>(tm, a, row, lo, span, t, c0, n, a0, a1, region, counter, stage, R, nx);
     else
-        num_row_body<Team, GLOBALMEM, NM_HASH, GROUPED, O32>(tm, a, row, lo, span, t, c0, n, a0, a1, region, counter, stage, R);
+        num_row_body<Team, GLOBALMEM, NM_HASH, GROUPED, O32>(tm, a, row, lo, span, t, c0, n, a0, a1, region, counter, stage, R, nx);
 }
 
 
@@ -3855,15 +3945,49 @@ __device__ __forceinline__ void num_wave_rows(const NumArgs& a, int bid = -1, in
     const int w = threadIdx.x >> 6;
     char* reg = smem + w * (GROUPED && a.wave_bytes > 0 ? a.wave_bytes : BYTES);  // (grouped: sized to the bin)
     WaveTeam tm;
+    if constexpr (GROUPED) {
+        // Group heads (R rows of one pattern each), the next one fetched under the current one's
+        // body (GroupNext).  A launch of about the resident set (cursor_walk, plan_numeric) strides
+        // through all but the last rounds of an XCD group's eighth and draws those from the group's
+        // cursor (mhs_groupwalk.hpp): a ticket is amortised over a body of tens of thousands of
+        // cycles, and no wave's end waits on a neighbour's last group.
+        // The other launches hold at most a group or two a wave and keep the static stride.
+        GroupNext nx{a};
+        nx.dyn = false;
+        if (a.cursor_walk && (nb & 7) == 0) {
+            const int g = bid & 7;
+            nx.gw = group_walk(a.count, g, nb);
+            nx.cur = a.cursor + g * CURSOR_STRIDE;
+            nx.li = nx.gw.begin + (bid >> 3) * WPB + w - nx.gw.waves;
+        } else {
+            // (RowWalk's walk, written out: its constructor is not inlined here)
+            nx.cur = nullptr;
+            if ((nb & 7) == 0) {
+                const int g = bid & 7;
+                nx.gw.waves = (nb >> 3) * WPB;
+                nx.gw.split = nx.gw.end = group_begin(a.count, g + 1);
+                nx.li = group_begin(a.count, g) + (bid >> 3) * WPB + w - nx.gw.waves;
+            } else {
+                nx.gw.waves = nb * WPB;
+                nx.gw.split = nx.gw.end = a.count;
+                nx.li = bid * WPB + w - nx.gw.waves;
+            }
+        }
+        nx.take();
+        nx.head();
+        nx.scalars();
+        while (nx.advance()) {
+            MHS_FLIGHT_ROW(nx.r.row, nx.li);
+            num_row_s<WaveTeam, false, true, MODES_ALL, O32>(tm, a, nx.r, reg + WAVE_HDR, (int*)reg, nullptr,
+                                                           nx.grp & GRP_RMASK, &nx);
+        }
+        return;
+    }
     auto one = [&](int li) {
         const int row = __builtin_amdgcn_readfirstlane(a.list[li]);
         MHS_FLIGHT_ROW(row, li);
-        if constexpr (GROUPED)  // a group head: R rows of one pattern
-            num_row<WaveTeam, false, true, MODES_ALL, O32>(tm, a, row, reg + WAVE_HDR, (int*)reg, nullptr,
-                                                         __builtin_amdgcn_readfirstlane((int)a.grp[row]) & GRP_RMASK);
-        else
-            num_row<WaveTeam, false, false, HASH ? MODES_HASH : MODES_NOHASH, O32>(tm, a, row, reg + WAVE_HDR,
-                                                                             (int*)reg, nullptr);
+        num_row<WaveTeam, false, false, HASH ? MODES_HASH : MODES_NOHASH, O32>(tm, a, row, reg + WAVE_HDR, (int*)reg,
+                                                                         nullptr);
     };
     // The 10 KiB bins (16 KiB before round 3) hold the heaviest wave rows (power-law rows of hundreds of tiles, a
     // few rows per wave): a static stride leaves the launch's end to the wave that drew the
@@ -4758,6 +4882,7 @@ NumArgs num_args(const NumPointers& p, const NumLaunch& l) {
     a.gbytes = l.gbytes;
     a.qall = l.qall;
     a.wave_bytes = l.wave_bytes;
+    a.cursor_walk = l.cursor_walk;
     return a;
 }
 
