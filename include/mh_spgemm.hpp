@@ -238,11 +238,16 @@ class ValuesPlan {
 public:
     mhs_ctx* ctx = nullptr;
     mhs_values_plan* plan = nullptr;
-    ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C) : ctx(tools.ctx) {
+    // masked: C's pattern is a mask, possibly smaller than the product's (mhs_values_plan_create_masked);
+    // form: an mhs_mask_form
+    ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C, bool masked = false, int form = MHS_MASK_AUTO)
+        : ctx(tools.ctx) {
         mhs_csr a{A.M, A.N, A.nnz, A.d_ptr, A.d_col, A.d_val};
         mhs_csr b{B.M, B.N, B.nnz, B.d_ptr, B.d_col, B.d_val};
         mhs_csr c{C.M, C.N, C.nnz, C.d_ptr, C.d_col, C.d_val};
-        if (mhs_values_plan_create(ctx, &a, &b, &c, &plan) != MHS_OK) {
+        const int rc = masked ? mhs_values_plan_create_masked(ctx, &a, &b, &c, form, &plan)
+                              : mhs_values_plan_create(ctx, &a, &b, &c, &plan);
+        if (rc != MHS_OK) {
             std::printf("%s\n", mhs_last_error(ctx));
             throw std::runtime_error(mhs_last_error(ctx));
         }
@@ -254,6 +259,12 @@ public:
         mhs_values_info i{};
         mhs_values_plan_info(plan, &i);
         return i;
+    }
+    // the products that land in C's pattern (all of them unless the plan is masked)
+    long long kept() const {
+        int64_t k = 0;
+        mhs_values_plan_kept(plan, &k);
+        return (long long)k;
     }
     // the hipEvent time of the last MH_spgemm_values call through this plan (ms)
     double last_ms = 0;

@@ -200,12 +200,40 @@ int mhs_spgemm_values(mhs_ctx *ctx, mhs_values_plan *plan, const double *Aval, c
                       double *Cval, double *ms);
 typedef struct mhs_values_info {
     int32_t rows[8];              /* rows per class, index = class id (0: nothing to compute; 1 team, 2 wave-direct,
-                                   * 3 wave-search, 4 block-direct, 5 block-search, 6 global) */
+                                   * 3 wave-search, 4 block-direct, 5 block-search, 6 global; 7 dot: masked plans) */
     int64_t products, nnzC, plan_bytes;
 } mhs_values_info;
 int mhs_values_plan_info(const mhs_values_plan *plan, mhs_values_info *info);
 /* Frees the plan's device memory (waits for the context stream first).  NULL plan: no-op. */
 void mhs_values_plan_destroy(mhs_ctx *ctx, mhs_values_plan *plan);
+
+/* ---- masked product: C<M> = A*B on a given pattern --------------------------
+ * For callers whose pattern is smaller than the product's (triangle counting L*L on L, ILU(0)- and
+ * SPAI-style updates on A's pattern, sparsified AMG coarse operators).  C->ptr / C->col are the mask:
+ * for every mask entry (i, j), Cval = sum_k A_ik * B_kj; duplicates in A and in B are summed, a mask
+ * entry no product reaches gets exactly 0.0, products whose column is not in the mask row are dropped.
+ * Complemented and value-dependent masks are not supported.  The result is an ordinary
+ * mhs_values_plan: mhs_spgemm_values, mhs_values_plan_info and mhs_values_plan_destroy run it as they
+ * run any other.  Validation is mhs_values_plan_create's (dimensions, the three row_ptr arrays, A's
+ * columns < B.M, C's columns strictly ascending in range) without the containment check; B's columns
+ * are checked to lie in [0, B.N) when B^T is built.  A's rows need not be sorted; B's are ascending.
+ * form says how rows are computed:
+ *   MHS_MASK_PRODUCT  every row walks its products and drops the misses (the classes 1..6 above)
+ *   MHS_MASK_DOT      every row with mask and A entries takes the inner-product form (class 7): per
+ *                     mask entry (i, j), A's row i is intersected with B's column j.  Its sum order
+ *                     is fixed -- A's entry order, then B's duplicate order -- so two calls give the
+ *                     same bits on these rows.
+ *   MHS_MASK_AUTO     per row, the dot form where its search steps, weighted, are fewer than the
+ *                     row's products
+ * The dot form reads B^T's pattern: built at creation for AUTO and DOT, kept (4 (B.N + 1) + 8 nnz(B)
+ * bytes of the plan's own memory, part of plan_bytes) only while some row uses it.  Any other form
+ * value: MHS_ERR_INVALID.  Additions to ABI version 10, like the entries above. */
+typedef enum mhs_mask_form { MHS_MASK_AUTO = 0, MHS_MASK_PRODUCT = 1, MHS_MASK_DOT = 2 } mhs_mask_form;
+int mhs_values_plan_create_masked(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
+                                  int form, mhs_values_plan **plan);
+/* The products that land in the plan's C pattern (mhs_values_info::products counts them all).
+ * A plan of mhs_values_plan_create: kept == products. */
+int mhs_values_plan_kept(const mhs_values_plan *plan, int64_t *kept_products);
 
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).

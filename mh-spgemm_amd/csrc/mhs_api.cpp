@@ -125,8 +125,13 @@ struct mhs_values_plan {
     int device = 0;
     ValPattern pat{};
     long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
+    long long kept = 0;    // products that land in C's pattern (masked plans count them; else = products)
     char* mem = nullptr;   // lists (M ints), counters (VAL_CNT_INTS), status (VAL_STATUS_INTS)
     size_t mem_bytes = 0;
+    // a masked plan with dot rows: B^T's pattern -- tptr (B.N + 1), trow, tperm (nnz(B) each) -- the plan's own too
+    char* tmem = nullptr;
+    size_t tmem_bytes = 0;
+    ValTrans trans{};
     int* lists = nullptr;
     int list_off[VAL_NCLASS] = {};
     ValCounts counts{};
@@ -135,7 +140,10 @@ struct mhs_values_plan {
 };
 
 namespace {
-constexpr int VAL_STATUS_INTS = 8;  // first bad row of: A.ptr, B.ptr, C.ptr, A's columns, C's columns, the products
+// first bad row of: A.ptr, B.ptr, C.ptr, A's columns, C's columns, the products, B's columns (masked plans)
+constexpr int VAL_STATUS_INTS = 8;
+static_assert((int)MHS_MASK_AUTO == (int)VM_AUTO && (int)MHS_MASK_PRODUCT == (int)VM_PRODUCT && (int)MHS_MASK_DOT == (int)VM_DOT,
+              "mhs_mask_form is ValMaskForm");
 }
 
 namespace {
@@ -1255,10 +1263,26 @@ int mhs_spgemm(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C, mhs
     }
 }
 
-int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
+namespace {
+
+// AUTO's ratio: VAL_DOT_RATIO, or MHS_VAL_DOT_RATIO (diagnostic: one build swept over the ratio)
+int val_dot_ratio() {
+    if (const char* v = std::getenv("MHS_VAL_DOT_RATIO")) {
+        const long r = std::strtol(v, nullptr, 10);
+        if (r >= 1 && r <= 1 << 20) return (int)r;
+    }
+    return VAL_DOT_RATIO;
+}
+
+// mhs_values_plan_create (masked false: C must contain the product's pattern) and
+// mhs_values_plan_create_masked (C is a mask; form: mhs_mask_form).
+int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form,
+                       mhs_values_plan** out) {
     if (!ctx) return MHS_ERR_INVALID;
     if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
     *out = nullptr;
+    if (masked && (form < MHS_MASK_AUTO || form > MHS_MASK_DOT))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: form is not an mhs_mask_form");
     if (A->M < 0 || A->N < 0 || A->nnz < 0 || B->M < 0 || B->N < 0 || B->nnz < 0 || C->M < 0 || C->N < 0 || C->nnz < 0)
         return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: negative dimension");
     if (A->N != B->M) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: A.N != B.M");
@@ -1320,14 +1344,50 @@ int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, con
     if ((e = read_status()) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: column check");
     if (status[3] != NONE) return bad_row(3, "a column of A is outside [0, B.M)");
     if (status[4] != NONE) return bad_row(4, "C's columns are not strictly ascending within [0, C.N)");
-    // 3. classes, lists, and every product's column looked up in its C row
-    launch_val_classify(p->pat, d_cnt, p->lists, s);
-    launch_val_verify(p->pat, d_status + 5, s);
+    void* sort_tmp = nullptr;  // (B^T's sort scratch: freed once the stream has been read back)
+    if (!masked) {
+        // 3. classes, lists, and every product's column looked up in its C row
+        launch_val_classify(p->pat, d_cnt, p->lists, s);
+        launch_val_verify(p->pat, d_status + 5, s);
+    } else {
+        // 3m. a mask: B^T's pattern for the dot class (its sort indexes by B's columns: checked first), classes
+        // by val_class_masked, and the products that land in the mask counted where the plain plan verifies
+        if (form != MHS_MASK_PRODUCT) {
+            launch_val_check_cols(B->ptr, B->col, B->M, B->N, false, d_status + 6, s);
+            if ((e = read_status()) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: column check");
+            if (status[6] != NONE) return bad_row(6, "a column of B is outside [0, B.N)");
+            const Csr b{B->M, B->N, B->nnz, B->ptr, B->col, nullptr};
+            const size_t nb = (size_t)B->nnz;
+            const size_t ptr_bytes = al(((size_t)B->N + 1) * 4), ent_bytes = al((nb ? nb : 1) * 4);
+            size_t tmp_bytes = 0;
+            if ((e = transpose_pattern(b, nullptr, nullptr, nullptr, nullptr, &tmp_bytes, s)) != hipSuccess)
+                return bail_hip(e, "mhs_values_plan_create: B^T (scratch size)");
+            if ((e = hipMalloc((void**)&p->tmem, ptr_bytes + 2 * ent_bytes)) != hipSuccess)
+                return bail_hip(e, "mhs_values_plan_create: B^T memory");
+            p->tmem_bytes = ptr_bytes + 2 * ent_bytes;
+            int* tptr = (int*)p->tmem;
+            int* trow = (int*)(p->tmem + ptr_bytes);
+            int* tperm = (int*)(p->tmem + ptr_bytes + ent_bytes);
+            e = hipMalloc(&sort_tmp, tmp_bytes ? tmp_bytes : 16);
+            if (e == hipSuccess) e = transpose_pattern(b, tptr, trow, tperm, sort_tmp, &tmp_bytes, s);
+            if (e != hipSuccess) {
+                if (sort_tmp) {
+                    (void)hipStreamSynchronize(s);
+                    (void)hipFree(sort_tmp);
+                }
+                return bail_hip(e, "mhs_values_plan_create: B^T");
+            }
+            p->trans = ValTrans{tptr, trow, tperm};
+        }
+        launch_val_classify_masked(p->pat, ValMask{p->trans.tptr, form, val_dot_ratio()}, d_cnt, p->lists, s);
+        launch_val_count_kept(p->pat, d_cnt, s);
+    }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = read_status();
+    if (sort_tmp) (void)hipFree(sort_tmp);
     if (e != hipSuccess) return bail_hip(e, "mhs_values_plan_create: classify");
-    if (status[5] != NONE) return bad_row(5, "C's pattern misses a column of the product A*B");
+    if (!masked && status[5] != NONE) return bad_row(5, "C's pattern misses a column of the product A*B");
     int off = 0;
     for (int c = 0; c < VAL_NCLASS; ++c) {
         p->counts.rows[c] = h_cnt[c * BINCNT_STRIDE];
@@ -1336,8 +1396,33 @@ int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, con
         off += p->counts.rows[c];
     }
     memcpy(&p->products, &h_cnt[3 * VAL_NCLASS * BINCNT_STRIDE], sizeof p->products);
+    p->kept = p->products;
+    if (masked) memcpy(&p->kept, &h_cnt[(3 * VAL_NCLASS + 1) * BINCNT_STRIDE], sizeof p->kept);
+    if (p->tmem && p->counts.rows[VC_DOT] == 0) {  // no row chose the dot class: B^T goes again
+        (void)hipFree(p->tmem);
+        p->tmem = nullptr;
+        p->tmem_bytes = 0;
+        p->trans = ValTrans{};
+    }
     p->plan = plan_values(p->counts);
     *out = p;
+    return MHS_OK;
+}
+
+}  // namespace
+
+int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, out);
+}
+
+int mhs_values_plan_create_masked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int form,
+                                  mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, true, form, out);
+}
+
+int mhs_values_plan_kept(const mhs_values_plan* p, int64_t* kept_products) {
+    if (!p || !kept_products) return MHS_ERR_INVALID;
+    *kept_products = p->kept;
     return MHS_OK;
 }
 
@@ -1353,7 +1438,7 @@ int mhs_spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, cons
     if (ms) MHS_HIP(hipEventRecord(p->ev[0], s));
     for (int i = 0; i < p->plan.n; ++i) {
         const ValLaunch& l = p->plan.launch[i];
-        issue_values(l, a, p->lists + p->list_off[l.cls], s);
+        issue_values(l, a, p->trans, p->lists + p->list_off[l.cls], s);
     }
     MHS_HIP(hipGetLastError());
     if (ms) {
@@ -1374,7 +1459,7 @@ int mhs_values_plan_info(const mhs_values_plan* p, mhs_values_info* info) {
     for (int c = 0; c < VAL_NCLASS; ++c) info->rows[c] = p->counts.rows[c];
     info->products = p->products;
     info->nnzC = p->nnzC;
-    info->plan_bytes = (int64_t)p->mem_bytes;
+    info->plan_bytes = (int64_t)(p->mem_bytes + p->tmem_bytes);
     return MHS_OK;
 }
 
@@ -1386,6 +1471,7 @@ void mhs_values_plan_destroy(mhs_ctx* ctx, mhs_values_plan* p) {
     for (hipEvent_t ev : p->ev)
         if (ev) (void)hipEventDestroy(ev);
     if (p->mem) (void)hipFree(p->mem);
+    if (p->tmem) (void)hipFree(p->tmem);
     (void)hipGetLastError();
     delete p;
 }

@@ -8,6 +8,8 @@
 // A's entries are in row-major order, so each column's entries keep ascending row
 // order), a gather of (row, value) through the sorted entry indices, and the row
 // pointer read off the sorted keys.
+// transpose_pattern shares the sort and stops before the values: (row, entry index) per
+// entry of A^T -- the B^T a masked values plan's dot class searches (mhs_values.hip).
 #include "mhs_internal.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -52,10 +54,22 @@ __global__ void k_tr_ptr(int N, int nnz, const int* __restrict__ key, int* __res
         for (int r = c + 1; r <= N; ++r) tptr[r] = nnz;
 }
 
-// tmp == nullptr: *tmp_bytes = the scratch size needed.  Else At (N x M, nnz(A)) is
-// written into tptr[N+1], tcol[nnz], tval[nnz].
-hipError_t transpose_csr(const Csr& A, int* tptr, int* tcol, double* tval, void* tmp, size_t* tmp_bytes,
-                         hipStream_t s) {
+// B^T's pattern with the way back to B's values: row of the entry, and the entry itself
+__global__ void k_tr_rows(int M, int nnz, const int* __restrict__ Aptr, const int* __restrict__ idx,
+                          int* __restrict__ trow, int* __restrict__ tperm) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nnz) return;
+    const int e = idx[k];
+    trow[k] = row_of(Aptr, M, e);
+    tperm[k] = e;
+}
+
+namespace {
+
+// What both transposes share: A's entry indices sorted (stably) by column.  tmp == nullptr:
+// *tmp_bytes = the scratch size needed.  Else *idx / *key point into tmp: the sorted entry indices
+// and their columns (nnz each; untouched when nnz == 0).
+hipError_t sort_by_column(const Csr& A, void* tmp, size_t* tmp_bytes, int** idx, int** key, hipStream_t s) {
     const size_t nnz = (size_t)A.nnz;
     const size_t a16 = 256;
     auto up = [&](size_t x) { return (x + a16 - 1) / a16 * a16; };
@@ -70,7 +84,7 @@ hipError_t transpose_csr(const Csr& A, int* tptr, int* tcol, double* tval, void*
         return hipSuccess;
     }
     if (*tmp_bytes < need) return hipErrorInvalidValue;
-    if (nnz == 0) return hipMemsetAsync(tptr, 0, sizeof(int) * ((size_t)A.N + 1), s);
+    if (nnz == 0) return hipSuccess;
     char* p = (char*)tmp;
     int* idx_in = (int*)p;
     p += up(nnz * 4 + 4);
@@ -82,9 +96,39 @@ hipError_t transpose_csr(const Csr& A, int* tptr, int* tcol, double* tval, void*
     hipLaunchKernelGGL(k_tr_iota, dim3(grid), dim3(256), 0, s, (int)nnz, idx_in);
     e = rocprim::radix_sort_pairs((void*)p, sort_bytes, A.col, key_out, (const int*)idx_in, idx_out, nnz, 0,
                                   32 - __builtin_clz((unsigned)(A.N > 1 ? A.N - 1 : 1)), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_tr_gather, dim3(grid), dim3(256), 0, s, A.M, (int)nnz, A.ptr, A.val, idx_out, tcol, tval);
-    hipLaunchKernelGGL(k_tr_ptr, dim3(grid), dim3(256), 0, s, A.N, (int)nnz, key_out, tptr);
+    *idx = idx_out;
+    *key = key_out;
+    return e;
+}
+
+}  // namespace
+
+// tmp == nullptr: *tmp_bytes = the scratch size needed.  Else At (N x M, nnz(A)) is
+// written into tptr[N+1], tcol[nnz], tval[nnz].
+hipError_t transpose_csr(const Csr& A, int* tptr, int* tcol, double* tval, void* tmp, size_t* tmp_bytes,
+                         hipStream_t s) {
+    int *idx = nullptr, *key = nullptr;
+    const hipError_t e = sort_by_column(A, tmp, tmp_bytes, &idx, &key, s);
+    if (e != hipSuccess || !tmp) return e;
+    if (A.nnz == 0) return hipMemsetAsync(tptr, 0, sizeof(int) * ((size_t)A.N + 1), s);
+    const unsigned grid = (unsigned)(((size_t)A.nnz + 255) / 256);
+    hipLaunchKernelGGL(k_tr_gather, dim3(grid), dim3(256), 0, s, A.M, A.nnz, A.ptr, A.val, idx, tcol, tval);
+    hipLaunchKernelGGL(k_tr_ptr, dim3(grid), dim3(256), 0, s, A.N, A.nnz, key, tptr);
+    return hipGetLastError();
+}
+
+// The same without values (A.val is not read): trow[k] = the row of At's entry k in A (ascending
+// within a row of At; duplicates of A stay repeated entries, in A's order), tperm[k] = its position
+// in A's arrays, so Aval[tperm[k]] is its value.  Scratch as transpose_csr.
+hipError_t transpose_pattern(const Csr& A, int* tptr, int* trow, int* tperm, void* tmp, size_t* tmp_bytes,
+                             hipStream_t s) {
+    int *idx = nullptr, *key = nullptr;
+    const hipError_t e = sort_by_column(A, tmp, tmp_bytes, &idx, &key, s);
+    if (e != hipSuccess || !tmp) return e;
+    if (A.nnz == 0) return hipMemsetAsync(tptr, 0, sizeof(int) * ((size_t)A.N + 1), s);
+    const unsigned grid = (unsigned)(((size_t)A.nnz + 255) / 256);
+    hipLaunchKernelGGL(k_tr_rows, dim3(grid), dim3(256), 0, s, A.M, A.nnz, A.ptr, idx, trow, tperm);
+    hipLaunchKernelGGL(k_tr_ptr, dim3(grid), dim3(256), 0, s, A.N, A.nnz, key, tptr);
     return hipGetLastError();
 }
 

@@ -14,6 +14,10 @@
 //   VC_BLOCK_SEARCH  position-indexed sums (12 bytes per C entry)
 //   VC_GLOBAL        rows past one workgroup's 160 KiB (and long rows without products): the row's
 //                    Cval segment zeroed, C.col searched in HBM, sums by HBM atomics
+// Those are the product-form classes: they walk every product of the row.  A masked plan
+// (mhs_values_plan_create_masked: C's pattern may be smaller than the product's) has one more:
+//   VC_DOT           inner-product form: a lane per mask entry (i, j) searches each of the row's A
+//                    columns in B^T's row j.  No LDS sums, no atomics; val_class_masked picks it.
 //
 // LDS arithmetic (gfx950: 160 KiB per CU and per workgroup, 32 waves per CU):
 //   team    12 B x n <= 768 B per row, 32 rows per 256-thread block: <= 24 KiB, 6 blocks per CU
@@ -41,7 +45,8 @@ enum ValClass : int {
     VC_BLOCK_DIRECT = 4,
     VC_BLOCK_SEARCH = 5,
     VC_GLOBAL = 6,
-    VC_COUNT = 7,
+    VC_COUNT = 7,  // the count of product-form classes (what val_class returns is below it)
+    VC_DOT = 7,    // the masked plans' dot class: the last index of mhs_values_info::rows
 };
 constexpr int VAL_NCLASS = 8;  // capacity of the per-class arrays (mhs_values_info::rows)
 
@@ -57,6 +62,9 @@ constexpr int VAL_BLOCK_BYTES = LDS_MAX_C - VAL_STAGE_BYTES;  // dynamic LDS of 
 constexpr int VAL_DENSE_RATIO = 16;    // span <= 16 n: zeroing and gathering the span costs less than searching
 constexpr int VAL_BLOCK_SMALL = 32768; // block launches of at most this much LDS run 256 threads, else 1024
 constexpr int VAL_GROUP = 16;          // lanes that share one A entry in the wave / block / global walks
+// Masked AUTO: a row goes to the dot class when VAL_DOT_RATIO x its dot form's search steps < its products
+// (a search step is a dependent HBM / L2 load, a product a streamed one: DESIGN section 11 has the sweep)
+constexpr int VAL_DOT_RATIO = 2;
 
 // LDS bytes of one row, per method
 __host__ __device__ constexpr long long val_lds_search(long long n) { return 12 * ((n + 1) & ~1LL); }  // sums, then columns
@@ -85,6 +93,30 @@ __host__ __device__ inline int val_class(int n, long long span, long long produc
     if (span <= VAL_BLOCK_DIRECT_SPAN) return VC_BLOCK_DIRECT;
     if (n <= VAL_BLOCK_SEARCH_N) return VC_BLOCK_SEARCH;
     return VC_GLOBAL;
+}
+// How a masked plan may compute its rows (mhs_mask_form of the C ABI)
+enum ValMaskForm : int { VM_AUTO = 0, VM_PRODUCT = 1, VM_DOT = 2 };
+// smallest k with 2^k >= x (x >= 1)
+__host__ __device__ inline int val_ceil_log2(long long x) {
+    int k = 0;
+    while (k < 62 && (1LL << k) < x) ++k;
+    return k;
+}
+// Search steps of one mask entry against a B^T row of `len` entries: the lower bound and the look at its result
+__host__ __device__ inline long long val_dot_steps(long long len) { return 1 + val_ceil_log2(len + 1); }
+constexpr long long VAL_SAT = 0x7fffffffffffffffLL;
+__host__ __device__ inline long long val_sat_add(long long a, long long b) { return a > VAL_SAT - b ? VAL_SAT : a + b; }
+__host__ __device__ inline long long val_sat_mul(long long a, long long b) {
+    return a > 0 && b > 0 && a > VAL_SAT / b ? VAL_SAT : a * b;
+}
+// The class of a masked plan's row: nA entries in A's row, dot_cost = nA x the sum of val_dot_steps
+// over the row's mask entries (saturated).  ratio: VAL_DOT_RATIO, or the diagnostic override.
+__host__ __device__ inline int val_class_masked(int n, long long span, long long products, int nA, long long dot_cost,
+                                                int form, int ratio = VAL_DOT_RATIO) {
+    const bool can = n > 0 && nA > 0;
+    if (can && form == VM_DOT) return VC_DOT;
+    if (can && form == VM_AUTO && val_sat_mul(ratio, dot_cost) < products) return VC_DOT;
+    return val_class(n, span, products);
 }
 // LDS bytes a row needs in its class (0: none)
 __host__ __device__ inline int val_row_need(int cls, int n, long long span) {
@@ -118,6 +150,7 @@ enum ValKernel : int {
     VK_BLOCK_DIRECT,  // k_val_block<T, direct>
     VK_BLOCK_SEARCH,  // k_val_block<T, search>
     VK_GLOBAL,        // k_val_global
+    VK_DOT,           // k_val_dot
 };
 
 // One launch.  `region`: LDS bytes per row in flight (team slice, wave slice, or the block's all).
@@ -158,6 +191,8 @@ inline ValPlan plan_values(const ValCounts& c) {
         l.region = region;
         l.count = c.rows[cls];
     };
+    // dot rows (masked plans only): a wave per row, static LDS only
+    if (c.rows[VC_DOT] > 0) add(VK_DOT, VC_DOT, ((long long)c.rows[VC_DOT] + WPB - 1) / WPB, VAL_WAVE_GRID, 64 * WPB, 0, 0);
     if (c.rows[VC_GLOBAL] > 0) add(VK_GLOBAL, VC_GLOBAL, c.rows[VC_GLOBAL], VAL_GLOBAL_GRID, 1024, 0, 0);
     for (int k = 0; k < 2; ++k) {
         const int cls = k ? VC_BLOCK_DIRECT : VC_BLOCK_SEARCH;

@@ -7,6 +7,9 @@
 // Aval / Bval only for values, and -- told the row's sorted columns -- only finds each product's
 // slot: by subtraction (direct classes) or by binary search (team, search and global classes).
 // Sums are FP64 atomics: ds_add_f64 in LDS, global_atomic_add_f64 in the global class.
+// Masked plans (mhs_values_plan_create_masked: C's pattern is a mask, products outside it are dropped)
+// classify by val_class_masked, count the kept products in place of the verify walk, and may send rows
+// to the dot class: k_val_dot, the inner-product form over B^T's pattern (no sums shared, no atomics).
 #include "mhs_internal.hpp"
 
 #include <climits>
@@ -141,8 +144,9 @@ __global__ __launch_bounds__(256) void k_val_check_cols(const int* __restrict__ 
 // One thread per row of C.  FILL false: count the rows and the largest LDS need per class (one
 // reservation per block and class, counters one per 128-byte line).  FILL true: write the rows into
 // their class lists, class c's list at the prefix of the counts before it.
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_val_classify(ValPattern p, int* __restrict__ cnt, int* __restrict__ lists) {
+// MASKED: the class by val_class_masked -- the row's A entries and, with B^T's row pointer, its dot cost.
+template <bool FILL, bool MASKED>
+__global__ __launch_bounds__(256) void k_val_classify(ValPattern p, ValMask m, int* __restrict__ cnt, int* __restrict__ lists) {
     __shared__ int s_cnt[VAL_NCLASS], s_need[VAL_NCLASS], s_base[VAL_NCLASS];
     __shared__ unsigned long long s_prod;
     for (int base = blockIdx.x * 256; base < p.M; base += gridDim.x * 256) {
@@ -155,14 +159,25 @@ __global__ __launch_bounds__(256) void k_val_classify(ValPattern p, int* __restr
             const int s = p.Cptr[i], e = p.Cptr[i + 1];
             const int n = e - s;
             long long span = 0, products = 0;
-            if (n > 0) {
-                span = (long long)p.Ccol[e - 1] - p.Ccol[s] + 1;
+            if (n > 0) span = (long long)p.Ccol[e - 1] - p.Ccol[s] + 1;
+            if (n > 0 || MASKED) {  // (a mask's empty rows still have products: mhs_values_info counts them all)
                 for (int k = p.Aptr[i]; k < p.Aptr[i + 1]; ++k) {
                     const int ac = p.Acol[k];
                     products += p.Bptr[ac + 1] - p.Bptr[ac];
                 }
             }
-            cls = val_class(n, span, products);
+            if constexpr (MASKED) {
+                const int nA = p.Aptr[i + 1] - p.Aptr[i];
+                long long steps = 0;
+                if (m.tptr && nA > 0 && m.form != VM_PRODUCT)
+                    for (int q = s; q < e; ++q) {
+                        const int j = p.Ccol[q];
+                        steps = val_sat_add(steps, val_dot_steps(m.tptr[j + 1] - m.tptr[j]));
+                    }
+                cls = val_class_masked(n, span, products, nA, val_sat_mul(nA, steps), m.tptr ? m.form : VM_PRODUCT, m.ratio);
+            } else {
+                cls = val_class(n, span, products);
+            }
             rank = atomicAdd(&s_cnt[cls], 1);
             if (!FILL) {
                 atomicMax(&s_need[cls], val_row_need(cls, n, span));
@@ -201,6 +216,24 @@ __global__ __launch_bounds__(256) void k_val_verify(ValPattern p, int* __restric
                                 [&](int c) { ok = ok && find_slot(p.Ccol + s, n, c) >= 0; });
         if (!ok) atomicMin(bad, i);
     }
+}
+
+// Masked plans, in place of the verify walk: the products whose column is in the row's mask, counted.
+__global__ __launch_bounds__(256) void k_val_count_kept(ValPattern p, unsigned long long* __restrict__ kept) {
+    __shared__ unsigned long long s_kept;
+    if (threadIdx.x == 0) s_kept = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    unsigned long long mine = 0;
+    for (int i = blockIdx.x * WPB + (threadIdx.x >> 6); i < p.M; i += gridDim.x * WPB) {
+        const int s = p.Cptr[i], n = p.Cptr[i + 1] - s;
+        if (n <= 0) continue;
+        walk_columns<VAL_GROUP>(p, i, lane / VAL_GROUP, 64 / VAL_GROUP, lane % VAL_GROUP,
+                                [&](int c) { mine += find_slot(p.Ccol + s, n, c) >= 0; });
+    }
+    if (mine) atomicAdd(&s_kept, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_kept) atomicAdd(kept, s_kept);
 }
 
 // ---------------------------------------------------------- value kernels ---
@@ -354,6 +387,58 @@ __global__ __launch_bounds__(1024) void k_val_global(ValArgs a, const int* __res
     }
 }
 
+// Dot class (masked plans): one wave64 per row, WPB rows per block.  Lane l owns the mask entries
+// l, l + 64, ... of the row, 64 at a time: for its entry (row, j) it holds B^T row j's bounds, and for
+// every A entry of the row -- staged 64 at a time as (column, value) in the wave's static LDS -- finds
+// the A column's lower bound in trow[lo0, hi0) and adds av * Bval[tperm[q]] over the equal run (B's
+// duplicates, in B's order).  One sum per entry in a register, in A's entry order: no atomics, the
+// same bits on every call; the entry is stored once, reached or not.
+struct DotStage {
+    int col[64];
+    double av[64];
+};
+__global__ __launch_bounds__(256) void k_val_dot(ValArgs a, ValTrans tr, const int* __restrict__ list, int count) {
+    __shared__ DotStage stage[WPB];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    DotStage& d = stage[wave];
+    for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB) {
+        const int row = list[idx];
+        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
+        const int a0 = a.Aptr[row], ae = a.Aptr[row + 1];
+        for (int p0 = 0; p0 < n; p0 += 64) {
+            const int p = p0 + lane;
+            int lo0 = 0, hi0 = 0;
+            if (p < n) {
+                const int j = a.Ccol[s + p];
+                lo0 = tr.tptr[j];
+                hi0 = tr.tptr[j + 1];
+            }
+            double sum = 0.0;
+            for (int k0 = a0; k0 < ae; k0 += 64) {
+                const int cnt = ae - k0 < 64 ? ae - k0 : 64;
+                if (lane < cnt) {
+                    d.col[lane] = a.Acol[k0 + lane];
+                    d.av[lane] = a.Aval[k0 + lane];
+                }
+                vwave_sync();
+                if (lo0 < hi0)
+                    for (int e = 0; e < cnt; ++e) {
+                        const int ac = d.col[e];
+                        int lo = lo0, hi = hi0;
+                        while (lo < hi) {
+                            const int mid = (lo + hi) >> 1;
+                            if (tr.trow[mid] < ac) lo = mid + 1;
+                            else hi = mid;
+                        }
+                        for (; lo < hi0 && tr.trow[lo] == ac; ++lo) sum += d.av[e] * a.Bval[tr.tperm[lo]];
+                    }
+                vwave_sync();
+            }
+            if (p < n) a.Cval[s + p] = sum;
+        }
+    }
+}
+
 int blocks_for(long long items, int per, int cap) {
     long long b = (items + per - 1) / per;
     if (b < 1) b = 1;
@@ -384,15 +469,26 @@ void launch_val_check_cols(const int* ptr, const int* col, int M, int ncols, boo
 void launch_val_classify(const ValPattern& p, int* cnt, int* lists, hipStream_t s) {
     if (p.M <= 0) return;
     const int grid = blocks_for(p.M, 256, 16384);
-    hipLaunchKernelGGL(k_val_classify<false>, dim3(grid), dim3(256), 0, s, p, cnt, lists);
-    hipLaunchKernelGGL(k_val_classify<true>, dim3(grid), dim3(256), 0, s, p, cnt, lists);
+    hipLaunchKernelGGL((k_val_classify<false, false>), dim3(grid), dim3(256), 0, s, p, ValMask{}, cnt, lists);
+    hipLaunchKernelGGL((k_val_classify<true, false>), dim3(grid), dim3(256), 0, s, p, ValMask{}, cnt, lists);
+}
+void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int* cnt, int* lists, hipStream_t s) {
+    if (p.M <= 0) return;
+    const int grid = blocks_for(p.M, 256, 16384);
+    hipLaunchKernelGGL((k_val_classify<false, true>), dim3(grid), dim3(256), 0, s, p, m, cnt, lists);
+    hipLaunchKernelGGL((k_val_classify<true, true>), dim3(grid), dim3(256), 0, s, p, m, cnt, lists);
+}
+void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s) {
+    if (p.M <= 0) return;
+    hipLaunchKernelGGL(k_val_count_kept, dim3(blocks_for(p.M, WPB, 16384)), dim3(256), 0, s, p,
+                       (unsigned long long*)(cnt + (3 * VAL_NCLASS + 1) * BINCNT_STRIDE));
 }
 void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s) {
     if (p.M <= 0) return;
     hipLaunchKernelGGL(k_val_verify, dim3(blocks_for(p.M, WPB, 16384)), dim3(256), 0, s, p, bad);
 }
 
-void issue_values(const ValLaunch& l, const ValArgs& a, const int* list, hipStream_t s) {
+void issue_values(const ValLaunch& l, const ValArgs& a, const ValTrans& t, const int* list, hipStream_t s) {
     const dim3 g(l.grid), b(l.block);
     switch (l.kernel) {
     case VK_TEAM: hipLaunchKernelGGL(k_val_team, g, b, l.lds, s, a, list, l.count, l.region); break;
@@ -407,6 +503,7 @@ void issue_values(const ValLaunch& l, const ValArgs& a, const int* list, hipStre
         else hipLaunchKernelGGL((k_val_block<256, false>), g, b, l.lds, s, a, list, l.count, l.region);
         break;
     case VK_GLOBAL: hipLaunchKernelGGL(k_val_global, g, b, 0, s, a, list, l.count); break;
+    case VK_DOT: hipLaunchKernelGGL(k_val_dot, g, b, 0, s, a, t, list, l.count); break;
     }
 }
 

@@ -1,7 +1,7 @@
 // spgemm_main.cpp -- the `spgemm <file.mtx>` driver (reference src/main.cu:74-217)
 // on top of the C-ABI, printing the reference's stdout lines.
 //
-//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] <file.mtx>
+//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -19,10 +19,16 @@
 //   --reuse N after the product, a values plan on C's pattern (mhs_values_plan_create) and N values-only
 //             calls on the same A and B (mhs_spgemm_values); their mean time on a line of its own, and
 //             with --check the recomputed values against the product's own by CSR::operator==
+//   --masked N after the product (and --reuse), a masked values plan (mhs_values_plan_create_masked, AUTO) of
+//             the same A and B on A's own pattern -- A*A kept where A has entries; needs rowA = colA -- and
+//             N calls; their mean time, the kept products and the dot rows on a line of its own, and with
+//             --check the values against the product's own C filtered to A's pattern (the 1e-9 rule)
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
 // e2e line that includes Form_mask_matrix_B.
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +36,7 @@
 #include <iomanip>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "mh_spgemm.hpp"
 #include "mhs_vendor.h"
@@ -58,8 +65,51 @@ static void recycle(Tool& tools, CSR& C) {
     C.d_val = nullptr;
 }
 
+// --masked N: A * B kept on A's pattern by a masked plan, N calls; with check against C (the full
+// product, on the device) filtered to A's pattern on the host.
+static void run_masked(Tool& tools, const CSR& A, const CSR& B, CSR& C, int calls, bool check) {
+    CSR mask;  // A's pattern (borrowed device arrays) with values of its own
+    mask.M = A.M;
+    mask.N = B.N;
+    mask.nnz = A.nnz;
+    mhs_shim::hip_check(hipMalloc((void**)&mask.d_val, sizeof(double) * (size_t)(A.nnz > 0 ? A.nnz : 1)), "hipMalloc mask");
+    mask.d_ptr = A.d_ptr;
+    mask.d_col = A.d_col;
+    try {
+        mhs_shim::ValuesPlan plan(tools, A, B, mask, true, MHS_MASK_AUTO);
+        double sum = 0;
+        for (int i = 0; i < calls; ++i) {
+            MH_spgemm_values(A, B, mask, plan);
+            sum += plan.last_ms;
+        }
+        const mhs_values_info info = plan.info();
+        std::printf("MH-SpGEMM masked (A's pattern) mean of %d calls is %.3lf ms, kept %lld of %lld products, dot rows %d\n", calls,
+                    sum / calls, plan.kept(), (long long)info.products, (int)info.rows[7]);
+        if (check) {
+            C.D2H();
+            std::vector<double> got((size_t)(A.nnz > 0 ? A.nnz : 1));
+            mhs_shim::hip_check(hipMemcpy(got.data(), mask.d_val, sizeof(double) * (size_t)A.nnz, hipMemcpyDeviceToHost), "D2H mask");
+            int err = 0;
+            for (int i = 0; i < A.M; ++i)
+                for (int k = A.ptr[i]; k < A.ptr[i + 1]; ++k) {
+                    const int *row = C.col + C.ptr[i], *end = C.col + C.ptr[i + 1];
+                    const int* hit = std::lower_bound(row, end, A.col[k]);
+                    const double want = hit != end && *hit == A.col[k] ? C.val[hit - C.col] : 0.0;
+                    const double d = std::fabs(want - got[(size_t)k]);
+                    if (!(d < 1e-9 || d < 1e-9 * std::fabs(want))) ++err;
+                }
+            std::puts(err == 0 ? "masked pass" : "masked fail");
+        }
+    } catch (const std::exception&) {
+        std::puts("masked fail");
+    }
+    (void)hipFree(mask.d_val);
+    mask.d_ptr = mask.d_col = nullptr;  // A's
+    mask.d_val = nullptr;
+}
+
 int main(int argc, char** argv) {
-    int iters = 1, warmup = 1, reuse = 0;
+    int iters = 1, warmup = 1, reuse = 0, masked = 0;
     bool aat = false, vendor = false, check = false, cache = false;
     std::string csv;
     const char* filename = nullptr;
@@ -73,12 +123,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--csv") && i + 1 < argc) csv = argv[++i];
         else if (!std::strcmp(argv[i], "--cache")) cache = true;
         else if (!std::strcmp(argv[i], "--reuse") && i + 1 < argc) reuse = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked = std::atoi(argv[++i]);
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
-    if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0) {
+    if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -187,6 +238,8 @@ int main(int argc, char** argv) {
                 }
             }
         }
+        if (masked > 0 && A.M != A.N) std::puts("masked: A's pattern as the mask must have rowA = colA. Skipped.");
+        else if (masked > 0) run_masked(tools, A, B, C, masked, check);
         C.d_release_csr();
     } catch (const std::exception&) {
         std::printf("MH-SpGEMM failed!!!\n");

@@ -29,6 +29,10 @@ MHS_OPT_TINY_FIRST_ROWS = 4
 MHS_OPT_SPECULATE = 5
 MHS_OPT_GROUP_GRID = 6
 
+MHS_MASK_AUTO = 0
+MHS_MASK_PRODUCT = 1
+MHS_MASK_DOT = 2
+
 STATUS_NAMES = {0: "MHS_OK", 1: "MHS_ERR_HIP", 2: "MHS_ERR_OOM", 3: "MHS_ERR_INVALID",
                 4: "MHS_ERR_OVERFLOW", 5: "MHS_ERR_IO"}
 
@@ -148,6 +152,12 @@ def lib() -> ctypes.CDLL:
         L.mhs_values_plan_info.restype = c_int
         L.mhs_values_plan_destroy.argtypes = [c_void_p, c_void_p]
         L.mhs_values_plan_destroy.restype = None
+        if hasattr(L, "mhs_values_plan_create_masked"):  # (masked product: a later addition to ABI 10)
+            L.mhs_values_plan_create_masked.argtypes = [c_void_p, P(mhs_csr), P(mhs_csr), P(mhs_csr), c_int,
+                                                        P(c_void_p)]
+            L.mhs_values_plan_create_masked.restype = c_int
+            L.mhs_values_plan_kept.argtypes = [c_void_p, P(ctypes.c_int64)]
+            L.mhs_values_plan_kept.restype = c_int
     _lib = L
     return L
 

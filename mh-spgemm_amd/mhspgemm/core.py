@@ -360,7 +360,8 @@ def spgemm(tool: Tool, A: CSR, B: CSR, timing: bool = True):
     return DeviceCSR(tool, c), (Timing.from_c(t) if t is not None else None)
 
 
-VALUES_CLASSES = ("none", "team", "wave_direct", "wave_search", "block_direct", "block_search", "global")
+VALUES_CLASSES = ("none", "team", "wave_direct", "wave_search", "block_direct", "block_search", "global", "dot")
+MASK_FORMS = {"auto": L.MHS_MASK_AUTO, "product": L.MHS_MASK_PRODUCT, "dot": L.MHS_MASK_DOT}
 
 
 class ValuesPlan:
@@ -371,11 +372,24 @@ class ValuesPlan:
     the pattern of A*B.  The plan borrows the six pattern arrays and keeps Python references
     to their owners, so they cannot be collected under it; they must not change while the
     plan lives.  Creation validates the patterns on the device (``MHSpGEMMError`` with status
-    3 otherwise); ``run`` does not validate again."""
+    3 otherwise); ``run`` does not validate again.
 
-    def __init__(self, tool: Tool, A: CSR, B: CSR, C):
+    ``masked=True`` (mhs_values_plan_create_masked): C's pattern is a mask and may be smaller than
+    the product's -- products outside it are dropped, mask entries no product reaches get 0.0.
+    ``form`` then says how rows are computed: ``"product"`` (walk the products, drop the misses),
+    ``"dot"`` (per mask entry, A's row against B's column, through B^T's pattern kept in the plan)
+    or ``"auto"`` (per row, the cheaper).  An integer ``form`` is passed to the library as it is."""
+
+    def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto"):
         if not hasattr(L.lib(), "mhs_values_plan_create"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no values-only entry points")
+        if masked and not hasattr(L.lib(), "mhs_values_plan_create_masked"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no masked entry points")
+        if isinstance(form, str):
+            if form not in MASK_FORMS:
+                raise ValueError(f"form: one of {sorted(MASK_FORMS)}, not {form!r}")
+            form = MASK_FORMS[form]
+        self.masked, self.form = bool(masked), int(form)
         self.tool, self.A, self.B, self.C = tool, A, B, C
         # (tensors can be rebound on the CSR objects: hold the arrays themselves too)
         self._keep = (A.d_ptr, A.d_col, A.dev, B.d_ptr, B.d_col, B.dev,
@@ -385,9 +399,14 @@ class ValuesPlan:
         self._c = c
         self.nnzA, self.nnzB, self.nnzC = int(a.nnz), int(b.nnz), int(c.nnz)
         self.plan = ctypes.c_void_p()
-        rc = L.lib().mhs_values_plan_create(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
-                                            ctypes.byref(self.plan))
-        _check(tool.ctx, rc, "mhs_values_plan_create")
+        if masked:
+            rc = L.lib().mhs_values_plan_create_masked(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                       self.form, ctypes.byref(self.plan))
+            _check(tool.ctx, rc, "mhs_values_plan_create_masked")
+        else:
+            rc = L.lib().mhs_values_plan_create(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                ctypes.byref(self.plan))
+            _check(tool.ctx, rc, "mhs_values_plan_create")
 
     @staticmethod
     def _ptr(t, n, what):
@@ -415,12 +434,18 @@ class ValuesPlan:
         return float(ms.value) if timed else None
 
     def info(self) -> dict:
-        """Rows per class (by name and as the ``rows`` list indexed by class id), products, nnzC, plan_bytes."""
+        """Rows per class (by name and as the ``rows`` list indexed by class id), products, nnzC, plan_bytes,
+        and kept_products: the products that land in C's pattern (all of them unless the plan is masked)."""
         i = L.mhs_values_info()
         _check(self.tool.ctx, L.lib().mhs_values_plan_info(self.plan, ctypes.byref(i)), "mhs_values_plan_info")
         rows = [int(x) for x in i.rows]
         d = {"rows": rows, "products": int(i.products), "nnzC": int(i.nnzC), "plan_bytes": int(i.plan_bytes)}
         d.update({name: rows[k] for k, name in enumerate(VALUES_CLASSES)})
+        d["kept_products"] = d["products"]
+        if hasattr(L.lib(), "mhs_values_plan_kept"):
+            kept = ctypes.c_int64(0)
+            _check(self.tool.ctx, L.lib().mhs_values_plan_kept(self.plan, ctypes.byref(kept)), "mhs_values_plan_kept")
+            d["kept_products"] = int(kept.value)
         return d
 
     def close(self):

@@ -1,0 +1,179 @@
+#!/usr/bin/env python3
+"""masked_bench.py -- the masked product against the full call a user makes today, one workload per run.
+
+    python tools/masked_bench.py [--workload triangle|cant|scircuit] [--blocks 5] [--window 0.4] [--full-only]
+
+Workloads: `triangle` is L*L on L's pattern, L the strictly lower triangle of a symmetrised
+synth.powerlaw graph with all values 1.0; `cant` and `scircuit` are A*A on A's pattern.
+
+Kinds, timed in alternating blocks after warm-up (the method of tools/values_bench.py: a block is
+enough calls for its window to last `--window` seconds between two host clock reads after device
+synchronises; per kind the median of the blocks' per-call times and the spread max - min):
+  full          the repeated full mhs_spgemm call (no filter counted), each C handed back to the pool
+  product, dot  the masked plan in a forced form
+  auto@R        the masked plan in AUTO with MHS_VAL_DOT_RATIO=R at its creation, R in 1 .. 64
+Before timing, every masked plan's output is checked against the full product filtered to the mask
+(the reference 1e-9 rule; mask entries outside the product exactly 0.0).
+
+--full-only times `full` alone and needs none of the masked entry points, so it runs against an
+older library (MHS_LIB=/path/to/libmhspgemm.so): the parent commit's, for the comparison the table
+reports.  Prints one JSON line."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (ROOT, ROOT / "mh-spgemm_amd"):
+    if str(p) not in sys.path:
+        sys.path.insert(0, str(p))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import mhspgemm  # noqa: E402
+from mhspgemm import _lib as L  # noqa: E402
+from mhspgemm import synth  # noqa: E402
+
+RATIOS = (1, 2, 4, 8, 16, 32, 64)
+
+
+def lower_triangle(n: int, seed: int = 3) -> mhspgemm.CSR:
+    G = synth.powerlaw(n, seed=seed)
+    r = np.repeat(np.arange(G.M, dtype=np.int64), np.diff(G.ptr))
+    c = G.col.astype(np.int64)
+    off = r != c
+    key = np.unique(np.maximum(r[off], c[off]) * n + np.minimum(r[off], c[off]))  # symmetrised, strictly lower
+    ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(key // n, minlength=n), out=ptr[1:])
+    return mhspgemm.CSR(n, n, ptr.astype(np.int32), (key % n).astype(np.int32), np.ones(len(key)))
+
+
+def filtered(Cp, Ci, Cv, Mp, Mc, N):
+    rows = lambda p: np.repeat(np.arange(len(p) - 1, dtype=np.int64), np.diff(p))  # noqa: E731
+    kC, kM = rows(Cp) * N + Ci, rows(Mp) * N + Mc
+    pos = np.minimum(np.searchsorted(kC, kM), max(len(kC) - 1, 0))
+    hit = kC[pos] == kM if len(kC) else np.zeros(len(kM), bool)
+    return np.where(hit, Cv[pos], 0.0) if len(kC) else np.zeros(len(kM)), hit
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--workload", default="triangle", choices=("triangle", "cant", "scircuit"))
+    ap.add_argument("--n", type=int, default=50_000, help="vertices of the triangle workload's graph")
+    ap.add_argument("--blocks", type=int, default=5, help="timed blocks per kind")
+    ap.add_argument("--window", type=float, default=0.4, help="seconds a timed block should last")
+    ap.add_argument("--warmup", type=int, default=5, help="warm-up calls per kind (1 for a kind slower than 0.1 s a call)")
+    ap.add_argument("--full-only", action="store_true", help="time the repeated full call alone")
+    args = ap.parse_args()
+
+    dev = 0
+    torch.cuda.set_device(dev)
+    if args.workload == "triangle":
+        A, source = lower_triangle(args.n), f"synth.powerlaw({args.n}), symmetrised, strictly lower, values 1.0"
+    else:
+        A, source = synth.load_or_synth(args.workload)
+    flop = mhspgemm.flop_count_np(A.col, A.ptr)
+    A.H2D(dev)
+    tool = mhspgemm.Tool(dev)
+    tool.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+
+    def sync():
+        torch.cuda.synchronize(dev)
+
+    out = {"workload": args.workload, "source": source, "M": A.M, "nnzA": A.nnz, "products": int(flop),
+           "blocks": args.blocks, "lib": L.lib_path()}
+    C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
+    out["nnzC"] = C.nnz
+    print(f"{args.workload}: nnz(A) {A.nnz}, {flop} products, nnz(C) {C.nnz}", file=sys.stderr, flush=True)
+
+    plans = {}
+    if not args.full_only:
+        Cp, Ci, Cv = C.to_host()
+        want, hit = filtered(Cp, Ci, Cv, A.ptr, A.col, A.N)
+        out["mask_entries"] = A.nnz
+        out["mask_entries_reached"] = int(hit.sum())
+        mask = mhspgemm.CSR(A.M, A.N, A.ptr, A.col, np.zeros(A.nnz))
+        mask.H2D(dev)
+        kinds = [("product", "product", None), ("dot", "dot", None)] + [(f"auto@{r}", "auto", r) for r in RATIOS]
+        out["plans"] = {}
+        for name, form, ratio in kinds:
+            if ratio is None:
+                os.environ.pop("MHS_VAL_DOT_RATIO", None)
+            else:
+                os.environ["MHS_VAL_DOT_RATIO"] = str(ratio)  # read by the library at plan creation
+            plan = mhspgemm.ValuesPlan(tool, A, A, mask, masked=True, form=form)
+            info = plan.info()
+            res = torch.full((A.nnz,), float("nan"), dtype=torch.float64, device=f"cuda:{dev}")
+            plan.run(out=res)
+            sync()
+            got = res.cpu().numpy()
+            assert mhspgemm.compare_ref(A.ptr, A.col, want, A.ptr, A.col, got), f"{name}: outside the 1e-9 rule"
+            assert np.all(got[~hit] == 0.0), f"{name}: an unreached mask entry is not 0.0"
+            plans[name] = plan
+            print(f"{name}: checked, dot rows {info['dot']}", file=sys.stderr, flush=True)
+            out["plans"][name] = {"dot_rows": info["dot"], "kept_products": info["kept_products"],
+                                  "plan_bytes": info["plan_bytes"],
+                                  "classes": {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}}
+        os.environ.pop("MHS_VAL_DOT_RATIO", None)
+        out["checked"] = "every plan against the full product filtered to the mask: the reference 1e-9 rule, misses exactly 0.0"
+
+    # ---- timing
+    tool.set_option(L.MHS_OPT_SYNC, 0)
+    state = {"C": None}
+
+    def full_calls(n):
+        for _ in range(n):
+            if state["C"] is not None:
+                state["C"].release()
+            state["C"], _ = mhspgemm.spgemm(tool, A, A, timing=False)
+
+    def masked_calls(plan):
+        def fn(n):
+            for _ in range(n):
+                plan.run()
+        return fn
+
+    def timed(fn, n):
+        sync()
+        t0 = time.perf_counter()
+        fn(n)
+        sync()
+        return (time.perf_counter() - t0) / n * 1e3  # ms per call
+
+    kinds = [("full", full_calls)] + [(name, masked_calls(plan)) for name, plan in plans.items()]
+    calls = {}
+    for name, fn in kinds:
+        # (a forced dot plan can take seconds a call on hub rows: warm up and size the block by its first call)
+        first = timed(fn, 1)
+        few = first > 100.0
+        fn(1 if few else args.warmup)
+        per = timed(fn, 2 if few else 20)
+        calls[name] = max(1 if few else 20, int(args.window * 1e3 / per) + 1)
+        print(f"{name}: {per:.4f} ms a call, {calls[name]} calls a block", file=sys.stderr, flush=True)
+    res = {name: [] for name, _ in kinds}
+    for _ in range(args.blocks):
+        for name, fn in kinds:
+            res[name].append(timed(fn, calls[name]))
+    tool.set_option(L.MHS_OPT_SYNC, 1)
+    for name, _ in kinds:
+        r = res[name]
+        out[name] = {"ms_median": round(statistics.median(r), 5), "ms_min": round(min(r), 5), "ms_max": round(max(r), 5),
+                     "spread_ms": round(max(r) - min(r), 5), "calls_per_block": calls[name],
+                     "blocks_ms": [round(x, 5) for x in r]}
+    if state["C"] is not None:
+        state["C"].release()
+    for plan in plans.values():
+        plan.close()
+    C.release()
+    tool.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
