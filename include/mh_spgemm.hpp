@@ -281,6 +281,18 @@ inline void MH_spgemm_values(const CSR& A, const CSR& B, CSR& C, mhs_shim::Value
     }
 }
 
+// The backward of MH_spgemm_values (mhs_spgemm_values_grad): for the cotangent dC on C's pattern (device,
+// nnz(C) doubles) the gradients of A.d_val into dA and of B.d_val into dB (device, nnz(A) / nnz(B) doubles;
+// either nullptr: not computed).  The call's hipEvent time goes to plan.last_ms.
+inline void MH_spgemm_values_grad(const CSR& A, const CSR& B, const double* dC, double* dA, double* dB,
+                                  mhs_shim::ValuesPlan& plan) {
+    const int rc = mhs_spgemm_values_grad(plan.ctx, plan.plan, A.d_val, B.d_val, dC, dA, dB, &plan.last_ms);
+    if (rc != MHS_OK) {
+        std::printf("%s\n", mhs_last_error(plan.ctx));
+        throw std::runtime_error(mhs_last_error(plan.ctx));
+    }
+}
+
 // src/utils.cpp:20-46 (B = A^T for AAT, src/main.cu:98-99) on the device: A must be
 // device-resident; B gets device arrays (and host arrays, as the reference's B).
 inline void matrix_transposition(const CSR& A, CSR& B, Tool& tools) {

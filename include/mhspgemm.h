@@ -83,6 +83,14 @@ const char *mhs_last_error(const mhs_ctx *ctx);
 /* Run on a caller-owned hipStream_t (e.g. PyTorch's current stream); NULL
  * restores the context's own stream. */
 int mhs_ctx_set_stream(mhs_ctx *ctx, void *hip_stream);
+/* The device's default (null) stream has the handle NULL and so cannot be given to mhs_ctx_set_stream:
+ * NULL selects the context's own stream, which is non-blocking -- it has no order against the null
+ * stream.  A caller whose data is produced or consumed on the null stream (PyTorch's default stream)
+ * and who runs unsynchronised calls (MHS_OPT_SYNC 0) fences them with this: after == 0, before the
+ * call: the context stream waits for everything queued on the null stream so far; after == 1, after
+ * the call: the null stream waits for everything queued on the context stream so far.  Two event
+ * operations, no host synchronisation.  An addition to ABI version 10: look the symbol up before use. */
+int mhs_ctx_fence_default_stream(mhs_ctx *ctx, int after);
 /* Release cached workspace and pooled output buffers. */
 int mhs_ctx_trim(mhs_ctx *ctx);
 
@@ -234,6 +242,28 @@ int mhs_values_plan_create_masked(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr 
 /* The products that land in the plan's C pattern (mhs_values_info::products counts them all).
  * A plan of mhs_values_plan_create: kept == products. */
 int mhs_values_plan_kept(const mhs_values_plan *plan, int64_t *kept_products);
+
+/* ---- the backward of a values call: gradients of Aval and Bval on a kept plan -------------
+ * For callers that differentiate through the product on fixed patterns (adjoint sensitivities of a
+ * Galerkin product, learned AMG or sparsifiers, a sparse-sparse product inside a PyTorch model).
+ * (Aval, Bval) -> Cval is bilinear; with dCval the cotangent on the plan's C pattern (nnz(C) doubles),
+ *   dAval[p] = sum over B's row k of Bval[(k,j)] * dCval[slot(i,j)]          for the A entry p = (i,k)
+ *   dBval[q] = sum over the A entries (i,k) of Aval[(i,k)] * dCval[slot(i,j)] for the B entry q = (k,j)
+ * Duplicates in B each contribute to dAval, duplicates in A each get their own (equal) gradient and each
+ * contribute to dBval.  On a masked plan a product whose column is not in the mask row contributes to
+ * neither.  dAval: nnz(A) doubles, dBval: nnz(B) doubles; either may be NULL (that side is not computed),
+ * not both.  Bval is read only when dAval is given and Aval only when dBval is given; the unused one may
+ * be NULL.  Outputs must not alias inputs.  Every entry of a requested output is written: an entry that
+ * no kept product reaches (an empty B row, an empty C row, a B row no A column points at) gets exactly 0.0.
+ * dAval is summed without atomics in a fixed order: two calls give the same bits.  dBval is summed by
+ * FP64 atomics: its order is not fixed.  A zero cotangent times a non-finite value may give 0 or NaN.
+ * ms and MHS_OPT_SYNC as in mhs_spgemm_values: a call with ms == NULL and MHS_OPT_SYNC 0 allocates nothing,
+ * reads nothing back and does not synchronise; it queues a zero fill of the outputs and the kernels on
+ * the context stream.  Hot calls do not re-validate.  NULL ctx, plan or dCval, both outputs NULL, or a
+ * needed input NULL: MHS_ERR_INVALID before any HIP call.  Any plan will do (mhs_values_plan_create or
+ * _masked, any form).  An addition to ABI version 10, like the entries above. */
+int mhs_spgemm_values_grad(mhs_ctx *ctx, mhs_values_plan *plan, const double *Aval, const double *Bval,
+                           const double *dCval, double *dAval, double *dBval, double *ms);
 
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).

@@ -136,6 +136,7 @@ struct mhs_values_plan {
     int list_off[VAL_NCLASS] = {};
     ValCounts counts{};
     ValPlan plan{};
+    ValPlan gplan{};        // the backward's launches (plan_grad)
     hipEvent_t ev[2] = {};  // timed calls
 };
 
@@ -1221,6 +1222,17 @@ int mhs_ctx_set_stream(mhs_ctx* ctx, void* s) {
     return MHS_OK;
 }
 
+int mhs_ctx_fence_default_stream(mhs_ctx* ctx, int after) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (after != 0 && after != 1) return fail(ctx, MHS_ERR_INVALID, "mhs_ctx_fence_default_stream: after is 0 or 1");
+    MHS_HIP(hipSetDevice(ctx->device));
+    // (stream_ev: a wait already queued keeps the record it was queued behind, so the event can be recorded again)
+    hipStream_t from = after ? ctx->stream : nullptr, to = after ? nullptr : ctx->stream;
+    MHS_HIP(hipEventRecord(ctx->stream_ev, from));
+    MHS_HIP(hipStreamWaitEvent(to, ctx->stream_ev, 0));
+    return MHS_OK;
+}
+
 int mhs_ctx_trim(mhs_ctx* ctx) {
     if (!ctx) return MHS_ERR_INVALID;
     (void)hipSetDevice(ctx->device);
@@ -1405,6 +1417,7 @@ int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const m
         p->trans = ValTrans{};
     }
     p->plan = plan_values(p->counts);
+    p->gplan = plan_grad(p->counts);
     *out = p;
     return MHS_OK;
 }
@@ -1439,6 +1452,40 @@ int mhs_spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, cons
     for (int i = 0; i < p->plan.n; ++i) {
         const ValLaunch& l = p->plan.launch[i];
         issue_values(l, a, p->trans, p->lists + p->list_off[l.cls], s);
+    }
+    MHS_HIP(hipGetLastError());
+    if (ms) {
+        float f = 0;
+        MHS_HIP(hipEventRecord(p->ev[1], s));
+        MHS_HIP(hipEventSynchronize(p->ev[1]));
+        MHS_HIP(hipEventElapsedTime(&f, p->ev[0], p->ev[1]));
+        *ms = f;
+    } else if (ctx->sync) {
+        MHS_HIP(hipStreamSynchronize(s));
+    }
+    return MHS_OK;
+}
+
+int mhs_spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* dCval,
+                           double* dAval, double* dBval, double* ms) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: null plan");
+    if (!dCval) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: null dCval");
+    if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: no output (dAval and dBval are both null)");
+    if ((dAval && !Bval) || (dBval && !Aval))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: dAval needs Bval, dBval needs Aval");
+    if (p->device != ctx->device)
+        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: the plan belongs to another device");
+    MHS_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const ValGradArgs a{p->pat.Aptr, p->pat.Acol, Aval, p->pat.Bptr, p->pat.Bcol, Bval, p->pat.Cptr, p->pat.Ccol, dCval, dAval, dBval};
+    if (ms) MHS_HIP(hipEventRecord(p->ev[0], s));
+    // dB is summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
+    if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(double) * (size_t)p->nnzA, s));
+    if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(double) * (size_t)p->nnzB, s));
+    for (int i = 0; i < p->gplan.n; ++i) {
+        const ValLaunch& l = p->gplan.launch[i];
+        issue_values_grad(l, a, p->lists + p->list_off[l.cls], s);
     }
     MHS_HIP(hipGetLastError());
     if (ms) {

@@ -193,6 +193,21 @@ void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int* cnt,
 void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s);
 // One launch of a values plan (plan_values) over its class's row list, on `s` (t: read by VK_DOT only).
 void issue_values(const ValLaunch& l, const ValArgs& a, const ValTrans& t, const int* list, hipStream_t s);
+// mhs_values_grad.hip: the backward of a values call (mhs_spgemm_values_grad).  G: the cotangent on C's pattern;
+// dA / dB: the gradients, zero-filled by the caller, either nullptr (that side is not computed, and Bval / Aval
+// is then not read).
+struct ValGradArgs {
+    const int *Aptr, *Acol;
+    const double* Aval;
+    const int *Bptr, *Bcol;
+    const double* Bval;
+    const int *Cptr, *Ccol;
+    const double* G;
+    double *dA, *dB;
+};
+hipError_t init_values_grad_attributes();  // (called by init_values_attributes)
+// One launch of a values plan's backward (plan_grad) over its class's row list, on `s`.
+void issue_values_grad(const ValLaunch& l, const ValGradArgs& a, const int* list, hipStream_t s);
 // device address of the probe-conflict counter (nullptr unless built with MHS_PROBE_STATS=1)
 hipError_t probe_counter(unsigned long long** dev);
 // mhs_hbm.hip: the streaming kernels of mhs_hbm_peak on the current device (gbps[3]: copy, read, write)

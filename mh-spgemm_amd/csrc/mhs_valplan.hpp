@@ -31,7 +31,8 @@
 //
 // plan_values(counts) is the whole launch plan of a hot call; issue_values (mhs_values.hip) turns one
 // ValLaunch and the call's arrays into a kernel launch.  No pointer and no HIP type in here:
-// tests/valplan_check.cpp runs it on the host.
+// tests/valplan_check.cpp runs it on the host.  plan_grad(counts) is the launch plan of the backward
+// (mhs_spgemm_values_grad; issue_values_grad, mhs_values_grad.hip): tests/gradplan_check.cpp.
 #pragma once
 #include "mhs_shape.hpp"
 
@@ -212,6 +213,16 @@ inline ValPlan plan_values(const ValCounts& c) {
         add(VK_TEAM, VC_TEAM, ((long long)c.rows[VC_TEAM] + VAL_TEAM_ROWS - 1) / VAL_TEAM_ROWS, VAL_TEAM_GRID, 256,
             VAL_TEAM_ROWS * region, region);
     }
+    return p;
+}
+
+// The launches of a backward call (mhs_spgemm_values_grad): the forward's, each run by its class's backward
+// kernel (mhs_values_grad.hip), but for the dot rows of a masked plan -- there is no dot-form backward: their
+// list goes to the global-form kernel, a wave per row (block 256; the global class runs it 1024 threads a row).
+inline ValPlan plan_grad(const ValCounts& c) {
+    ValPlan p = plan_values(c);
+    for (int i = 0; i < p.n; ++i)
+        if (p.launch[i].kernel == VK_DOT) p.launch[i].kernel = VK_GLOBAL;  // (cls stays VC_DOT: the list it walks)
     return p;
 }
 

@@ -10,31 +10,12 @@
 // Masked plans (mhs_values_plan_create_masked: C's pattern is a mask, products outside it are dropped)
 // classify by val_class_masked, count the kept products in place of the verify walk, and may send rows
 // to the dot class: k_val_dot, the inner-product form over B^T's pattern (no sums shared, no atomics).
-#include "mhs_internal.hpp"
+#include "mhs_valwalk.hpp"
 
 #include <climits>
 
 namespace mhs {
 namespace {
-
-// Ordering point for LDS traffic between lanes of one wave (a wave's LDS operations are
-// performed in issue order; only the compiler must not move accesses across it).
-__device__ __forceinline__ void vwave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Position of column c in the ascending cols[0, n), or -1.
-__device__ __forceinline__ int find_slot(const int* cols, int n, int c) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cols[mid] < c) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && cols[lo] == c ? lo : -1;
-}
 
 // The products of row `row`: group g of ng groups takes A entries g, g + ng, ...; its G lanes
 // stride over the B row.  add(column, value) per product.
@@ -54,12 +35,6 @@ __device__ __forceinline__ void walk_products(const ValArgs& a, int row, int g, 
 // lanes takes staged entries g, g + ng, ... and reads its B row VAL_PIECES G-wide pieces at a time,
 // every load issued before the first sum.  pre() runs once, between the first stage's loads and the
 // sync that publishes them (the row's zero fill rides on that sync).
-template <int CH>
-struct ValStage {
-    int bs[CH], len[CH];
-    double av[CH];
-};
-constexpr int VAL_PIECES = 8;
 template <int G, int CH, class Sync, class Pre, class F>
 __device__ __forceinline__ void walk_staged(const ValArgs& a, int row, int t, int lanes, ValStage<CH>& d, Sync sync, Pre pre,
                                             F add) {
@@ -454,6 +429,7 @@ hipError_t init_values_attributes() {
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)k_val_block<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 VAL_BLOCK_BYTES);
+    if (e == hipSuccess) e = init_values_grad_attributes();  // their backward (mhs_values_grad.hip)
     return e;
 }
 

@@ -1,7 +1,7 @@
 // spgemm_main.cpp -- the `spgemm <file.mtx>` driver (reference src/main.cu:74-217)
 // on top of the C-ABI, printing the reference's stdout lines.
 //
-//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] <file.mtx>
+//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -23,6 +23,10 @@
 //             the same A and B on A's own pattern -- A*A kept where A has entries; needs rowA = colA -- and
 //             N calls; their mean time, the kept products and the dot rows on a line of its own, and with
 //             --check the values against the product's own C filtered to A's pattern (the 1e-9 rule)
+//   --grad N  after the product (and --reuse, --masked), a values plan on C's pattern and, with a seeded
+//             cotangent G on it, N values calls and N backward calls (mhs_spgemm_values_grad, both
+//             gradients); the two median times on a line of its own, and with --check the adjoint
+//             identities <G, C> = <dA, Aval> = <dB, Bval> (the product is bilinear) on host-computed sums
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -108,8 +112,63 @@ static void run_masked(Tool& tools, const CSR& A, const CSR& B, CSR& C, int call
     mask.d_val = nullptr;
 }
 
+static double median(std::vector<double> v) {
+    std::sort(v.begin(), v.end());
+    return v.empty() ? 0.0 : 0.5 * (v[(v.size() - 1) / 2] + v[v.size() / 2]);
+}
+
+// --grad N: the backward of the values call on C's own pattern, N calls beside N values calls; with check the
+// adjoint identities.  Both sides of an identity are the same terms a * b * g summed in another order, so they
+// agree to rounding: the bound is 1e-9 of the sums of the absolute per-entry terms.
+static void run_grad(Tool& tools, const CSR& A, const CSR& B, CSR& C, int calls, bool check) {
+    double *dG = nullptr, *dA = nullptr, *dB = nullptr;
+    const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)C.nnz;
+    try {
+        std::vector<double> G(nC ? nC : 1);
+        unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
+        for (size_t s = 0; s < nC; ++s) {
+            state = state * 6364136223846793005ULL + 1442695040888963407ULL;
+            G[s] = 0.1 + 0.9 * (double)(state >> 11) / 9007199254740992.0;
+        }
+        mhs_shim::hip_check(hipMalloc((void**)&dG, sizeof(double) * (nC ? nC : 1)), "hipMalloc G");
+        mhs_shim::hip_check(hipMalloc((void**)&dA, sizeof(double) * (nA ? nA : 1)), "hipMalloc dA");
+        mhs_shim::hip_check(hipMalloc((void**)&dB, sizeof(double) * (nB ? nB : 1)), "hipMalloc dB");
+        mhs_shim::hip_check(hipMemcpy(dG, G.data(), sizeof(double) * nC, hipMemcpyHostToDevice), "H2D G");
+        mhs_shim::ValuesPlan plan(tools, A, B, C);
+        std::vector<double> fwd, bwd;
+        for (int i = 0; i < calls; ++i) {
+            MH_spgemm_values(A, B, C, plan);
+            fwd.push_back(plan.last_ms);
+        }
+        for (int i = 0; i < calls; ++i) {
+            MH_spgemm_values_grad(A, B, dG, dA, dB, plan);
+            bwd.push_back(plan.last_ms);
+        }
+        std::printf("MH-SpGEMM values backward (both gradients) median of %d calls is %.3lf ms, the values call's %.3lf ms\n", calls,
+                    median(bwd), median(fwd));
+        if (check) {
+            C.D2H();
+            std::vector<double> gA(nA ? nA : 1), gB(nB ? nB : 1);
+            mhs_shim::hip_check(hipMemcpy(gA.data(), dA, sizeof(double) * nA, hipMemcpyDeviceToHost), "D2H dA");
+            mhs_shim::hip_check(hipMemcpy(gB.data(), dB, sizeof(double) * nB, hipMemcpyDeviceToHost), "D2H dB");
+            long double gc = 0, ga = 0, gb = 0, ac = 0, aa = 0, ab = 0;
+            for (size_t s = 0; s < nC; ++s) gc += (long double)G[s] * C.val[s], ac += std::fabs(G[s] * C.val[s]);
+            for (size_t p = 0; p < nA; ++p) ga += (long double)gA[p] * A.val[p], aa += std::fabs(gA[p] * A.val[p]);
+            for (size_t q = 0; q < nB; ++q) gb += (long double)gB[q] * B.val[q], ab += std::fabs(gB[q] * B.val[q]);
+            const bool ok = std::fabs((double)(gc - ga)) <= 1e-9 * (double)(ac + aa) && std::fabs((double)(gc - gb)) <= 1e-9 * (double)(ac + ab);
+            std::printf("<G,C> = %.12e, <dA,A> = %.12e, <dB,B> = %.12e\n", (double)gc, (double)ga, (double)gb);
+            std::puts(ok ? "grad pass" : "grad error");
+        }
+    } catch (const std::exception&) {
+        std::puts("grad error");
+    }
+    (void)hipFree(dG);
+    (void)hipFree(dA);
+    (void)hipFree(dB);
+}
+
 int main(int argc, char** argv) {
-    int iters = 1, warmup = 1, reuse = 0, masked = 0;
+    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0;
     bool aat = false, vendor = false, check = false, cache = false;
     std::string csv;
     const char* filename = nullptr;
@@ -124,12 +183,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--cache")) cache = true;
         else if (!std::strcmp(argv[i], "--reuse") && i + 1 < argc) reuse = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--grad") && i + 1 < argc) grad = std::atoi(argv[++i]);
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
-    if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0) {
+    if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0 || grad < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -240,6 +300,7 @@ int main(int argc, char** argv) {
         }
         if (masked > 0 && A.M != A.N) std::puts("masked: A's pattern as the mask must have rowA = colA. Skipped.");
         else if (masked > 0) run_masked(tools, A, B, C, masked, check);
+        if (grad > 0) run_grad(tools, A, B, C, grad, check);
         C.d_release_csr();
     } catch (const std::exception&) {
         std::printf("MH-SpGEMM failed!!!\n");

@@ -158,6 +158,13 @@ def lib() -> ctypes.CDLL:
             L.mhs_values_plan_create_masked.restype = c_int
             L.mhs_values_plan_kept.argtypes = [c_void_p, P(ctypes.c_int64)]
             L.mhs_values_plan_kept.restype = c_int
+        if hasattr(L, "mhs_spgemm_values_grad"):  # (the backward of a values call: a later addition to ABI 10)
+            L.mhs_spgemm_values_grad.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 P(ctypes.c_double)]
+            L.mhs_spgemm_values_grad.restype = c_int
+    if hasattr(L, "mhs_ctx_fence_default_stream"):  # (a later addition to ABI 10)
+        L.mhs_ctx_fence_default_stream.argtypes = [c_void_p, c_int]
+        L.mhs_ctx_fence_default_stream.restype = c_int
     _lib = L
     return L
 

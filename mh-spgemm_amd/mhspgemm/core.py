@@ -58,6 +58,13 @@ class Tool:
     def set_stream(self, hip_stream: int | None):
         _check(self.ctx, L.lib().mhs_ctx_set_stream(self.ctx, hip_stream or None), "mhs_ctx_set_stream")
 
+    def fence_default_stream(self, after: bool):
+        """mhs_ctx_fence_default_stream: order the context stream against the device's default (null) stream,
+        whose handle 0 ``set_stream`` cannot take (0 selects the context's own, non-blocking stream).
+        ``after=False``, before a call: the context stream waits for what is queued on the null stream;
+        ``after=True``, after it: the null stream waits for what is queued on the context stream."""
+        _check(self.ctx, L.lib().mhs_ctx_fence_default_stream(self.ctx, 1 if after else 0), "mhs_ctx_fence_default_stream")
+
     def set_option(self, option: int, value: int):
         """mhs_ctx_set_option: MHS_OPT_SYNC (0: return once the numeric phase is
         queued) or MHS_OPT_NUMERIC_EVENTS (ring size of numeric-phase events)."""
@@ -378,7 +385,10 @@ class ValuesPlan:
     the product's -- products outside it are dropped, mask entries no product reaches get 0.0.
     ``form`` then says how rows are computed: ``"product"`` (walk the products, drop the misses),
     ``"dot"`` (per mask entry, A's row against B's column, through B^T's pattern kept in the plan)
-    or ``"auto"`` (per row, the cheaper).  An integer ``form`` is passed to the library as it is."""
+    or ``"auto"`` (per row, the cheaper).  An integer ``form`` is passed to the library as it is.
+
+    ``grad`` is the backward of ``run`` on the same plan (mhs_spgemm_values_grad) and ``apply`` the pair as a
+    ``torch.autograd.Function``, for products inside a differentiable program."""
 
     def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto"):
         if not hasattr(L.lib(), "mhs_values_plan_create"):
@@ -399,6 +409,7 @@ class ValuesPlan:
         self._c = c
         self.nnzA, self.nnzB, self.nnzC = int(a.nnz), int(b.nnz), int(c.nnz)
         self.plan = ctypes.c_void_p()
+        self._pad = None
         if masked:
             rc = L.lib().mhs_values_plan_create_masked(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
                                                        self.form, ctypes.byref(self.plan))
@@ -433,6 +444,65 @@ class ValuesPlan:
         _check(self.tool.ctx, rc, "mhs_spgemm_values")
         return float(ms.value) if timed else None
 
+    def grad(self, dC, Aval=None, Bval=None, need_A: bool = True, need_B: bool = True, out_A=None, out_B=None,
+             timed: bool = False):
+        """The backward of ``run`` (mhs_spgemm_values_grad): for the cotangent ``dC`` on C's pattern (nnz(C)
+        entries) the gradients of ``Aval`` and ``Bval`` (default: the operands' own ``d_val``), into ``out_A`` /
+        ``out_B`` (nnz(A) / nnz(B) entries; allocated with torch when not given).  Tensors as in ``run``.
+        Returns ``(dA, dB)`` with None for a side not asked for -- that side's buffer is not touched and the
+        other operand's values are not read -- and ``(dA, dB, ms)`` when ``timed``.  When one tensor is both
+        ``Aval`` and ``Bval`` (A*A) the two gradients still come back apart: the caller (autograd) adds them."""
+        if not self.plan:
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "ValuesPlan.grad: the plan is closed")
+        if not hasattr(L.lib(), "mhs_spgemm_values_grad"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no mhs_spgemm_values_grad")
+        if not (need_A or need_B):
+            raise ValueError("ValuesPlan.grad: need_A or need_B")
+        torch = _torch()
+        dev = f"cuda:{self.tool.device}"
+        gp = self._ptr(dC, self.nnzC, "dC")
+        # (an empty array has no address; the library wants one for every array it is given: nothing reads it)
+        if self._pad is None:
+            self._pad = torch.zeros(1, dtype=torch.float64, device=dev)
+        pad = self._pad.data_ptr()
+        av = bv = pa = pb = None
+        dA = dB = None
+        if need_A:
+            bv = (self.B.c_view().val if Bval is None else self._ptr(Bval, self.nnzB, "Bval")) or pad
+            dA = torch.empty(self.nnzA, dtype=torch.float64, device=dev) if out_A is None else out_A
+            pa = self._ptr(dA, self.nnzA, "out_A") or pad
+        if need_B:
+            av = (self.A.c_view().val if Aval is None else self._ptr(Aval, self.nnzA, "Aval")) or pad
+            dB = torch.empty(self.nnzB, dtype=torch.float64, device=dev) if out_B is None else out_B
+            pb = self._ptr(dB, self.nnzB, "out_B") or pad
+        ms = ctypes.c_double(0.0)
+        rc = L.lib().mhs_spgemm_values_grad(self.tool.ctx, self.plan, av, bv, gp or pad, pa, pb,
+                                            ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, "mhs_spgemm_values_grad")
+        return (dA, dB, float(ms.value)) if timed else (dA, dB)
+
+    def apply(self, Aval, Bval):
+        """C's values of A*B as a differentiable function of ``Aval`` and ``Bval`` (a ``torch.autograd.Function``):
+        the forward is ``run`` into a fresh nnz(C) tensor, the backward ``grad`` for the inputs that need it
+        (once differentiable).  Both are ordered on torch's current stream, also with MHS_OPT_SYNC 0: a stream
+        of torch's making is handed to the tool; torch's default stream (the null stream, handle 0) cannot be,
+        so there the calls run on the tool's own stream between two fences (``Tool.fence_default_stream``)."""
+        return _values_function().apply(self, Aval, Bval)
+
+    def _ordered_on_current_stream(self, call):
+        """Run ``call()`` with its library work ordered after what torch's current stream holds, and before
+        what it is given next."""
+        torch = _torch()
+        handle = torch.cuda.current_stream(self.tool.device).cuda_stream
+        self.tool.set_stream(handle)
+        if handle:
+            return call()
+        self.tool.fence_default_stream(after=False)
+        try:
+            return call()
+        finally:
+            self.tool.fence_default_stream(after=True)
+
     def info(self) -> dict:
         """Rows per class (by name and as the ``rows`` list indexed by class id), products, nnzC, plan_bytes,
         and kept_products: the products that land in C's pattern (all of them unless the plan is masked)."""
@@ -459,6 +529,41 @@ class ValuesPlan:
             self.close()
         except Exception:
             pass
+
+
+_VALUES_FUNCTION = None
+
+
+def _values_function():
+    """The autograd function behind ``ValuesPlan.apply`` (made on first use: torch is imported lazily)."""
+    global _VALUES_FUNCTION
+    if _VALUES_FUNCTION is not None:
+        return _VALUES_FUNCTION
+    torch = _torch()
+    from torch.autograd.function import once_differentiable
+
+    class ValuesProduct(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, Aval, Bval):
+            out = torch.empty(plan.nnzC, dtype=torch.float64, device=f"cuda:{plan.tool.device}")
+            plan._ordered_on_current_stream(lambda: plan.run(Aval, Bval, out=out))
+            ctx.plan = plan
+            ctx.save_for_backward(Aval, Bval)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dC):
+            Aval, Bval = ctx.saved_tensors
+            _, need_A, need_B = ctx.needs_input_grad
+            if not (need_A or need_B):
+                return None, None, None
+            plan, dC = ctx.plan, dC.contiguous()
+            dA, dB = plan._ordered_on_current_stream(lambda: plan.grad(dC, Aval, Bval, need_A=need_A, need_B=need_B))
+            return None, dA, dB
+
+    _VALUES_FUNCTION = ValuesProduct
+    return ValuesProduct
 
 
 def transpose(tool: Tool, A: CSR) -> CSR:

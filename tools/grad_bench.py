@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""grad_bench.py -- the values backward against the values call on the same plan, one workload per run.
+
+    python tools/grad_bench.py [--workload cant|scircuit|triangle] [--blocks 5] [--window 0.4]
+
+Workloads: `cant` and `scircuit` are A*A on the product's own pattern (the stand-ins of
+mhspgemm.synth unless the real matrices are present); `triangle` is L*L on L's pattern, a masked plan
+in AUTO, L the strictly lower triangle of a symmetrised synth.powerlaw graph (tools/masked_bench.py's).
+
+Kinds, timed in alternating blocks after warm-up (the method of tools/values_bench.py: a block is
+enough calls for its window to last `--window` seconds between two host clock reads after device
+synchronises; per kind the median of the blocks' per-call times and the spread max - min):
+  forward   mhs_spgemm_values
+  grad_A    mhs_spgemm_values_grad, dAval only (no atomics)
+  grad_B    ... dBval only (one FP64 atomic per kept product)
+  grad_AB   ... both
+Before timing, every output is checked against the forward through the adjoint identity: with X, Y
+fresh positive values, <G, run(X, Bval)> = <grad_A, X> and <G, run(Aval, Y)> = <grad_B, Y> to 1e-9
+relative (the same terms summed in another order), for the one-sided calls and for the call with both.
+Also reported: the dB side's atomic bytes per second, 8 * kept_products / the grad_B time, and
+`masked_alternative_products`: what the two gradients would walk as masked products of their own,
+dA = (G*B^T)<A>: the sum over C's entries (i, j) of len(B^T row j), and dB = (A^T*G)<B>: the sum over
+A's entries (i, k) of len(C row i) = sum_i nnzA(i) * nnzC(i)  ("not done").
+Prints one JSON line."""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (ROOT, ROOT / "mh-spgemm_amd", ROOT / "tools"):
+    if str(p) not in sys.path:
+        sys.path.insert(0, str(p))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import mhspgemm  # noqa: E402
+from mhspgemm import _lib as L  # noqa: E402
+from mhspgemm import synth  # noqa: E402
+from masked_bench import lower_triangle  # noqa: E402
+
+
+def lib_name() -> str:
+    """The library's path, relative to the repository when it is the one built in it."""
+    path = Path(L.lib_path()).resolve()
+    return str(path.relative_to(ROOT)) if ROOT in path.parents else str(path)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--workload", default="cant", choices=("cant", "scircuit", "triangle"))
+    ap.add_argument("--n", type=int, default=50_000, help="vertices of the triangle workload's graph")
+    ap.add_argument("--blocks", type=int, default=5, help="timed blocks per kind")
+    ap.add_argument("--window", type=float, default=0.4, help="seconds a timed block should last")
+    ap.add_argument("--warmup", type=int, default=5)
+    args = ap.parse_args()
+
+    dev = 0
+    torch.cuda.set_device(dev)
+    device = f"cuda:{dev}"
+    masked = args.workload == "triangle"
+    if masked:
+        A, source = lower_triangle(args.n), f"synth.powerlaw({args.n}), symmetrised, strictly lower, values 1.0"
+    else:
+        A, source = synth.load_or_synth(args.workload)
+    flop = mhspgemm.flop_count_np(A.col, A.ptr)
+    A.H2D(dev)
+    tool = mhspgemm.Tool(dev)
+    tool.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+
+    def sync():
+        torch.cuda.synchronize(dev)
+
+    out = {"workload": args.workload, "source": source, "M": A.M, "nnzA": A.nnz, "products": int(flop),
+           "blocks": args.blocks, "lib": lib_name()}
+    if masked:
+        C = mhspgemm.CSR(A.M, A.N, A.ptr, A.col, np.zeros(A.nnz))
+        C.H2D(dev)
+        plan = mhspgemm.ValuesPlan(tool, A, A, C, masked=True, form="auto")
+    else:
+        C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
+        plan = mhspgemm.ValuesPlan(tool, A, A, C)
+    info = plan.info()
+    out.update({"nnzC": info["nnzC"], "kept_products": info["kept_products"], "plan_bytes": info["plan_bytes"],
+                "classes": {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}})
+    Cp, Ci = (A.ptr, A.col) if masked else C.to_host()[:2]
+    out["masked_alternative_products"] = {
+        "dA": int(np.bincount(A.col, minlength=A.N).astype(np.int64)[Ci].sum()),
+        "dB": int((np.diff(A.ptr).astype(np.int64) * np.diff(Cp).astype(np.int64)).sum())}
+    del Cp, Ci
+    print(f"{args.workload}: nnz(A) {A.nnz}, {flop} products, {info['kept_products']} kept, nnz(C) {info['nnzC']}",
+          file=sys.stderr, flush=True)
+
+    gen = torch.Generator(device=device).manual_seed(17)
+    rnd = lambda n: torch.rand(n, dtype=torch.float64, device=device, generator=gen) * 0.9 + 0.1  # noqa: E731
+    av, bv, X, Y, G = rnd(A.nnz), rnd(A.nnz), rnd(A.nnz), rnd(A.nnz), rnd(info["nnzC"])
+    res_c = torch.empty(info["nnzC"], dtype=torch.float64, device=device)
+    gA, gB = (torch.full((A.nnz,), float("nan"), dtype=torch.float64, device=device) for _ in range(2))
+    sync()  # (torch's default stream has the handle 0: the tool runs on its own stream, ordered by device synchronises)
+
+    # ---- the check: the adjoint identity against the forward, for every kind of call
+    plan.run(X, bv, out=res_c)
+    lhs_a = float((G * res_c).sum())
+    plan.run(av, Y, out=res_c)
+    lhs_b = float((G * res_c).sum())
+    worst = 0.0
+    for need_a, need_b in ((True, False), (False, True), (True, True)):
+        gA.fill_(float("nan"))
+        gB.fill_(float("nan"))
+        sync()
+        plan.grad(G, av, bv, need_A=need_a, need_B=need_b, out_A=gA, out_B=gB)
+        sync()
+        for need, g, other, lhs in ((need_a, gA, X, lhs_a), (need_b, gB, Y, lhs_b)):
+            if not need:
+                continue
+            assert not torch.isnan(g).any().item(), "an entry of a requested output was not written"
+            rel = abs(float((g * other).sum()) - lhs) / lhs
+            assert rel <= 1e-9, f"adjoint identity off by {rel:.3e} (need_A={need_a}, need_B={need_b})"
+            worst = max(worst, rel)
+    out["checked"] = f"adjoint identity against the forward, one-sided and two-sided calls: worst relative gap {worst:.2e}"
+
+    # ---- timing
+    tool.set_option(L.MHS_OPT_SYNC, 0)
+
+    def forward_calls(n):
+        for _ in range(n):
+            plan.run(av, bv, out=res_c)
+
+    def grad_calls(need_a, need_b):
+        def fn(n):
+            for _ in range(n):
+                plan.grad(G, av, bv, need_A=need_a, need_B=need_b, out_A=gA, out_B=gB)
+        return fn
+
+    def timed(fn, n):
+        sync()
+        t0 = time.perf_counter()
+        fn(n)
+        sync()
+        return (time.perf_counter() - t0) / n * 1e3  # ms per call
+
+    kinds = [("forward", forward_calls), ("grad_A", grad_calls(True, False)), ("grad_B", grad_calls(False, True)),
+             ("grad_AB", grad_calls(True, True))]
+    calls = {}
+    for name, fn in kinds:
+        fn(args.warmup)
+        per = timed(fn, 10)
+        calls[name] = max(10, int(args.window * 1e3 / per) + 1)
+        print(f"{name}: {per:.4f} ms a call, {calls[name]} calls a block", file=sys.stderr, flush=True)
+    res = {name: [] for name, _ in kinds}
+    for _ in range(args.blocks):
+        for name, fn in kinds:
+            res[name].append(timed(fn, calls[name]))
+    tool.set_option(L.MHS_OPT_SYNC, 1)
+    for name, _ in kinds:
+        r = res[name]
+        out[name] = {"ms_median": round(statistics.median(r), 5), "ms_min": round(min(r), 5), "ms_max": round(max(r), 5),
+                     "spread_ms": round(max(r) - min(r), 5), "calls_per_block": calls[name],
+                     "blocks_ms": [round(x, 5) for x in r]}
+    fwd = out["forward"]["ms_median"]
+    out["over_forward"] = {k: round(out[k]["ms_median"] / fwd, 3) for k in ("grad_A", "grad_B", "grad_AB")}
+    out["grad_B_atomic_GBps"] = round(8.0 * info["kept_products"] / (out["grad_B"]["ms_median"] * 1e-3) / 1e9, 1)
+    plan.close()
+    if not masked:
+        C.release()
+    tool.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
