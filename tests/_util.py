@@ -280,3 +280,182 @@ def near_zoo(seed: int = 4):
     ptr[1:] = np.cumsum(lens)
     A = (B.M, B.M, ptr.astype(np.int32), np.concatenate(cols).astype(np.int32), np.concatenate(vals))
     return A, (B.M, B.N, B.ptr, B.col, B.val)
+
+
+# ------------------------------------------- the values backward's reference ---
+def keys(ptr, col, N):
+    rows = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
+    return rows * N + col
+
+
+def expand(Ap, Ac, Bp, Bc, Cp, Ci, N):
+    """Every product of A*B whose column is in its C row, as index arrays: A entry p, B entry q, C slot s."""
+    lens = (Bp[Ac.astype(np.int64) + 1] - Bp[Ac.astype(np.int64)]).astype(np.int64)
+    p = np.repeat(np.arange(len(Ac), dtype=np.int64), lens)
+    q = np.repeat(Bp[Ac.astype(np.int64)].astype(np.int64), lens) + (np.arange(lens.sum()) - np.repeat(np.cumsum(lens) - lens, lens))
+    i = np.repeat(np.arange(len(Ap) - 1, dtype=np.int64), np.diff(Ap))[p]
+    kC = keys(Cp, Ci, N)
+    if len(kC) == 0 or len(p) == 0:
+        e = np.zeros(0, np.int64)
+        return e, e, e
+    key = i * N + Bc[q]
+    s = np.minimum(np.searchsorted(kC, key), len(kC) - 1)
+    hit = kC[s] == key
+    return p[hit], q[hit], s[hit]
+
+
+def ref_grad(pqs, av, bv, G, nnzA, nnzB):
+    p, q, s = pqs
+    return np.bincount(p, bv[q] * G[s], nnzA), np.bincount(q, av[p] * G[s], nnzB)
+
+
+# ------------------------------------------------------------ the edge ladder ---
+# Rows that sit exactly on a bin or class edge of csrc/mhs_shape.hpp / mhs_valplan.hpp.  The edges themselves
+# come from tests/golden/shape_edges.json (printed by tests/shape_edges.cpp from the headers); the families
+# below build a matrix pair whose first EDGE_COPIES * R rows of A all have the prescribed parameters.  Every
+# value is an integer of +-{1, 2, 3}: products and partial sums stay integers below 9 * flop < 2^53, so the
+# product is exact in any summation order and the tests compare with np.array_equal.
+EDGE_COPIES = 8  # two blocks of four waves: every wave of a block holds an edge row at once
+
+
+def load_edges():
+    return json.loads((GOLDEN / "shape_edges.json").read_text())
+
+
+def edge_values(n, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.integers(1, 4, n) * rng.choice([-1, 1], n)).astype(np.float64)
+
+
+def _edge_pair(M, K, N, alen, acol, blen, bcol, seed):
+    Ap = np.zeros(M + 1, np.int64)
+    np.cumsum(alen, out=Ap[1:])
+    Bp = np.zeros(K + 1, np.int64)
+    np.cumsum(blen, out=Bp[1:])
+    assert Ap[-1] == len(acol) and Bp[-1] == len(bcol) and N < 2**31 and Ap[-1] < 2**31 and Bp[-1] < 2**31
+    acol, bcol = np.asarray(acol, np.int32), np.asarray(bcol, np.int32)
+    return ((M, K, Ap.astype(np.int32), acol, edge_values(len(acol), seed)),
+            (K, N, Bp.astype(np.int32), bcol, edge_values(len(bcol), seed + 1)))
+
+
+def _ragged(lens):
+    """Index within its row of every entry of rows of the given lengths."""
+    lens = np.asarray(lens, np.int64)
+    return np.arange(lens.sum()) - np.repeat(np.cumsum(lens) - lens, lens)
+
+
+def edge_band(s, n, stride=1, R=1, copies=EDGE_COPIES, seed=1):
+    """band(s, n): B row k holds c[k % s] columns at the start of tile stride * k, c spreading n over s tiles
+    (at most 64 a tile); A row j is the s consecutive B rows from j, R times in a row (R > 1: a row group).
+    Every row has tile span stride * (s - 1) + 1, t = s tiles, n C entries, n products, s tile products and
+    s A entries; c is periodic, so the copies differ in pattern only.  stride 1 is direct mode; a wider
+    stride is scatter(t, n, stride), hash mode."""
+    assert s <= n <= 64 * s
+    c = n // s + (np.arange(s) < n % s)
+    K = s + copies - 1
+    blen = c[np.arange(K) % s]
+    bcol = np.repeat(64 * stride * np.arange(K, dtype=np.int64), blen) + _ragged(blen)
+    first = np.repeat(np.arange(copies), R)
+    acol = (first[:, None] + np.arange(s)[None, :]).reshape(-1)
+    return _edge_pair(copies * R, K, 64 * stride * K, np.full(copies * R, s), acol, blen, bcol, seed)
+
+
+def edge_scatter(t, n, stride, copies=EDGE_COPIES, seed=1):
+    return edge_band(t, n, stride=stride, copies=copies, seed=seed)
+
+
+def edge_work(flop, copies=EDGE_COPIES, seed=1):
+    """work(flop): A row j repeats the full 64-column B row j flop // 64 times; B row copies + j adds the
+    remainder in the same tile.  n = 64 over one tile (528 bytes of tables) whatever the product count."""
+    q, r = divmod(flop, 64)
+    assert q >= 1
+    blen = np.concatenate([np.full(copies, 64), np.full(copies, r)])
+    bcol = np.repeat(64 * (np.arange(2 * copies, dtype=np.int64) % copies), blen) + _ragged(blen)
+    alen = np.full(copies, q + (r > 0))
+    acol = np.repeat(np.arange(copies), alen)
+    if r:
+        acol[np.cumsum(alen) - 1] = copies + np.arange(copies)
+    return _edge_pair(copies, 2 * copies, 64 * copies, alen, acol, blen, bcol, seed)
+
+
+def edge_symwork(tflop, copies=EDGE_COPIES, seed=1):
+    """One-entry B rows: A row j repeats B row j (one column, in tile j) tflop times -- tile work without a table."""
+    acol = np.repeat(np.arange(copies), tflop)
+    return _edge_pair(copies, copies, 64 * copies, np.full(copies, tflop), acol, np.ones(copies, np.int64),
+                      64 * np.arange(copies, dtype=np.int64), seed)
+
+
+def edge_val(n, span, products, copies=EDGE_COPIES, seed=1):
+    """A C row of n entries over a column span of `span` with `products` products: B row 3j holds the row's
+    first n - 1 columns, row 3j + 2 its last one, row 3j + 1 the first (products - 1) % (n - 1) columns again;
+    A row j repeats row 3j (products - 1) // (n - 1) times, then the other two.  Copy j starts at column 100 j."""
+    assert 2 <= n <= span and products >= n
+    m, r = divmod(products - 1, n - 1)
+    blen = np.tile([n - 1, r, 1], copies)
+    base = np.repeat(100 * np.arange(copies, dtype=np.int64), 3)
+    bcol = np.repeat(base, blen) + _ragged(blen)
+    bcol[np.cumsum(blen)[2::3] - 1] += span - 1
+    one = np.concatenate([np.zeros(m, np.int64), np.ones(1 if r else 0, np.int64), np.full(1, 2)])
+    acol = (3 * np.arange(copies)[:, None] + one[None, :]).reshape(-1)
+    return _edge_pair(copies, 3 * copies, 100 * copies + span, np.full(copies, len(one)), acol, blen, bcol, seed)
+
+
+def edge_rows(M, s=201, seed=1):
+    """M rows for the row-count edges: A bidiagonal (row i: B rows i, i + 1) with a few band rows of s B rows
+    mixed in (first rows, the middle, the last row); B row k holds 1, 2, 3, 1, ... columns at the start of tile k."""
+    K = M + s
+    blen = 1 + np.arange(K) % 3
+    bcol = np.repeat(64 * np.arange(K, dtype=np.int64), blen) + _ragged(blen)
+    alen = np.full(M, 2)
+    alen[[0, min(5, M - 1), M // 2, M - 1]] = s
+    acol = np.repeat(np.arange(M, dtype=np.int64), alen) + _ragged(alen)
+    return _edge_pair(M, K, 64 * K, alen, acol, blen, bcol, seed)
+
+
+def edge_case(family, params, R=1):
+    """The matrix pair of one side of a rung of shape_edges.json."""
+    if family == "band":
+        return edge_band(params["s"], params["n"], R=R)
+    if family == "scatter":
+        return edge_scatter(params["t"], params["n"], params["stride"])
+    if family == "work":
+        return edge_work(params["flop"])
+    if family == "symwork":
+        return edge_symwork(params["tflop"])
+    if family == "val":
+        return edge_val(params["n"], params["span"], params["products"])
+    raise ValueError(family)
+
+
+def _per_row(ptr, per_entry):
+    """Sum of an integer per-entry quantity over each CSR row (exact: cumulative sums in int64)."""
+    cs = np.zeros(len(per_entry) + 1, np.int64)
+    np.cumsum(per_entry, out=cs[1:])
+    return cs[ptr[1:]] - cs[ptr[:-1]]
+
+
+def _new_tile(ptr, col):
+    """1 where an entry opens a new 64-column tile of its row."""
+    tile = col.astype(np.int64) >> 6
+    new = np.ones(len(col), np.int64)
+    new[1:] = tile[1:] != tile[:-1]
+    new[ptr[:-1][np.diff(ptr) > 0]] = 1
+    return new
+
+
+def row_shapes(A, B, Cp, Ci):
+    """What the bin ladders see of every row of C = A*B, recomputed from the matrices and the oracle's pattern:
+    a dict of int64 arrays span (tiles from the first to the last), t (distinct tiles), n (C entries), flop
+    (products), tflop (B tiles walked), nA (A entries), and colspan (last column - first + 1)."""
+    _, _, Ap, Ac, _ = A
+    _, _, Bp, Bc, _ = B
+    Ap, Bp, Cp = Ap.astype(np.int64), Bp.astype(np.int64), np.asarray(Cp, np.int64)
+    btiles = _per_row(Bp, _new_tile(Bp, Bc))
+    n = np.diff(Cp)
+    has = n > 0
+    first, last = Cp[:-1][has], Cp[1:][has] - 1
+    span, colspan = np.zeros(len(n), np.int64), np.zeros(len(n), np.int64)
+    span[has] = (Ci[last].astype(np.int64) >> 6) - (Ci[first].astype(np.int64) >> 6) + 1
+    colspan[has] = Ci[last].astype(np.int64) - Ci[first] + 1
+    return {"span": span, "t": _per_row(Cp, _new_tile(Cp, Ci)), "n": n, "flop": _per_row(Ap, np.diff(Bp)[Ac]),
+            "tflop": _per_row(Ap, btiles[Ac]), "nA": np.diff(Ap), "colspan": colspan}

@@ -14,7 +14,7 @@ import torch
 import mhspgemm
 from mhspgemm import _lib, synth
 from oracle import oracle as orc
-from _util import GOLDEN, PRODUCT_CASES, bin_zoo, load_golden, random_csr, tiny_zoo
+from _util import GOLDEN, PRODUCT_CASES, bin_zoo, expand, load_golden, random_csr, ref_grad, tiny_zoo
 
 pytestmark = pytest.mark.gpu
 
@@ -40,33 +40,6 @@ def filled(tool, n, value=float("nan")):
     out = torch.full((n,), value, dtype=torch.float64, device=f"cuda:{tool.device}")
     torch.cuda.synchronize()
     return out
-
-
-def keys(ptr, col, N):
-    rows = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
-    return rows * N + col
-
-
-# ------------------------------------------------------------------ reference ---
-def expand(Ap, Ac, Bp, Bc, Cp, Ci, N):
-    """Every product of A*B whose column is in its C row, as index arrays: A entry p, B entry q, C slot s."""
-    lens = (Bp[Ac.astype(np.int64) + 1] - Bp[Ac.astype(np.int64)]).astype(np.int64)
-    p = np.repeat(np.arange(len(Ac), dtype=np.int64), lens)
-    q = np.repeat(Bp[Ac.astype(np.int64)].astype(np.int64), lens) + (np.arange(lens.sum()) - np.repeat(np.cumsum(lens) - lens, lens))
-    i = np.repeat(np.arange(len(Ap) - 1, dtype=np.int64), np.diff(Ap))[p]
-    kC = keys(Cp, Ci, N)
-    if len(kC) == 0 or len(p) == 0:
-        e = np.zeros(0, np.int64)
-        return e, e, e
-    key = i * N + Bc[q]
-    s = np.minimum(np.searchsorted(kC, key), len(kC) - 1)
-    hit = kC[s] == key
-    return p[hit], q[hit], s[hit]
-
-
-def ref_grad(pqs, av, bv, G, nnzA, nnzB):
-    p, q, s = pqs
-    return np.bincount(p, bv[q] * G[s], nnzA), np.bincount(q, av[p] * G[s], nnzB)
 
 
 def assert_grad(got, want, absw, reached, what):
