@@ -18,9 +18,11 @@
 //   -> speculate_numeric (phase A of the previous call's plan) -> handoff
 //   -> finish_speculated (phase B, or the miss) -> numeric_after_handoff -> finish_call
 // and C's arrays belong to the Call's owner (mhs_owner.hpp) until finish_call commits.
-#include "mhs_internal.hpp"
+// Around the call, the context's own entry points: creation and options, streams, the output pool
+// (mhs_ctx_recycle, mhs_ctx_trim), mhs_transpose, the diagnostics.  The context itself (mhs_ctx) and the
+// entry points' error helpers are in mhs_ctx.hpp; the values plans and their calls in mhs_values_api.cpp.
+#include "mhs_ctx.hpp"
 #include "mhs_owner.hpp"
-#include "../../include/mhspgemm.h"
 
 #include <algorithm>
 #include <chrono>
@@ -33,132 +35,7 @@
 
 using namespace mhs;
 
-struct mhs_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-    std::string err;
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
-    char* gscratch = nullptr;
-    size_t gscratch_bytes = 0;
-    Stats* h_stats = nullptr;  // pinned
-    Published* pub = nullptr;  // fine-grained pinned: Stats handed over by the last pre-numeric kernel
-    Published* d_pub = nullptr;
-    int seq = 0;
-    hipEvent_t ev[8] = {};
-    bool sync = true;      // MHS_OPT_SYNC
-    bool groups = true;     // row groups (MHS_NO_GROUPS=1: every row alone)
-    bool near = true;       // near row groups (GRP_NEAR; MHS_NO_NEAR=1: off)
-    bool split = true;      // block bins split by LDS need (MHS_NO_SPLIT=1: off)
-    // MHS_OPT_NUMERIC_EVENTS: ring of (start, end) events around the numeric phase
-    std::vector<hipEvent_t> nev;
-    long long ncalls = 0;
-    int mc_list = 0;         // tile-list cap of the row cache (0: mc_list_for(M); MHS_MC_LIST)
-    bool stats_zero = false; // the workspace's device Stats are zero (left so by the last k_scan)
-    bool use_mcache = true;  // symbolic keeps narrow rows' tile masks for numeric (MHS_NO_MCACHE)
-    bool tiny_num = true;    // numeric tiny (sort) classes (MHS_NO_TINY_NUM=1: off)
-    // numeric-first tiny rows from this many rows of A on (MHS_OPT_TINY_FIRST_ROWS,
-    // MHS_NFT_MIN_M; < 0: never): one hand-off more per call, so big matrices only
-    long long nft_min_m = 1 << 19;
-    bool sym_fork = false;   // MHS_SYM_FORK=1: rare symbolic bins on an aux stream for every call
-    // ... and for every call of at least this many rows (MHS_SYM_FORK_MIN_M; < 0: never): the
-    // fork's cross-stream wait (~20 us) is noise there, the rare bins' milliseconds are not
-    long long sym_fork_min_m = 1 << 19;
-    bool nft_slots = true;   // MHS_NFT_NO_SLOTS=1 (tests): count the rows only, as when the slots do not fit
-    int nft_other_pct = 5;   // slots only when at most this share of the rows is past the tiny classes (MHS_NFT_OTHER_PCT)
-    // numeric-first tiny rows without the probe below nft_min_m rows, for matrices averaging fewer
-    // than this many entries a row (MHS_NFT_AUTO_AVG; 0: off): the slots are sized by their upper
-    // bound (TINY_SLOT_MAX a row), so no hand-off decides them
-    int nft_auto_avg = 12;
-    char* slots = nullptr;   // their value slots (cached across calls)
-    size_t slots_bytes = 0;
-    size_t mem_budget = 0;   // MHS_OPT_MEM_BUDGET (MiB): a call's workspace + C beyond it count as OOM (tests)
-    size_t c_held = 0;       // C bytes a row-chunked call holds while it lays out its second pass
-    long long front_passes = 0;  // front_pass calls (row-chunked passes; mhs_ctx_chunked_calls diagnostics)
-    long long chunked_calls = 0;  // calls that ran row-chunked (mhs_ctx_chunked_calls)
-    long long stat[9] = {};       // path counters (mhs_ctx_stat; [0] unused: chunked_calls)
-    int dense_span_max = 0;  // NM_DENSE for rows spanning <= this many 64-column tiles (MHS_DENSE_SPAN; off: occupancy)
-    // output pool (caching allocator for C arrays): (buffer, allocation size)
-    std::vector<std::pair<void*, size_t>> pool;
-    hipEvent_t stream_ev = nullptr;  // orders a new caller stream after the previous one
-    // numeric bins on several streams (MHS_NUM_STREAMS, default 4; 1 = one stream): aux
-    // streams fork from the call's stream after the Stats hand-off and join it before return
-    static constexpr int NAUX = 7;
-    int num_streams = 4;
-    hipStream_t aux[NAUX] = {};
-    hipEvent_t fork_ev = nullptr, join_ev[NAUX] = {};
-    hipEvent_t split_ev = nullptr;  // k_split_bins done (the split block launches wait for it)
-    // launch plan speculation (SpecArgs, mhs_shape.hpp): the last hand-off's Stats and the
-    // operands they belong to; MHS_NO_SPEC=1 turns it off
-    struct PlanKey {
-        const void* p[6];
-        long long M, N, MB, nnzA, nnzB, gen;
-        int near, nft, mc_list, pad;  // (no implicit padding: compared bytewise)
-        bool operator==(const PlanKey& o) const { return memcmp(this, &o, sizeof *this) == 0; }
-    };
-    bool spec = true;
-    bool plan_valid = false;
-    PlanKey plan_key{};
-    Stats plan_h{};
-    long long gen = 0;        // bumped by every mhs_ctx_set_option (options change the pipeline)
-    int* d_go = nullptr;      // k_scan's verdict on a speculated plan (device int)
-    bool spec_fork = false;  // MHS_SPEC_FORK=1: speculated plans also behind every forked symbolic pass (A/B)
-    // speculated calls run their plan's rare symbolic rows on an aux stream beside k_sym_common
-    // (scircuit-like -3.9 %, the other configs within 0.5 %: r06sf2); MHS_SPEC_FORK=0 turns it off
-    bool spec_fork_rare = true;
-    // a forked symbolic pass launches k_sym_common before the aux stream's rare rows (no host launch
-    // ahead of the call stream's: scircuit-like -0.6 %, webbase-like -0.3 %, cage15-like -0.1 %: r06fo);
-    // MHS_FORK_ORDER=0: the rare rows first
-    bool fork_common_first = true;
-    int spec_nss = mhs_ctx::NAUX + 1;  // streams of a speculated numeric phase (MHS_SPEC_NSS: a cap, A/B)
-    // the grouped numeric bin's cursor walk (plan_numeric): the device's compute units size its
-    // resident set (MHS_GROUP_WALK=0: cus stays 0, the static walk); MHS_OPT_GROUP_GRID caps its blocks
-    int cus = 0;
-    int group_cap = 0;
-};
-
-// A values plan (mhs_values_plan_create): the six borrowed pattern arrays, the class lists and the
-// launch plan.  Its device memory is its own (not the context workspace): mhs_spgemm calls and
-// mhs_ctx_trim on the same context leave it alone.
-struct mhs_values_plan {
-    int device = 0;
-    ValPattern pat{};
-    long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
-    long long kept = 0;    // products that land in C's pattern (masked plans count them; else = products)
-    char* mem = nullptr;   // lists (M ints), counters (VAL_CNT_INTS), status (VAL_STATUS_INTS)
-    size_t mem_bytes = 0;
-    // a masked plan with dot rows: B^T's pattern -- tptr (B.N + 1), trow, tperm (nnz(B) each) -- the plan's own too
-    char* tmem = nullptr;
-    size_t tmem_bytes = 0;
-    ValTrans trans{};
-    int* lists = nullptr;
-    int list_off[VAL_NCLASS] = {};
-    ValCounts counts{};
-    ValPlan plan{};
-    ValPlan gplan{};        // the backward's launches (plan_grad)
-    hipEvent_t ev[2] = {};  // timed calls
-};
-
 namespace {
-// first bad row of: A.ptr, B.ptr, C.ptr, A's columns, C's columns, the products, B's columns (masked plans)
-constexpr int VAL_STATUS_INTS = 8;
-static_assert((int)MHS_MASK_AUTO == (int)VM_AUTO && (int)MHS_MASK_PRODUCT == (int)VM_PRODUCT && (int)MHS_MASK_DOT == (int)VM_DOT,
-              "mhs_mask_form is ValMaskForm");
-}
-
-namespace {
-
-int fail(mhs_ctx* ctx, int code, const std::string& what) {
-    if (ctx) ctx->err = what;
-    return code;
-}
-
-int fail_hip(mhs_ctx* ctx, hipError_t e, const char* what) {
-    std::string m = std::string(what) + ": " + hipGetErrorString(e);
-    (void)hipGetLastError();
-    return fail(ctx, e == hipErrorOutOfMemory ? MHS_ERR_OOM : MHS_ERR_HIP, m);
-}
 
 // Spin until the device has published call `seq`'s Stats.  Every 256 polls the
 // stream is queried: a fault ends the wait with the HIP error, an idle stream
@@ -179,14 +56,6 @@ int wait_published(mhs_ctx* ctx, hipStream_t s, const Published* pub, int seq) {
 #endif
     }
 }
-
-#define MHS_HIP(expr)                                                   \
-    do {                                                                \
-        hipError_t e_ = (expr);                                         \
-        if (e_ != hipSuccess) return fail_hip(ctx, e_, #expr);          \
-    } while (0)
-
-inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
 double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1273,254 +1142,6 @@ int mhs_spgemm(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C, mhs
         const int rc = spgemm_attempt(ctx, A, B, C, t);
         if (rc != CALL_RERUN) return rc;
     }
-}
-
-namespace {
-
-// AUTO's ratio: VAL_DOT_RATIO, or MHS_VAL_DOT_RATIO (diagnostic: one build swept over the ratio)
-int val_dot_ratio() {
-    if (const char* v = std::getenv("MHS_VAL_DOT_RATIO")) {
-        const long r = std::strtol(v, nullptr, 10);
-        if (r >= 1 && r <= 1 << 20) return (int)r;
-    }
-    return VAL_DOT_RATIO;
-}
-
-// mhs_values_plan_create (masked false: C must contain the product's pattern) and
-// mhs_values_plan_create_masked (C is a mask; form: mhs_mask_form).
-int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form,
-                       mhs_values_plan** out) {
-    if (!ctx) return MHS_ERR_INVALID;
-    if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
-    *out = nullptr;
-    if (masked && (form < MHS_MASK_AUTO || form > MHS_MASK_DOT))
-        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: form is not an mhs_mask_form");
-    if (A->M < 0 || A->N < 0 || A->nnz < 0 || B->M < 0 || B->N < 0 || B->nnz < 0 || C->M < 0 || C->N < 0 || C->nnz < 0)
-        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: negative dimension");
-    if (A->N != B->M) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: A.N != B.M");
-    if (C->M != A->M) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: C.M != A.M");
-    if (C->N != B->N) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: C.N != B.N");
-    if ((A->M > 0 && (!A->ptr || !C->ptr)) || (B->M > 0 && !B->ptr) || (A->nnz > 0 && !A->col) || (B->nnz > 0 && !B->col) ||
-        (C->nnz > 0 && !C->col))
-        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null device array");
-    MHS_HIP(hipSetDevice(ctx->device));
-    mhs_values_plan* p = new mhs_values_plan();
-    p->device = ctx->device;
-    p->pat = ValPattern{A->M, A->ptr, A->col, B->ptr, B->col, C->ptr, C->col};
-    p->nnzA = A->nnz, p->nnzB = B->nnz, p->nnzC = C->nnz;
-    const int M = A->M;
-    hipStream_t s = ctx->stream;
-    const size_t lists_bytes = al((size_t)(M > 0 ? M : 1) * 4);
-    p->mem_bytes = lists_bytes + al((size_t)VAL_CNT_INTS * 4) + al((size_t)VAL_STATUS_INTS * 4);
-    int status[VAL_STATUS_INTS];
-    int h_cnt[VAL_CNT_INTS];
-    auto bail = [&](int rc) {
-        mhs_values_plan_destroy(ctx, p);
-        return rc;
-    };
-    auto bail_hip = [&](hipError_t e, const char* what) { return bail(fail_hip(ctx, e, what)); };
-    hipError_t e = hipMalloc((void**)&p->mem, p->mem_bytes);
-    if (e != hipSuccess) return bail_hip(e, "mhs_values_plan_create: plan memory");
-    for (hipEvent_t& ev : p->ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: events");
-    p->lists = (int*)p->mem;
-    int* d_cnt = (int*)(p->mem + lists_bytes);
-    int* d_status = d_cnt + al((size_t)VAL_CNT_INTS * 4) / 4;
-    // status words start at INT_MAX (0x7f7f7f7f is as good: any row index is below it)
-    if ((e = hipMemsetAsync(d_cnt, 0, (size_t)VAL_CNT_INTS * 4, s)) != hipSuccess) return bail_hip(e, "plan counters");
-    if ((e = hipMemsetAsync(d_status, 0x7f, (size_t)VAL_STATUS_INTS * 4, s)) != hipSuccess) return bail_hip(e, "plan status");
-    constexpr int NONE = 0x7f7f7f7f;
-    auto read_status = [&]() -> hipError_t {
-        hipError_t r = hipGetLastError();
-        if (r == hipSuccess) r = hipMemcpyAsync(status, d_status, sizeof status, hipMemcpyDeviceToHost, s);
-        if (r == hipSuccess) r = hipStreamSynchronize(s);
-        return r;
-    };
-    auto bad_row = [&](int k, const char* what) {
-        return bail(fail(ctx, MHS_ERR_INVALID, std::string("mhs_values_plan_create: ") + what + " (first at row " +
-                                                   std::to_string(status[k]) + ")"));
-    };
-    // 1. the three row_ptr arrays: everything after this indexes through them
-    launch_val_check_ptr(A->ptr, A->M, A->nnz, d_status + 0, s);
-    launch_val_check_ptr(B->ptr, B->M, B->nnz, d_status + 1, s);
-    launch_val_check_ptr(C->ptr, C->M, C->nnz, d_status + 2, s);
-    if ((e = read_status()) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: row_ptr check");
-    if (status[0] != NONE) return bad_row(0, "A.ptr is not a row_ptr of nnz(A) entries");
-    if (status[1] != NONE) return bad_row(1, "B.ptr is not a row_ptr of nnz(B) entries");
-    if (status[2] != NONE) return bad_row(2, "C.ptr is not monotone from 0 to C.nnz");
-    if ((A->M == 0 && A->nnz != 0) || (B->M == 0 && B->nnz != 0) || (C->M == 0 && C->nnz != 0))
-        return bail(fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: entries without rows"));
-    // 2. A's columns index B's rows; C's columns ascend strictly within [0, C.N)
-    launch_val_check_cols(A->ptr, A->col, A->M, B->M, false, d_status + 3, s);
-    launch_val_check_cols(C->ptr, C->col, C->M, C->N, true, d_status + 4, s);
-    if ((e = read_status()) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: column check");
-    if (status[3] != NONE) return bad_row(3, "a column of A is outside [0, B.M)");
-    if (status[4] != NONE) return bad_row(4, "C's columns are not strictly ascending within [0, C.N)");
-    void* sort_tmp = nullptr;  // (B^T's sort scratch: freed once the stream has been read back)
-    if (!masked) {
-        // 3. classes, lists, and every product's column looked up in its C row
-        launch_val_classify(p->pat, d_cnt, p->lists, s);
-        launch_val_verify(p->pat, d_status + 5, s);
-    } else {
-        // 3m. a mask: B^T's pattern for the dot class (its sort indexes by B's columns: checked first), classes
-        // by val_class_masked, and the products that land in the mask counted where the plain plan verifies
-        if (form != MHS_MASK_PRODUCT) {
-            launch_val_check_cols(B->ptr, B->col, B->M, B->N, false, d_status + 6, s);
-            if ((e = read_status()) != hipSuccess) return bail_hip(e, "mhs_values_plan_create: column check");
-            if (status[6] != NONE) return bad_row(6, "a column of B is outside [0, B.N)");
-            const Csr b{B->M, B->N, B->nnz, B->ptr, B->col, nullptr};
-            const size_t nb = (size_t)B->nnz;
-            const size_t ptr_bytes = al(((size_t)B->N + 1) * 4), ent_bytes = al((nb ? nb : 1) * 4);
-            size_t tmp_bytes = 0;
-            if ((e = transpose_pattern(b, nullptr, nullptr, nullptr, nullptr, &tmp_bytes, s)) != hipSuccess)
-                return bail_hip(e, "mhs_values_plan_create: B^T (scratch size)");
-            if ((e = hipMalloc((void**)&p->tmem, ptr_bytes + 2 * ent_bytes)) != hipSuccess)
-                return bail_hip(e, "mhs_values_plan_create: B^T memory");
-            p->tmem_bytes = ptr_bytes + 2 * ent_bytes;
-            int* tptr = (int*)p->tmem;
-            int* trow = (int*)(p->tmem + ptr_bytes);
-            int* tperm = (int*)(p->tmem + ptr_bytes + ent_bytes);
-            e = hipMalloc(&sort_tmp, tmp_bytes ? tmp_bytes : 16);
-            if (e == hipSuccess) e = transpose_pattern(b, tptr, trow, tperm, sort_tmp, &tmp_bytes, s);
-            if (e != hipSuccess) {
-                if (sort_tmp) {
-                    (void)hipStreamSynchronize(s);
-                    (void)hipFree(sort_tmp);
-                }
-                return bail_hip(e, "mhs_values_plan_create: B^T");
-            }
-            p->trans = ValTrans{tptr, trow, tperm};
-        }
-        launch_val_classify_masked(p->pat, ValMask{p->trans.tptr, form, val_dot_ratio()}, d_cnt, p->lists, s);
-        launch_val_count_kept(p->pat, d_cnt, s);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = read_status();
-    if (sort_tmp) (void)hipFree(sort_tmp);
-    if (e != hipSuccess) return bail_hip(e, "mhs_values_plan_create: classify");
-    if (!masked && status[5] != NONE) return bad_row(5, "C's pattern misses a column of the product A*B");
-    int off = 0;
-    for (int c = 0; c < VAL_NCLASS; ++c) {
-        p->counts.rows[c] = h_cnt[c * BINCNT_STRIDE];
-        p->counts.need[c] = h_cnt[(2 * VAL_NCLASS + c) * BINCNT_STRIDE];
-        p->list_off[c] = off;
-        off += p->counts.rows[c];
-    }
-    memcpy(&p->products, &h_cnt[3 * VAL_NCLASS * BINCNT_STRIDE], sizeof p->products);
-    p->kept = p->products;
-    if (masked) memcpy(&p->kept, &h_cnt[(3 * VAL_NCLASS + 1) * BINCNT_STRIDE], sizeof p->kept);
-    if (p->tmem && p->counts.rows[VC_DOT] == 0) {  // no row chose the dot class: B^T goes again
-        (void)hipFree(p->tmem);
-        p->tmem = nullptr;
-        p->tmem_bytes = 0;
-        p->trans = ValTrans{};
-    }
-    p->plan = plan_values(p->counts);
-    p->gplan = plan_grad(p->counts);
-    *out = p;
-    return MHS_OK;
-}
-
-}  // namespace
-
-int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, out);
-}
-
-int mhs_values_plan_create_masked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int form,
-                                  mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, true, form, out);
-}
-
-int mhs_values_plan_kept(const mhs_values_plan* p, int64_t* kept_products) {
-    if (!p || !kept_products) return MHS_ERR_INVALID;
-    *kept_products = p->kept;
-    return MHS_OK;
-}
-
-int mhs_spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, double* Cval, double* ms) {
-    if (!ctx) return MHS_ERR_INVALID;
-    if (!p) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: null plan");
-    if ((p->nnzA > 0 && !Aval) || (p->nnzB > 0 && !Bval) || (p->nnzC > 0 && !Cval))
-        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: null value array");
-    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: the plan belongs to another device");
-    MHS_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const ValArgs a{p->pat.Aptr, p->pat.Acol, Aval, p->pat.Bptr, p->pat.Bcol, Bval, p->pat.Cptr, p->pat.Ccol, Cval};
-    if (ms) MHS_HIP(hipEventRecord(p->ev[0], s));
-    for (int i = 0; i < p->plan.n; ++i) {
-        const ValLaunch& l = p->plan.launch[i];
-        issue_values(l, a, p->trans, p->lists + p->list_off[l.cls], s);
-    }
-    MHS_HIP(hipGetLastError());
-    if (ms) {
-        float f = 0;
-        MHS_HIP(hipEventRecord(p->ev[1], s));
-        MHS_HIP(hipEventSynchronize(p->ev[1]));
-        MHS_HIP(hipEventElapsedTime(&f, p->ev[0], p->ev[1]));
-        *ms = f;
-    } else if (ctx->sync) {
-        MHS_HIP(hipStreamSynchronize(s));
-    }
-    return MHS_OK;
-}
-
-int mhs_spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* dCval,
-                           double* dAval, double* dBval, double* ms) {
-    if (!ctx) return MHS_ERR_INVALID;
-    if (!p) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: null plan");
-    if (!dCval) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: null dCval");
-    if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: no output (dAval and dBval are both null)");
-    if ((dAval && !Bval) || (dBval && !Aval))
-        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: dAval needs Bval, dBval needs Aval");
-    if (p->device != ctx->device)
-        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: the plan belongs to another device");
-    MHS_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const ValGradArgs a{p->pat.Aptr, p->pat.Acol, Aval, p->pat.Bptr, p->pat.Bcol, Bval, p->pat.Cptr, p->pat.Ccol, dCval, dAval, dBval};
-    if (ms) MHS_HIP(hipEventRecord(p->ev[0], s));
-    // dB is summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
-    if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(double) * (size_t)p->nnzA, s));
-    if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(double) * (size_t)p->nnzB, s));
-    for (int i = 0; i < p->gplan.n; ++i) {
-        const ValLaunch& l = p->gplan.launch[i];
-        issue_values_grad(l, a, p->lists + p->list_off[l.cls], s);
-    }
-    MHS_HIP(hipGetLastError());
-    if (ms) {
-        float f = 0;
-        MHS_HIP(hipEventRecord(p->ev[1], s));
-        MHS_HIP(hipEventSynchronize(p->ev[1]));
-        MHS_HIP(hipEventElapsedTime(&f, p->ev[0], p->ev[1]));
-        *ms = f;
-    } else if (ctx->sync) {
-        MHS_HIP(hipStreamSynchronize(s));
-    }
-    return MHS_OK;
-}
-
-int mhs_values_plan_info(const mhs_values_plan* p, mhs_values_info* info) {
-    if (!p || !info) return MHS_ERR_INVALID;
-    memset(info, 0, sizeof *info);
-    for (int c = 0; c < VAL_NCLASS; ++c) info->rows[c] = p->counts.rows[c];
-    info->products = p->products;
-    info->nnzC = p->nnzC;
-    info->plan_bytes = (int64_t)(p->mem_bytes + p->tmem_bytes);
-    return MHS_OK;
-}
-
-void mhs_values_plan_destroy(mhs_ctx* ctx, mhs_values_plan* p) {
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);  // calls still queued read the lists
-    else (void)hipDeviceSynchronize();
-    for (hipEvent_t ev : p->ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (p->mem) (void)hipFree(p->mem);
-    if (p->tmem) (void)hipFree(p->tmem);
-    (void)hipGetLastError();
-    delete p;
 }
 
 int mhs_transpose(mhs_ctx* ctx, const mhs_csr* A, mhs_csr* At) {

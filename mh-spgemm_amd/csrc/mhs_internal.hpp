@@ -22,7 +22,6 @@
 #include <hip/hip_runtime.h>
 
 #include "mhs_numplan.hpp"
-#include "mhs_valplan.hpp"
 
 namespace mhs {
 
@@ -154,60 +153,9 @@ hipError_t transpose_csr(const Csr& A, int* tptr, int* tcol, double* tval, void*
 hipError_t transpose_pattern(const Csr& A, int* tptr, int* trow, int* tperm, void* tmp, size_t* tmp_bytes,
                              hipStream_t s);
 hipError_t init_kernel_attributes();
-// mhs_values.hip: values-only SpGEMM on a kept pattern (mhs_spgemm_values; classes and plan in mhs_valplan.hpp).
-// The six pattern arrays a values plan borrows ...
-struct ValPattern {
-    int M;
-    const int *Aptr, *Acol, *Bptr, *Bcol, *Cptr, *Ccol;
-};
-// ... and what a hot call's kernels take: the patterns and the call's three value arrays.
-struct ValArgs {
-    const int *Aptr, *Acol;
-    const double* Aval;
-    const int *Bptr, *Bcol;
-    const double* Bval;
-    const int *Cptr, *Ccol;
-    double* Cval;
-};
-// A masked plan's B^T pattern (transpose_pattern of B), read by the dot class only; tptr null: none
-struct ValTrans {
-    const int *tptr, *trow, *tperm;
-};
-// How a masked plan classifies: the form (ValMaskForm), AUTO's ratio, and B^T's row pointer for the dot cost
-struct ValMask {
-    const int* tptr;
-    int form, ratio;
-};
-constexpr int VAL_CNT_INTS = (3 * VAL_NCLASS + 2) * BINCNT_STRIDE;
-hipError_t init_values_attributes();  // (called by init_kernel_attributes)
-// Plan creation.  bad: a device int holding the first offending row (atomicMin; INT_MAX: none).
-void launch_val_check_ptr(const int* ptr, int M, int nnz, int* bad, hipStream_t s);
-void launch_val_check_cols(const int* ptr, const int* col, int M, int ncols, bool strict, int* bad, hipStream_t s);
-// cnt: VAL_CNT_INTS ints zeroed by the caller -- 3 * VAL_NCLASS counters BINCNT_STRIDE ints apart (rows, list
-// cursors, LDS need per class), then the 64-bit product count and (masked plans) the 64-bit kept count; lists: M ints, class c's rows at the prefix of the counts before it
-void launch_val_classify(const ValPattern& p, int* cnt, int* lists, hipStream_t s);
-void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s);
-// Masked plans: the same two classify passes by val_class_masked, and in place of the verify walk a
-// count of the products that land in the mask, into the 64-bit counter after the product count
-void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int* cnt, int* lists, hipStream_t s);
-void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s);
-// One launch of a values plan (plan_values) over its class's row list, on `s` (t: read by VK_DOT only).
-void issue_values(const ValLaunch& l, const ValArgs& a, const ValTrans& t, const int* list, hipStream_t s);
-// mhs_values_grad.hip: the backward of a values call (mhs_spgemm_values_grad).  G: the cotangent on C's pattern;
-// dA / dB: the gradients, zero-filled by the caller, either nullptr (that side is not computed, and Bval / Aval
-// is then not read).
-struct ValGradArgs {
-    const int *Aptr, *Acol;
-    const double* Aval;
-    const int *Bptr, *Bcol;
-    const double* Bval;
-    const int *Cptr, *Ccol;
-    const double* G;
-    double *dA, *dB;
-};
-hipError_t init_values_grad_attributes();  // (called by init_values_attributes)
-// One launch of a values plan's backward (plan_grad) over its class's row list, on `s`.
-void issue_values_grad(const ValLaunch& l, const ValGradArgs& a, const int* list, hipStream_t s);
+// mhs_values.hip: the values-only kernels' launch attributes (called by init_kernel_attributes; their
+// declarations are in mhs_valwalk.hpp)
+hipError_t init_values_attributes();
 // device address of the probe-conflict counter (nullptr unless built with MHS_PROBE_STATS=1)
 hipError_t probe_counter(unsigned long long** dev);
 // mhs_hbm.hip: the streaming kernels of mhs_hbm_peak on the current device (gbps[3]: copy, read, write)

@@ -144,6 +144,30 @@ struct ValCounts {
     int need[VAL_NCLASS];
 };
 
+// k_val_classify's counter block, as int offsets: per class the rows, the list cursor of the fill pass
+// and the need, every counter on a 128-byte line of its own (BINCNT_STRIDE ints apart), then two
+// 64-bit counts: the pattern's products and (masked plans: launch_val_count_kept) the kept ones.
+constexpr int val_cnt_rows(int c) { return c * BINCNT_STRIDE; }
+constexpr int val_cnt_cursor(int c) { return (VAL_NCLASS + c) * BINCNT_STRIDE; }
+constexpr int val_cnt_need(int c) { return (2 * VAL_NCLASS + c) * BINCNT_STRIDE; }
+constexpr int VAL_CNT_PRODUCTS = 3 * VAL_NCLASS * BINCNT_STRIDE;
+constexpr int VAL_CNT_WIDE = BINCNT_STRIDE > 2 ? BINCNT_STRIDE : 2;  // (a 64-bit count is two ints, whatever the stride)
+constexpr int VAL_CNT_KEPT = VAL_CNT_PRODUCTS + VAL_CNT_WIDE;
+constexpr int VAL_CNT_INTS = VAL_CNT_KEPT + VAL_CNT_WIDE;
+
+// Plan creation's status words: the first bad row of each check (atomicMin; none: still the fill value)
+enum ValStatus : int {
+    VS_APTR,      // A.ptr
+    VS_BPTR,      // B.ptr
+    VS_CPTR,      // C.ptr
+    VS_ACOL,      // A's columns
+    VS_CCOL,      // C's columns
+    VS_PRODUCTS,  // a product's column missing in C
+    VS_BCOL,      // B's columns (masked plans)
+    VS_COUNT,
+};
+constexpr int VAL_STATUS_INTS = (VS_COUNT + 1) & ~1;  // whole 8-byte words
+
 enum ValKernel : int {
     VK_TEAM,          // k_val_team
     VK_WAVE_DIRECT,   // k_val_wave<direct>

@@ -21,12 +21,12 @@ namespace {
 // stride over the B row.  add(column, value) per product.
 template <int G, class F>
 __device__ __forceinline__ void walk_products(const ValArgs& a, int row, int g, int ng, int t, F add) {
-    const int ae = a.Aptr[row + 1];
-    for (int k = a.Aptr[row] + g; k < ae; k += ng) {
-        const int ac = a.Acol[k];
-        const double av = a.Aval[k];
-        const int be = a.Bptr[ac + 1];
-        for (int j = a.Bptr[ac] + t; j < be; j += G) add(a.Bcol[j], av * a.Bval[j]);
+    const int ae = a.A.ptr[row + 1];
+    for (int k = a.A.ptr[row] + g; k < ae; k += ng) {
+        const int ac = a.A.col[k];
+        const double av = a.A.val[k];
+        const int be = a.B.ptr[ac + 1];
+        for (int j = a.B.ptr[ac] + t; j < be; j += G) add(a.B.col[j], av * a.B.val[j]);
     }
 }
 // The same products for a wave's or a block's row, with memory-level parallelism: the row's `lanes`
@@ -39,7 +39,7 @@ template <int G, int CH, class Sync, class Pre, class F>
 __device__ __forceinline__ void walk_staged(const ValArgs& a, int row, int t, int lanes, ValStage<CH>& d, Sync sync, Pre pre,
                                             F add) {
     const int g = t / G, ng = lanes / G, tl = t % G;
-    const int ae = a.Aptr[row + 1], a0 = a.Aptr[row];
+    const int ae = a.A.ptr[row + 1], a0 = a.A.ptr[row];
     if (a0 >= ae) {
         pre();
         sync();
@@ -48,11 +48,11 @@ __device__ __forceinline__ void walk_staged(const ValArgs& a, int row, int t, in
     for (int k0 = a0; k0 < ae; k0 += CH) {
         const int cnt = ae - k0 < CH ? ae - k0 : CH;
         if (t < cnt) {
-            const int ac = a.Acol[k0 + t];
-            const int bs = a.Bptr[ac];
+            const int ac = a.A.col[k0 + t];
+            const int bs = a.B.ptr[ac];
             d.bs[t] = bs;
-            d.len[t] = a.Bptr[ac + 1] - bs;
-            d.av[t] = a.Aval[k0 + t];
+            d.len[t] = a.B.ptr[ac + 1] - bs;
+            d.av[t] = a.A.val[k0 + t];
         }
         if (k0 == a0) pre();
         sync();
@@ -66,8 +66,8 @@ __device__ __forceinline__ void walk_staged(const ValArgs& a, int row, int t, in
                 for (int u = 0; u < VAL_PIECES; ++u) {
                     const int jj = j + u * G;
                     const bool in = jj < len;
-                    c[u] = in ? a.Bcol[bs + jj] : -1;
-                    v[u] = in ? a.Bval[bs + jj] : 0.0;
+                    c[u] = in ? a.B.col[bs + jj] : -1;
+                    v[u] = in ? a.B.val[bs + jj] : 0.0;
                 }
 #pragma unroll
                 for (int u = 0; u < VAL_PIECES; ++u)
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void k_val_check_cols(const int* __restrict__ 
 
 // --------------------------------------------------------------- classify ---
 // One thread per row of C.  FILL false: count the rows and the largest LDS need per class (one
-// reservation per block and class, counters one per 128-byte line).  FILL true: write the rows into
+// reservation per block and class; cnt is the counter block of mhs_valplan.hpp).  FILL true: write the rows into
 // their class lists, class c's list at the prefix of the counts before it.
 // MASKED: the class by val_class_masked -- the row's A entries and, with B^T's row pointer, its dot cost.
 template <bool FILL, bool MASKED>
@@ -161,16 +161,16 @@ __global__ __launch_bounds__(256) void k_val_classify(ValPattern p, ValMask m, i
         }
         __syncthreads();
         if (!FILL && threadIdx.x == 0 && s_prod > 0)  // the pattern's product count (mhs_values_info)
-            atomicAdd((unsigned long long*)(cnt + 3 * VAL_NCLASS * BINCNT_STRIDE), s_prod);
+            atomicAdd((unsigned long long*)(cnt + VAL_CNT_PRODUCTS), s_prod);
         if (threadIdx.x < VAL_NCLASS && s_cnt[threadIdx.x] > 0) {
             const int c = threadIdx.x;
             if (FILL) {
                 int off = 0;
-                for (int b = 0; b < c; ++b) off += cnt[b * BINCNT_STRIDE];
-                s_base[c] = off + atomicAdd(&cnt[(VAL_NCLASS + c) * BINCNT_STRIDE], s_cnt[c]);
+                for (int b = 0; b < c; ++b) off += cnt[val_cnt_rows(b)];
+                s_base[c] = off + atomicAdd(&cnt[val_cnt_cursor(c)], s_cnt[c]);
             } else {
-                atomicAdd(&cnt[c * BINCNT_STRIDE], s_cnt[c]);
-                atomicMax(&cnt[(2 * VAL_NCLASS + c) * BINCNT_STRIDE], s_need[c]);
+                atomicAdd(&cnt[val_cnt_rows(c)], s_cnt[c]);
+                atomicMax(&cnt[val_cnt_need(c)], s_need[c]);
             }
         }
         __syncthreads();
@@ -221,7 +221,7 @@ __device__ __forceinline__ void row_search(const ValArgs& a, int s, int n, doubl
     walk(
         [&] {
             for (int p = t; p < n; p += lanes) {
-                cols[p] = a.Ccol[s + p];
+                cols[p] = a.C.col[s + p];
                 acc[p] = 0.0;
             }
         },
@@ -230,7 +230,7 @@ __device__ __forceinline__ void row_search(const ValArgs& a, int s, int n, doubl
             if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64
         });
     sync();
-    for (int p = t; p < n; p += lanes) a.Cval[s + p] = acc[p];
+    for (int p = t; p < n; p += lanes) a.C.val[s + p] = acc[p];
     sync();
 }
 // Span-indexed sums of one row: acc[col - first], gathered through C.col afterwards.
@@ -246,28 +246,33 @@ __device__ __forceinline__ void row_direct(const ValArgs& a, int s, int n, int f
             if (slot < (unsigned)span) atomicAdd(&acc[slot], v);  // ds_add_f64
         });
     sync();
-    for (int p = t; p < n; p += lanes) a.Cval[s + p] = acc[a.Ccol[s + p] - first];
+    for (int p = t; p < n; p += lanes) a.C.val[s + p] = acc[a.C.col[s + p] - first];
     sync();
+}
+
+// One row of a wave or block class in the row frame: direct or searched sums over the staged walk.
+template <bool DIRECT, int CH, class Sync>
+__device__ __forceinline__ void row_sums(const ValArgs& a, int row, char* base, int region, int t, int lanes, ValStage<CH>& d,
+                                         Sync sync) {
+    val_row<DIRECT>(a, row, base, region, [&](int s, int n, int first, int span, double* acc, int* cols) {
+        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP>(a, row, t, lanes, d, sync, pre, add); };
+        if constexpr (DIRECT) row_direct(a, s, n, first, span, acc, t, lanes, sync, walk);
+        else row_search(a, s, n, acc, cols, t, lanes, sync, walk);
+    });
 }
 
 // Team class: VAL_TEAM_LANES lanes per row, the teams of a wave in step (wave-level ordering).
 __global__ __launch_bounds__(256) void k_val_team(ValArgs a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     const int team = threadIdx.x / VAL_TEAM_LANES, t = threadIdx.x % VAL_TEAM_LANES;
-    const int ne = region / 12;
-    double* acc = (double*)(lds + (size_t)team * region);
-    int* cols = (int*)(acc + ne);
+    const ValSlice sl = search_slice(lds + (size_t)team * region, region);
+    double* acc = sl.val;
+    int* cols = sl.cols;
     for (int base = blockIdx.x * VAL_TEAM_ROWS; base < count; base += gridDim.x * VAL_TEAM_ROWS) {
-        const int idx = base + team;
-        const int row = idx < count ? list[idx] : -1;
-        int s = 0, n = 0;
-        if (row >= 0) {
-            s = a.Cptr[row];
-            n = a.Cptr[row + 1] - s;
-            if (n > ne) n = 0;  // (not this plan's pattern: leave the row alone rather than overrun the slice)
-        }
+        int s, n;
+        const int row = val_team_row(a, list, count, base + team, sl.ne, s, n);
         for (int p = t; p < n; p += VAL_TEAM_LANES) {
-            cols[p] = a.Ccol[s + p];
+            cols[p] = a.C.col[s + p];
             acc[p] = 0.0;
         }
         vwave_sync();
@@ -277,7 +282,7 @@ __global__ __launch_bounds__(256) void k_val_team(ValArgs a, const int* __restri
                 if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64
             });
         vwave_sync();
-        for (int p = t; p < n; p += VAL_TEAM_LANES) a.Cval[s + p] = acc[p];
+        for (int p = t; p < n; p += VAL_TEAM_LANES) a.C.val[s + p] = acc[p];
         vwave_sync();
     }
 }
@@ -288,24 +293,9 @@ __global__ __launch_bounds__(256) void k_val_wave(ValArgs a, const int* __restri
     extern __shared__ __align__(16) char lds[];
     __shared__ ValStage<64> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double* acc = (double*)(lds + (size_t)wave * region);
     auto sync = [] { vwave_sync(); };
-    for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB) {
-        const int row = list[idx];
-        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP>(a, row, lane, 64, stage[wave], sync, pre, add); };
-        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
-        if (n <= 0) continue;
-        if constexpr (DIRECT) {
-            const int first = a.Ccol[s];
-            const long long span = (long long)a.Ccol[s + n - 1] - first + 1;
-            if (span <= 0 || span * 8 > region) continue;  // (not this plan's pattern)
-            row_direct(a, s, n, first, (int)span, acc, lane, 64, sync, walk);
-        } else {
-            const int ne = region / 12;
-            if (n > ne) continue;
-            row_search(a, s, n, acc, (int*)(acc + ne), lane, 64, sync, walk);
-        }
-    }
+    for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB)
+        row_sums<DIRECT>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
 }
 
 // Block classes: one block of T threads per row, up to the whole 160 KiB (VAL_BLOCK_BYTES dynamic + the stage).
@@ -313,37 +303,10 @@ template <int T, bool DIRECT>
 __global__ __launch_bounds__(T) void k_val_block(ValArgs a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     __shared__ ValStage<VAL_STAGE> stage;
-    double* acc = (double*)lds;
-    const int t = threadIdx.x;
     auto sync = [] { __syncthreads(); };
-    // Consecutive rows read the same B rows, and blocks go to the 8 XCDs in turn: XCD x (blocks x, x + 8, ...)
-    // walks its own stretch of the list, in proportion to its blocks, so neighbours meet in one L2.
-    int lo = 0, hi = count, first_j = blockIdx.x, step = gridDim.x;
-    if (gridDim.x >= 8) {
-        const int xcd = blockIdx.x & 7;
-        int before = 0;
-        for (int y = 0; y < xcd; ++y) before += (gridDim.x - y + 7) >> 3;
-        step = (gridDim.x - xcd + 7) >> 3;
-        first_j = blockIdx.x >> 3;
-        lo = (int)((long long)count * before / gridDim.x);
-        hi = (int)((long long)count * (before + step) / gridDim.x);
-    }
-    for (int idx = lo + first_j; idx < hi; idx += step) {
-        const int row = list[idx];
-        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP>(a, row, t, T, stage, sync, pre, add); };
-        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
-        if (n <= 0) continue;
-        if constexpr (DIRECT) {
-            const int first = a.Ccol[s];
-            const long long span = (long long)a.Ccol[s + n - 1] - first + 1;
-            if (span <= 0 || span * 8 > region) continue;
-            row_direct(a, s, n, first, (int)span, acc, t, T, sync, walk);
-        } else {
-            const int ne = region / 12;
-            if (n > ne) continue;
-            row_search(a, s, n, acc, (int*)(acc + ne), t, T, sync, walk);
-        }
-    }
+    const XcdStretch x = xcd_stretch(count);
+    for (int idx = x.begin; idx < x.end; idx += x.step)
+        row_sums<DIRECT>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
 }
 
 // Global class: the row's Cval segment is the accumulator.
@@ -351,13 +314,13 @@ __global__ __launch_bounds__(1024) void k_val_global(ValArgs a, const int* __res
     const int t = threadIdx.x;
     for (int idx = blockIdx.x; idx < count; idx += gridDim.x) {
         const int row = list[idx];
-        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
-        for (int p = t; p < n; p += 1024) a.Cval[s + p] = 0.0;
+        const int s = a.C.ptr[row], n = a.C.ptr[row + 1] - s;
+        for (int p = t; p < n; p += 1024) a.C.val[s + p] = 0.0;
         __threadfence();
         __syncthreads();
         walk_products<VAL_GROUP>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, double v) {
-            const int slot = find_slot(a.Ccol + s, n, c);
-            if (slot >= 0) unsafeAtomicAdd(&a.Cval[s + slot], v);  // global_atomic_add_f64
+            const int slot = find_slot(a.C.col + s, n, c);
+            if (slot >= 0) unsafeAtomicAdd(&a.C.val[s + slot], v);  // global_atomic_add_f64
         });
     }
 }
@@ -378,13 +341,13 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs a, ValTrans tr, const i
     DotStage& d = stage[wave];
     for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB) {
         const int row = list[idx];
-        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
-        const int a0 = a.Aptr[row], ae = a.Aptr[row + 1];
+        const int s = a.C.ptr[row], n = a.C.ptr[row + 1] - s;
+        const int a0 = a.A.ptr[row], ae = a.A.ptr[row + 1];
         for (int p0 = 0; p0 < n; p0 += 64) {
             const int p = p0 + lane;
             int lo0 = 0, hi0 = 0;
             if (p < n) {
-                const int j = a.Ccol[s + p];
+                const int j = a.C.col[s + p];
                 lo0 = tr.tptr[j];
                 hi0 = tr.tptr[j + 1];
             }
@@ -392,8 +355,8 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs a, ValTrans tr, const i
             for (int k0 = a0; k0 < ae; k0 += 64) {
                 const int cnt = ae - k0 < 64 ? ae - k0 : 64;
                 if (lane < cnt) {
-                    d.col[lane] = a.Acol[k0 + lane];
-                    d.av[lane] = a.Aval[k0 + lane];
+                    d.col[lane] = a.A.col[k0 + lane];
+                    d.av[lane] = a.A.val[k0 + lane];
                 }
                 vwave_sync();
                 if (lo0 < hi0)
@@ -405,11 +368,11 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs a, ValTrans tr, const i
                             if (tr.trow[mid] < ac) lo = mid + 1;
                             else hi = mid;
                         }
-                        for (; lo < hi0 && tr.trow[lo] == ac; ++lo) sum += d.av[e] * a.Bval[tr.tperm[lo]];
+                        for (; lo < hi0 && tr.trow[lo] == ac; ++lo) sum += d.av[e] * a.B.val[tr.tperm[lo]];
                     }
                 vwave_sync();
             }
-            if (p < n) a.Cval[s + p] = sum;
+            if (p < n) a.C.val[s + p] = sum;
         }
     }
 }
@@ -420,15 +383,20 @@ int blocks_for(long long items, int per, int cap) {
     return (int)(b < cap ? b : cap);
 }
 
+// The forward's kernels over the LDS classes' lists (val_lds_kernel)
+struct ValKernels {
+    using Fn = void (*)(ValArgs, const int*, int, int);
+    static Fn team() { return k_val_team; }
+    template <bool DIRECT>
+    static Fn wave() { return k_val_wave<DIRECT>; }
+    template <int T, bool DIRECT>
+    static Fn block() { return k_val_block<T, DIRECT>; }
+};
+
 }  // namespace
 
 hipError_t init_values_attributes() {
-    // the 1024-thread block kernels may take the whole 160 KiB (the 256-thread ones run at most VAL_BLOCK_SMALL)
-    hipError_t e = hipFuncSetAttribute((const void*)k_val_block<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       VAL_BLOCK_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k_val_block<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                VAL_BLOCK_BYTES);
+    hipError_t e = val_allow_max_lds<ValKernels>();
     if (e == hipSuccess) e = init_values_grad_attributes();  // their backward (mhs_values_grad.hip)
     return e;
 }
@@ -457,7 +425,7 @@ void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int* cnt,
 void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s) {
     if (p.M <= 0) return;
     hipLaunchKernelGGL(k_val_count_kept, dim3(blocks_for(p.M, WPB, 16384)), dim3(256), 0, s, p,
-                       (unsigned long long*)(cnt + (3 * VAL_NCLASS + 1) * BINCNT_STRIDE));
+                       (unsigned long long*)(cnt + VAL_CNT_KEPT));
 }
 void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s) {
     if (p.M <= 0) return;
@@ -466,21 +434,10 @@ void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s) {
 
 void issue_values(const ValLaunch& l, const ValArgs& a, const ValTrans& t, const int* list, hipStream_t s) {
     const dim3 g(l.grid), b(l.block);
-    switch (l.kernel) {
-    case VK_TEAM: hipLaunchKernelGGL(k_val_team, g, b, l.lds, s, a, list, l.count, l.region); break;
-    case VK_WAVE_DIRECT: hipLaunchKernelGGL(k_val_wave<true>, g, b, l.lds, s, a, list, l.count, l.region); break;
-    case VK_WAVE_SEARCH: hipLaunchKernelGGL(k_val_wave<false>, g, b, l.lds, s, a, list, l.count, l.region); break;
-    case VK_BLOCK_DIRECT:
-        if (l.block == 1024) hipLaunchKernelGGL((k_val_block<1024, true>), g, b, l.lds, s, a, list, l.count, l.region);
-        else hipLaunchKernelGGL((k_val_block<256, true>), g, b, l.lds, s, a, list, l.count, l.region);
-        break;
-    case VK_BLOCK_SEARCH:
-        if (l.block == 1024) hipLaunchKernelGGL((k_val_block<1024, false>), g, b, l.lds, s, a, list, l.count, l.region);
-        else hipLaunchKernelGGL((k_val_block<256, false>), g, b, l.lds, s, a, list, l.count, l.region);
-        break;
-    case VK_GLOBAL: hipLaunchKernelGGL(k_val_global, g, b, 0, s, a, list, l.count); break;
-    case VK_DOT: hipLaunchKernelGGL(k_val_dot, g, b, 0, s, a, t, list, l.count); break;
-    }
+    if (const ValKernels::Fn k = val_lds_kernel<ValKernels>(l.kernel, l.block))
+        hipLaunchKernelGGL(k, g, b, l.lds, s, a, list, l.count, l.region);
+    else if (l.kernel == VK_GLOBAL) hipLaunchKernelGGL(k_val_global, g, b, 0, s, a, list, l.count);
+    else if (l.kernel == VK_DOT) hipLaunchKernelGGL(k_val_dot, g, b, 0, s, a, t, list, l.count);
 }
 
 }  // namespace mhs

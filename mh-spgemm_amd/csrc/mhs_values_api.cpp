@@ -1,0 +1,326 @@
+// mhs_values_api.cpp -- the C ABI of the values-only SpGEMM (include/mhspgemm.h): values plans on a
+// kept or masked pattern, the values call and its backward.
+//
+// Plan creation (values_plan_create) is the only part with host round trips; it runs as numbered steps
+//   1 the three row_ptr arrays -> 2 A's and C's columns -> 3 classify and verify (3m, a mask: B's
+//   columns, B^T, classify, count the kept products) -> one read-back of counters and status
+// on the context's stream, each check read back before the next step indexes through what it checked.
+// A hot call (mhs_spgemm_values, mhs_spgemm_values_grad) is its argument checks and run_values: the
+// plan's launch list issued on the context's stream, timed by the plan's event pair when asked.
+// Kernels and launchers: mhs_values.hip, mhs_values_grad.hip (declared in mhs_valwalk.hpp); classes,
+// launch plans, counter block and status words: mhs_valplan.hpp.
+#include "mhs_ctx.hpp"
+#include "mhs_valwalk.hpp"
+
+#include <cstdlib>
+#include <memory>
+
+using namespace mhs;
+
+// A values plan (mhs_values_plan_create): the six borrowed pattern arrays, the class lists and the
+// launch plan.  Its device memory is its own (not the context workspace): mhs_spgemm calls and
+// mhs_ctx_trim on the same context leave it alone.
+struct mhs_values_plan {
+    int device = 0;
+    ValPattern pat{};
+    long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
+    long long kept = 0;    // products that land in C's pattern (masked plans count them; else = products)
+    char* mem = nullptr;   // lists (M ints), counters (VAL_CNT_INTS), status (VAL_STATUS_INTS)
+    size_t mem_bytes = 0;
+    // a masked plan with dot rows: B^T's pattern -- tptr (B.N + 1), trow, tperm (nnz(B) each) -- the plan's own too
+    char* tmem = nullptr;
+    size_t tmem_bytes = 0;
+    ValTrans trans{};
+    int* lists = nullptr;
+    int list_off[VAL_NCLASS] = {};
+    ValCounts counts{};
+    ValPlan plan{};
+    ValPlan gplan{};        // the backward's launches (plan_grad)
+    hipEvent_t ev[2] = {};  // timed calls
+};
+
+namespace {
+
+static_assert((int)MHS_MASK_AUTO == (int)VM_AUTO && (int)MHS_MASK_PRODUCT == (int)VM_PRODUCT && (int)MHS_MASK_DOT == (int)VM_DOT,
+              "mhs_mask_form is ValMaskForm");
+
+// AUTO's ratio: VAL_DOT_RATIO, or MHS_VAL_DOT_RATIO (diagnostic: one build swept over the ratio)
+int val_dot_ratio() {
+    if (const char* v = std::getenv("MHS_VAL_DOT_RATIO")) {
+        const long r = std::strtol(v, nullptr, 10);
+        if (r >= 1 && r <= 1 << 20) return (int)r;
+    }
+    return VAL_DOT_RATIO;
+}
+
+// Device scratch with one owner: freed once, when the owner goes -- in plan creation after the stream
+// that used it has been read back (or synchronized by the failed plan's destruction).
+struct HipFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+using Scratch = std::unique_ptr<void, HipFree>;
+
+// A plan under construction: the steps of values_plan_create.  Each returns MHS_OK or the call's error
+// (message set); the plan is the caller's to destroy.
+struct PlanBuild {
+    mhs_ctx* ctx;
+    mhs_values_plan* p;
+    const mhs_csr *A, *B, *C;
+    hipStream_t s;
+    int *d_cnt = nullptr, *d_status = nullptr;
+    int status[VAL_STATUS_INTS];
+    int h_cnt[VAL_CNT_INTS];
+    static constexpr int NONE = 0x7f7f7f7f;  // a status word's fill: any row index is below it, as below INT_MAX
+
+    int hip(hipError_t e, const char* what) const { return e == hipSuccess ? MHS_OK : fail_hip(ctx, e, what); }
+    // the status words on the host, once the stream has run what was launched
+    int read_status(const char* what) {
+        hipError_t r = hipGetLastError();
+        if (r == hipSuccess) r = hipMemcpyAsync(status, d_status, sizeof status, hipMemcpyDeviceToHost, s);
+        if (r == hipSuccess) r = hipStreamSynchronize(s);
+        return hip(r, what);
+    }
+    int bad_row(int k, const char* what) const {
+        if (status[k] == NONE) return MHS_OK;
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string("mhs_values_plan_create: ") + what + " (first at row " + std::to_string(status[k]) + ")");
+    }
+
+    // 0. the plan's own memory: lists, counter block (zero), status words (NONE), and its event pair
+    int allocate() {
+        const size_t lists_bytes = al((size_t)(A->M > 0 ? A->M : 1) * 4);
+        p->mem_bytes = lists_bytes + al((size_t)VAL_CNT_INTS * 4) + al((size_t)VAL_STATUS_INTS * 4);
+        if (const int rc = hip(hipMalloc((void**)&p->mem, p->mem_bytes), "mhs_values_plan_create: plan memory")) return rc;
+        for (hipEvent_t& ev : p->ev)
+            if (const int rc = hip(hipEventCreate(&ev), "mhs_values_plan_create: events")) return rc;
+        p->lists = (int*)p->mem;
+        d_cnt = (int*)(p->mem + lists_bytes);
+        d_status = d_cnt + al((size_t)VAL_CNT_INTS * 4) / 4;
+        if (const int rc = hip(hipMemsetAsync(d_cnt, 0, (size_t)VAL_CNT_INTS * 4, s), "plan counters")) return rc;
+        return hip(hipMemsetAsync(d_status, 0x7f, (size_t)VAL_STATUS_INTS * 4, s), "plan status");
+    }
+    // 1. the three row_ptr arrays: everything after this indexes through them
+    int check_row_ptr() {
+        launch_val_check_ptr(A->ptr, A->M, A->nnz, d_status + VS_APTR, s);
+        launch_val_check_ptr(B->ptr, B->M, B->nnz, d_status + VS_BPTR, s);
+        launch_val_check_ptr(C->ptr, C->M, C->nnz, d_status + VS_CPTR, s);
+        if (const int rc = read_status("mhs_values_plan_create: row_ptr check")) return rc;
+        if (const int rc = bad_row(VS_APTR, "A.ptr is not a row_ptr of nnz(A) entries")) return rc;
+        if (const int rc = bad_row(VS_BPTR, "B.ptr is not a row_ptr of nnz(B) entries")) return rc;
+        if (const int rc = bad_row(VS_CPTR, "C.ptr is not monotone from 0 to C.nnz")) return rc;
+        if ((A->M == 0 && A->nnz != 0) || (B->M == 0 && B->nnz != 0) || (C->M == 0 && C->nnz != 0))
+            return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: entries without rows");
+        return MHS_OK;
+    }
+    // 2. A's columns index B's rows; C's columns ascend strictly within [0, C.N)
+    int check_columns() {
+        launch_val_check_cols(A->ptr, A->col, A->M, B->M, false, d_status + VS_ACOL, s);
+        launch_val_check_cols(C->ptr, C->col, C->M, C->N, true, d_status + VS_CCOL, s);
+        if (const int rc = read_status("mhs_values_plan_create: column check")) return rc;
+        if (const int rc = bad_row(VS_ACOL, "a column of A is outside [0, B.M)")) return rc;
+        return bad_row(VS_CCOL, "C's columns are not strictly ascending within [0, C.N)");
+    }
+    // 3. classes, lists, and every product's column looked up in its C row
+    void classify_and_verify() {
+        launch_val_classify(p->pat, d_cnt, p->lists, s);
+        launch_val_verify(p->pat, d_status + VS_PRODUCTS, s);
+    }
+    // 3m. a mask: B^T's pattern for the dot class (its sort indexes by B's columns: checked first; its scratch
+    // is sort_tmp's), classes by val_class_masked, and the products that land in the mask counted where the
+    // plain plan verifies
+    int classify_and_count(int form, Scratch& sort_tmp) {
+        if (form != MHS_MASK_PRODUCT) {
+            launch_val_check_cols(B->ptr, B->col, B->M, B->N, false, d_status + VS_BCOL, s);
+            if (const int rc = read_status("mhs_values_plan_create: column check")) return rc;
+            if (const int rc = bad_row(VS_BCOL, "a column of B is outside [0, B.N)")) return rc;
+            const Csr b{B->M, B->N, B->nnz, B->ptr, B->col, nullptr};
+            const size_t nb = (size_t)B->nnz;
+            const size_t ptr_bytes = al(((size_t)B->N + 1) * 4), ent_bytes = al((nb ? nb : 1) * 4);
+            size_t tmp_bytes = 0;
+            if (const int rc = hip(transpose_pattern(b, nullptr, nullptr, nullptr, nullptr, &tmp_bytes, s),
+                                   "mhs_values_plan_create: B^T (scratch size)"))
+                return rc;
+            if (const int rc = hip(hipMalloc((void**)&p->tmem, ptr_bytes + 2 * ent_bytes), "mhs_values_plan_create: B^T memory"))
+                return rc;
+            p->tmem_bytes = ptr_bytes + 2 * ent_bytes;
+            int* tptr = (int*)p->tmem;
+            int* trow = (int*)(p->tmem + ptr_bytes);
+            int* tperm = (int*)(p->tmem + ptr_bytes + ent_bytes);
+            void* tmp = nullptr;
+            hipError_t e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16);
+            sort_tmp.reset(tmp);
+            if (e == hipSuccess) e = transpose_pattern(b, tptr, trow, tperm, tmp, &tmp_bytes, s);
+            if (const int rc = hip(e, "mhs_values_plan_create: B^T")) return rc;
+            p->trans = ValTrans{tptr, trow, tperm};
+        }
+        launch_val_classify_masked(p->pat, ValMask{p->trans.tptr, form, val_dot_ratio()}, d_cnt, p->lists, s);
+        launch_val_count_kept(p->pat, d_cnt, s);
+        return MHS_OK;
+    }
+    // The one read-back of step 3: the counter block and the status words, then the launch plans from them
+    int read_back(bool masked) {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, s);
+        if (const int rc = hip(e, "mhs_values_plan_create: classify")) return rc;
+        if (const int rc = read_status("mhs_values_plan_create: classify")) return rc;
+        if (!masked)
+            if (const int rc = bad_row(VS_PRODUCTS, "C's pattern misses a column of the product A*B")) return rc;
+        int off = 0;
+        for (int c = 0; c < VAL_NCLASS; ++c) {
+            p->counts.rows[c] = h_cnt[val_cnt_rows(c)];
+            p->counts.need[c] = h_cnt[val_cnt_need(c)];
+            p->list_off[c] = off;
+            off += p->counts.rows[c];
+        }
+        memcpy(&p->products, &h_cnt[VAL_CNT_PRODUCTS], sizeof p->products);
+        p->kept = p->products;
+        if (masked) memcpy(&p->kept, &h_cnt[VAL_CNT_KEPT], sizeof p->kept);
+        if (p->tmem && p->counts.rows[VC_DOT] == 0) {  // no row chose the dot class: B^T goes again
+            (void)hipFree(p->tmem);
+            p->tmem = nullptr;
+            p->tmem_bytes = 0;
+            p->trans = ValTrans{};
+        }
+        p->plan = plan_values(p->counts);
+        p->gplan = plan_grad(p->counts);
+        return MHS_OK;
+    }
+};
+
+// mhs_values_plan_create (masked false: C must contain the product's pattern) and
+// mhs_values_plan_create_masked (C is a mask; form: mhs_mask_form).
+int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form,
+                       mhs_values_plan** out) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
+    *out = nullptr;
+    if (masked && (form < MHS_MASK_AUTO || form > MHS_MASK_DOT))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: form is not an mhs_mask_form");
+    if (A->M < 0 || A->N < 0 || A->nnz < 0 || B->M < 0 || B->N < 0 || B->nnz < 0 || C->M < 0 || C->N < 0 || C->nnz < 0)
+        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: negative dimension");
+    if (A->N != B->M) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: A.N != B.M");
+    if (C->M != A->M) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: C.M != A.M");
+    if (C->N != B->N) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: C.N != B.N");
+    if ((A->M > 0 && (!A->ptr || !C->ptr)) || (B->M > 0 && !B->ptr) || (A->nnz > 0 && !A->col) || (B->nnz > 0 && !B->col) ||
+        (C->nnz > 0 && !C->col))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null device array");
+    MHS_HIP(hipSetDevice(ctx->device));
+    mhs_values_plan* p = new mhs_values_plan();
+    p->device = ctx->device;
+    p->pat = ValPattern{A->M, A->ptr, A->col, B->ptr, B->col, C->ptr, C->col};
+    p->nnzA = A->nnz, p->nnzB = B->nnz, p->nnzC = C->nnz;
+    Scratch sort_tmp;  // (B^T's sort scratch: it outlives the build's last step, which syncs the stream either way)
+    PlanBuild b{ctx, p, A, B, C, ctx->stream};
+    int rc = b.allocate();
+    if (rc == MHS_OK) rc = b.check_row_ptr();
+    if (rc == MHS_OK) rc = b.check_columns();
+    if (rc == MHS_OK && masked) rc = b.classify_and_count(form, sort_tmp);
+    if (rc == MHS_OK && !masked) b.classify_and_verify();
+    if (rc == MHS_OK) rc = b.read_back(masked);
+    if (rc != MHS_OK) {
+        mhs_values_plan_destroy(ctx, p);  // (synchronizes the stream: what it still runs may read the plan's memory)
+        return rc;
+    }
+    *out = p;
+    return MHS_OK;
+}
+
+// A values launch list on the context's stream: pre (the backward's zero fills; may be null) and then
+// issue(launch) for each launch of `plan`, between the plan's events when ms is asked for (the call then
+// returns with the launches done and their time), else followed by the context's sync if it is on.
+template <class Pre, class Issue>
+int run_values(mhs_ctx* ctx, mhs_values_plan* p, const ValPlan& plan, double* ms, Pre pre, Issue issue) {
+    MHS_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    if (ms) MHS_HIP(hipEventRecord(p->ev[0], s));
+    if (const int rc = pre(s)) return rc;
+    for (int i = 0; i < plan.n; ++i) {
+        const ValLaunch& l = plan.launch[i];
+        issue(l, p->lists + p->list_off[l.cls], s);
+    }
+    MHS_HIP(hipGetLastError());
+    if (ms) {
+        float f = 0;
+        MHS_HIP(hipEventRecord(p->ev[1], s));
+        MHS_HIP(hipEventSynchronize(p->ev[1]));
+        MHS_HIP(hipEventElapsedTime(&f, p->ev[0], p->ev[1]));
+        *ms = f;
+    } else if (ctx->sync) {
+        MHS_HIP(hipStreamSynchronize(s));
+    }
+    return MHS_OK;
+}
+
+}  // namespace
+
+int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, out);
+}
+
+int mhs_values_plan_create_masked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int form,
+                                  mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, true, form, out);
+}
+
+int mhs_values_plan_kept(const mhs_values_plan* p, int64_t* kept_products) {
+    if (!p || !kept_products) return MHS_ERR_INVALID;
+    *kept_products = p->kept;
+    return MHS_OK;
+}
+
+int mhs_spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, double* Cval, double* ms) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: null plan");
+    if ((p->nnzA > 0 && !Aval) || (p->nnzB > 0 && !Bval) || (p->nnzC > 0 && !Cval))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: null value array");
+    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: the plan belongs to another device");
+    const ValArgs a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, Cval}};
+    return run_values(
+        ctx, p, p->plan, ms, [](hipStream_t) { return MHS_OK; },
+        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values(l, a, p->trans, list, s); });
+}
+
+int mhs_spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* dCval,
+                           double* dAval, double* dBval, double* ms) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: null plan");
+    if (!dCval) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: null dCval");
+    if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: no output (dAval and dBval are both null)");
+    if ((dAval && !Bval) || (dBval && !Aval))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: dAval needs Bval, dBval needs Aval");
+    if (p->device != ctx->device)
+        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: the plan belongs to another device");
+    const ValGradArgs a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, dCval}, dAval, dBval};
+    return run_values(
+        ctx, p, p->gplan, ms,
+        [&](hipStream_t s) {
+            // dB is summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
+            if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(double) * (size_t)p->nnzA, s));
+            if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(double) * (size_t)p->nnzB, s));
+            return (int)MHS_OK;
+        },
+        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_grad(l, a, list, s); });
+}
+
+int mhs_values_plan_info(const mhs_values_plan* p, mhs_values_info* info) {
+    if (!p || !info) return MHS_ERR_INVALID;
+    memset(info, 0, sizeof *info);
+    for (int c = 0; c < VAL_NCLASS; ++c) info->rows[c] = p->counts.rows[c];
+    info->products = p->products;
+    info->nnzC = p->nnzC;
+    info->plan_bytes = (int64_t)(p->mem_bytes + p->tmem_bytes);
+    return MHS_OK;
+}
+
+void mhs_values_plan_destroy(mhs_ctx* ctx, mhs_values_plan* p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    if (ctx && ctx->stream) (void)hipStreamSynchronize(ctx->stream);  // calls still queued read the lists
+    else (void)hipDeviceSynchronize();
+    for (hipEvent_t ev : p->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    if (p->mem) (void)hipFree(p->mem);
+    if (p->tmem) (void)hipFree(p->tmem);
+    (void)hipGetLastError();
+    delete p;
+}

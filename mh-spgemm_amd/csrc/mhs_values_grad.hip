@@ -49,11 +49,11 @@ __device__ __forceinline__ void grad_staged(const ValGradArgs& a, int a0, int ae
     for (int k0 = a0; k0 < ae; k0 += CH) {
         const int cnt = ae - k0 < CH ? ae - k0 : CH;
         if (t < cnt) {
-            const int ac = a.Acol[k0 + t];
-            const int bs = a.Bptr[ac];
+            const int ac = a.A.col[k0 + t];
+            const int bs = a.B.ptr[ac];
             d.bs[t] = bs;
-            d.len[t] = a.Bptr[ac + 1] - bs;
-            d.av[t] = wb ? a.Aval[k0 + t] : 0.0;
+            d.len[t] = a.B.ptr[ac + 1] - bs;
+            d.av[t] = wb ? a.A.val[k0 + t] : 0.0;
         }
         sync();
         for (int e0 = 0; e0 < cnt; e0 += ng) {  // the same trip count in every lane of the row
@@ -70,8 +70,8 @@ __device__ __forceinline__ void grad_staged(const ValGradArgs& a, int a0, int ae
                     for (int u = 0; u < VAL_PIECES; ++u) {
                         const int jj = j + u * G;
                         const bool in = jj < len;
-                        c[u] = in ? a.Bcol[bs + jj] : -1;
-                        v[u] = in && wa ? a.Bval[bs + jj] : 0.0;
+                        c[u] = in ? a.B.col[bs + jj] : -1;
+                        v[u] = in && wa ? a.B.val[bs + jj] : 0.0;
                     }
 #pragma unroll
                     for (int u = 0; u < VAL_PIECES; ++u) {
@@ -90,34 +90,36 @@ __device__ __forceinline__ void grad_staged(const ValGradArgs& a, int a0, int ae
     }
 }
 
-// One row of a wave or block class: stage G (and C.col) in the row's LDS slice, then the walk.
+// One row of a wave or block class in the row frame: stage G (and C.col) in the row's LDS slice, then the walk.
 template <bool DIRECT, int CH, class Sync>
-__device__ __forceinline__ void grad_row(const ValGradArgs& a, int row, int s, int n, int first, int span, double* g, int* cols,
-                                         int t, int lanes, ValStage<CH>& d, Sync sync) {
-    const int a0 = a.Aptr[row], ae = a.Aptr[row + 1];
-    if (a0 >= ae) return;
-    if constexpr (DIRECT) {
-        for (int p = t; p < span; p += lanes) g[p] = 0.0;
-        sync();
-        for (int p = t; p < n; p += lanes) g[a.Ccol[s + p] - first] = a.G[s + p];
-        grad_staged<VAL_GROUP>(a, a0, ae, t, lanes, d, sync, [&](int c, double& gv) {
-            const unsigned slot = (unsigned)(c - first);
-            if (slot >= (unsigned)span) return false;
-            gv = g[slot];
-            return gv != 0.0;  // (0: outside the pattern, or a zero cotangent -- nothing to add either way)
-        });
-    } else {
-        for (int p = t; p < n; p += lanes) {
-            cols[p] = a.Ccol[s + p];
-            g[p] = a.G[s + p];
+__device__ __forceinline__ void grad_row(const ValGradArgs& a, int row, char* base, int region, int t, int lanes, ValStage<CH>& d,
+                                         Sync sync) {
+    val_row<DIRECT>(a, row, base, region, [&](int s, int n, int first, int span, double* g, int* cols) {
+        const int a0 = a.A.ptr[row], ae = a.A.ptr[row + 1];
+        if (a0 >= ae) return;
+        if constexpr (DIRECT) {
+            for (int p = t; p < span; p += lanes) g[p] = 0.0;
+            sync();
+            for (int p = t; p < n; p += lanes) g[a.C.col[s + p] - first] = a.C.val[s + p];
+            grad_staged<VAL_GROUP>(a, a0, ae, t, lanes, d, sync, [&](int c, double& gv) {
+                const unsigned slot = (unsigned)(c - first);
+                if (slot >= (unsigned)span) return false;
+                gv = g[slot];
+                return gv != 0.0;  // (0: outside the pattern, or a zero cotangent -- nothing to add either way)
+            });
+        } else {
+            for (int p = t; p < n; p += lanes) {
+                cols[p] = a.C.col[s + p];
+                g[p] = a.C.val[s + p];
+            }
+            grad_staged<VAL_GROUP>(a, a0, ae, t, lanes, d, sync, [&](int c, double& gv) {
+                const int slot = find_slot(cols, n, c);
+                if (slot < 0) return false;
+                gv = g[slot];
+                return true;
+            });
         }
-        grad_staged<VAL_GROUP>(a, a0, ae, t, lanes, d, sync, [&](int c, double& gv) {
-            const int slot = find_slot(cols, n, c);
-            if (slot < 0) return false;
-            gv = g[slot];
-            return true;
-        });
-    }
+    });
 }
 
 // Team class: VAL_TEAM_LANES lanes per row, the teams of a wave in step; a team's lanes are the group
@@ -125,26 +127,20 @@ __device__ __forceinline__ void grad_row(const ValGradArgs& a, int row, int s, i
 __global__ __launch_bounds__(256) void k_grad_team(ValGradArgs a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     const int team = threadIdx.x / VAL_TEAM_LANES, t = threadIdx.x % VAL_TEAM_LANES;
-    const int ne = region / 12;
-    double* g = (double*)(lds + (size_t)team * region);
-    int* cols = (int*)(g + ne);
+    const ValSlice sl = search_slice(lds + (size_t)team * region, region);
+    double* g = sl.val;
+    int* cols = sl.cols;
     const bool wa = a.dA != nullptr, wb = a.dB != nullptr;
     for (int base = blockIdx.x * VAL_TEAM_ROWS; base < count; base += gridDim.x * VAL_TEAM_ROWS) {
-        const int idx = base + team;
-        const int row = idx < count ? list[idx] : -1;
-        int s = 0, n = 0, a0 = 0, nA = 0;
-        if (row >= 0) {
-            s = a.Cptr[row];
-            n = a.Cptr[row + 1] - s;
-            if (n > ne) n = 0;  // (not this plan's pattern: leave the row alone rather than overrun the slice)
-        }
+        int s, n, a0 = 0, nA = 0;
+        const int row = val_team_row(a, list, count, base + team, sl.ne, s, n);
         if (n > 0) {
-            a0 = a.Aptr[row];
-            nA = a.Aptr[row + 1] - a0;
+            a0 = a.A.ptr[row];
+            nA = a.A.ptr[row + 1] - a0;
         }
         for (int p = t; p < n; p += VAL_TEAM_LANES) {
-            cols[p] = a.Ccol[s + p];
-            g[p] = a.G[s + p];
+            cols[p] = a.C.col[s + p];
+            g[p] = a.C.val[s + p];
         }
         // every lane of the wave makes as many steps as its longest A row has entries
         int steps = nA;
@@ -159,12 +155,12 @@ __global__ __launch_bounds__(256) void k_grad_team(ValGradArgs a, const int* __r
             const bool on = it < nA;
             double sum = 0.0;
             if (on) {
-                const int ac = a.Acol[a0 + it];
-                const double av = wb ? a.Aval[a0 + it] : 0.0;
-                const int be = a.Bptr[ac + 1];
-                for (int j = a.Bptr[ac] + t; j < be; j += VAL_TEAM_LANES) {
-                    const int slot = find_slot(cols, n, a.Bcol[j]);
-                    if (slot >= 0) grad_product(a, wa, wb, j, wa ? a.Bval[j] : 0.0, av, g[slot], sum);
+                const int ac = a.A.col[a0 + it];
+                const double av = wb ? a.A.val[a0 + it] : 0.0;
+                const int be = a.B.ptr[ac + 1];
+                for (int j = a.B.ptr[ac] + t; j < be; j += VAL_TEAM_LANES) {
+                    const int slot = find_slot(cols, n, a.B.col[j]);
+                    if (slot >= 0) grad_product(a, wa, wb, j, wa ? a.B.val[j] : 0.0, av, g[slot], sum);
                 }
             }
             if (wa) {
@@ -182,23 +178,9 @@ __global__ __launch_bounds__(256) void k_grad_wave(ValGradArgs a, const int* __r
     extern __shared__ __align__(16) char lds[];
     __shared__ ValStage<64> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double* g = (double*)(lds + (size_t)wave * region);
     auto sync = [] { vwave_sync(); };
-    for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB) {
-        const int row = list[idx];
-        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
-        if (n <= 0) continue;
-        if constexpr (DIRECT) {
-            const int first = a.Ccol[s];
-            const long long span = (long long)a.Ccol[s + n - 1] - first + 1;
-            if (span <= 0 || span * 8 > region) continue;  // (not this plan's pattern)
-            grad_row<true>(a, row, s, n, first, (int)span, g, nullptr, lane, 64, stage[wave], sync);
-        } else {
-            const int ne = region / 12;
-            if (n > ne) continue;
-            grad_row<false>(a, row, s, n, 0, 0, g, (int*)(g + ne), lane, 64, stage[wave], sync);
-        }
-    }
+    for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB)
+        grad_row<DIRECT>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
 }
 
 // Block classes: one block of T threads per row, the forward's split of the list over the XCDs.
@@ -206,34 +188,10 @@ template <int T, bool DIRECT>
 __global__ __launch_bounds__(T) void k_grad_block(ValGradArgs a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     __shared__ ValStage<VAL_STAGE> stage;
-    double* g = (double*)lds;
-    const int t = threadIdx.x;
     auto sync = [] { __syncthreads(); };
-    int lo = 0, hi = count, first_j = blockIdx.x, step = gridDim.x;
-    if (gridDim.x >= 8) {
-        const int xcd = blockIdx.x & 7;
-        int before = 0;
-        for (int y = 0; y < xcd; ++y) before += (gridDim.x - y + 7) >> 3;
-        step = (gridDim.x - xcd + 7) >> 3;
-        first_j = blockIdx.x >> 3;
-        lo = (int)((long long)count * before / gridDim.x);
-        hi = (int)((long long)count * (before + step) / gridDim.x);
-    }
-    for (int idx = lo + first_j; idx < hi; idx += step) {
-        const int row = list[idx];
-        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
-        if (n <= 0) continue;
-        if constexpr (DIRECT) {
-            const int first = a.Ccol[s];
-            const long long span = (long long)a.Ccol[s + n - 1] - first + 1;
-            if (span <= 0 || span * 8 > region) continue;
-            grad_row<true>(a, row, s, n, first, (int)span, g, nullptr, t, T, stage, sync);
-        } else {
-            const int ne = region / 12;
-            if (n > ne) continue;
-            grad_row<false>(a, row, s, n, 0, 0, g, (int*)(g + ne), t, T, stage, sync);
-        }
-    }
+    const XcdStretch x = xcd_stretch(count);
+    for (int idx = x.begin; idx < x.end; idx += x.step)
+        grad_row<DIRECT>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
 }
 
 // Global form: LANES lanes per row (1024: a block per row of the global class; 64: a wave per row, the
@@ -246,20 +204,20 @@ __global__ __launch_bounds__(LANES < 256 ? 256 : LANES) void k_grad_global(ValGr
     const bool wa = a.dA != nullptr, wb = a.dB != nullptr;
     for (int idx = blockIdx.x * ROWS + threadIdx.x / LANES; idx < count; idx += gridDim.x * ROWS) {
         const int row = list[idx];
-        const int s = a.Cptr[row], n = a.Cptr[row + 1] - s;
+        const int s = a.C.ptr[row], n = a.C.ptr[row + 1] - s;
         if (n <= 0) continue;
-        const int a0 = a.Aptr[row], ae = a.Aptr[row + 1];
+        const int a0 = a.A.ptr[row], ae = a.A.ptr[row + 1];
         for (int k0 = a0; k0 < ae; k0 += NG) {  // the same trip count in every lane of the row
             const int k = k0 + g;
             const bool on = k < ae;
             double sum = 0.0;
             if (on) {
-                const int ac = a.Acol[k];
-                const double av = wb ? a.Aval[k] : 0.0;
-                const int be = a.Bptr[ac + 1];
-                for (int j = a.Bptr[ac] + tl; j < be; j += VAL_GROUP) {
-                    const int slot = find_slot(a.Ccol + s, n, a.Bcol[j]);
-                    if (slot >= 0) grad_product(a, wa, wb, j, wa ? a.Bval[j] : 0.0, av, a.G[s + slot], sum);
+                const int ac = a.A.col[k];
+                const double av = wb ? a.A.val[k] : 0.0;
+                const int be = a.B.ptr[ac + 1];
+                for (int j = a.B.ptr[ac] + tl; j < be; j += VAL_GROUP) {
+                    const int slot = find_slot(a.C.col + s, n, a.B.col[j]);
+                    if (slot >= 0) grad_product(a, wa, wb, j, wa ? a.B.val[j] : 0.0, av, a.C.val[s + slot], sum);
                 }
             }
             if (wa) {
@@ -270,37 +228,28 @@ __global__ __launch_bounds__(LANES < 256 ? 256 : LANES) void k_grad_global(ValGr
     }
 }
 
+// The backward's kernels over the LDS classes' lists (val_lds_kernel)
+struct GradKernels {
+    using Fn = void (*)(ValGradArgs, const int*, int, int);
+    static Fn team() { return k_grad_team; }
+    template <bool DIRECT>
+    static Fn wave() { return k_grad_wave<DIRECT>; }
+    template <int T, bool DIRECT>
+    static Fn block() { return k_grad_block<T, DIRECT>; }
+};
+
 }  // namespace
 
-hipError_t init_values_grad_attributes() {
-    // as the forward's: the 1024-thread block kernels may take the whole 160 KiB
-    hipError_t e = hipFuncSetAttribute((const void*)k_grad_block<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       VAL_BLOCK_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k_grad_block<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                VAL_BLOCK_BYTES);
-    return e;
-}
+hipError_t init_values_grad_attributes() { return val_allow_max_lds<GradKernels>(); }
 
 void issue_values_grad(const ValLaunch& l, const ValGradArgs& a, const int* list, hipStream_t s) {
     const dim3 g(l.grid), b(l.block);
-    switch (l.kernel) {
-    case VK_TEAM: hipLaunchKernelGGL(k_grad_team, g, b, l.lds, s, a, list, l.count, l.region); break;
-    case VK_WAVE_DIRECT: hipLaunchKernelGGL(k_grad_wave<true>, g, b, l.lds, s, a, list, l.count, l.region); break;
-    case VK_WAVE_SEARCH: hipLaunchKernelGGL(k_grad_wave<false>, g, b, l.lds, s, a, list, l.count, l.region); break;
-    case VK_BLOCK_DIRECT:
-        if (l.block == 1024) hipLaunchKernelGGL((k_grad_block<1024, true>), g, b, l.lds, s, a, list, l.count, l.region);
-        else hipLaunchKernelGGL((k_grad_block<256, true>), g, b, l.lds, s, a, list, l.count, l.region);
-        break;
-    case VK_BLOCK_SEARCH:
-        if (l.block == 1024) hipLaunchKernelGGL((k_grad_block<1024, false>), g, b, l.lds, s, a, list, l.count, l.region);
-        else hipLaunchKernelGGL((k_grad_block<256, false>), g, b, l.lds, s, a, list, l.count, l.region);
-        break;
-    case VK_GLOBAL:  // (plan_grad: 1024 threads a row for the global class, a wave a row for the dot rows)
+    if (const GradKernels::Fn k = val_lds_kernel<GradKernels>(l.kernel, l.block)) {
+        hipLaunchKernelGGL(k, g, b, l.lds, s, a, list, l.count, l.region);
+    } else if (l.kernel == VK_GLOBAL) {  // (plan_grad has no other kernel)
+        // 1024 threads a row for the global class, a wave a row for the dot rows
         if (l.block == 1024) hipLaunchKernelGGL(k_grad_global<1024>, g, b, 0, s, a, list, l.count);
         else hipLaunchKernelGGL(k_grad_global<64>, g, b, 0, s, a, list, l.count);
-        break;
-    default: break;  // (plan_grad has no other kernel)
     }
 }
 

@@ -1,11 +1,66 @@
-// mhs_valwalk.hpp -- device helpers shared by the values kernels (mhs_values.hip) and their
-// backward (mhs_values_grad.hip): the wave-level LDS ordering point, the slot search, and the
-// stage of A entries that the wave and block walks read their B rows from.
+// mhs_valwalk.hpp -- what the values kernels (mhs_values.hip), their backward (mhs_values_grad.hip)
+// and their host side (mhs_values_api.cpp) share.  First the declarations: the argument structs and
+// the launchers.  Then the device helpers of the forward and the backward walk: the wave-level LDS
+// ordering point, the slot search, the XCD stretch of a block's list, the row frame (a class row's C
+// segment, guarded against the launch's LDS region), the stage of A entries that the wave and block
+// walks read their B rows from, and the kernel of a launch.
 #pragma once
 #include "mhs_internal.hpp"
+#include "mhs_valplan.hpp"
+
+#include <initializer_list>
 
 namespace mhs {
 
+// ---------------------------------------------------------- declarations ---
+// The six pattern arrays a values plan borrows ...
+struct ValPattern {
+    int M;
+    const int *Aptr, *Acol, *Bptr, *Bcol, *Cptr, *Ccol;
+};
+// ... and what a hot call's kernels take: each matrix as its pattern and the call's value array for it.
+template <class V>
+struct ValCsr {
+    const int *ptr, *col;
+    V* val;
+};
+struct ValArgs {
+    ValCsr<const double> A, B;
+    ValCsr<double> C;
+};
+// The backward's (mhs_spgemm_values_grad).  C.val is G, the cotangent on C's pattern; dA / dB: the gradients,
+// zero-filled by the caller, either nullptr (that side is not computed, and B.val / A.val is then not read).
+struct ValGradArgs {
+    ValCsr<const double> A, B, C;
+    double *dA, *dB;
+};
+// A masked plan's B^T pattern (transpose_pattern of B), read by the dot class only; tptr null: none
+struct ValTrans {
+    const int *tptr, *trow, *tperm;
+};
+// How a masked plan classifies: the form (ValMaskForm), AUTO's ratio, and B^T's row pointer for the dot cost
+struct ValMask {
+    const int* tptr;
+    int form, ratio;
+};
+// Plan creation.  bad: a device int holding the first offending row (atomicMin; INT_MAX: none).
+void launch_val_check_ptr(const int* ptr, int M, int nnz, int* bad, hipStream_t s);
+void launch_val_check_cols(const int* ptr, const int* col, int M, int ncols, bool strict, int* bad, hipStream_t s);
+// cnt: the counter block of mhs_valplan.hpp (VAL_CNT_INTS ints), zeroed by the caller; lists: M ints,
+// class c's rows at the prefix of the counts before it
+void launch_val_classify(const ValPattern& p, int* cnt, int* lists, hipStream_t s);
+void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s);
+// Masked plans: the same two classify passes by val_class_masked, and in place of the verify walk a
+// count of the products that land in the mask, into the counter block's kept count
+void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int* cnt, int* lists, hipStream_t s);
+void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s);
+// One launch of a values plan (plan_values) over its class's row list, on `s` (t: read by VK_DOT only).
+void issue_values(const ValLaunch& l, const ValArgs& a, const ValTrans& t, const int* list, hipStream_t s);
+// One launch of a values plan's backward (plan_grad) over its class's row list, on `s`.
+void issue_values_grad(const ValLaunch& l, const ValGradArgs& a, const int* list, hipStream_t s);
+hipError_t init_values_grad_attributes();  // (called by init_values_attributes)
+
+// -------------------------------------------------------- device helpers ---
 // Ordering point for LDS traffic between lanes of one wave (a wave's LDS operations are
 // performed in issue order; only the compiler must not move accesses across it).
 static __device__ __forceinline__ void vwave_sync() {
@@ -25,6 +80,68 @@ static __device__ __forceinline__ int find_slot(const int* cols, int n, int c) {
     return lo < n && cols[lo] == c ? lo : -1;
 }
 
+// The list positions of a block-per-row kernel's block: begin, begin + step, ... below end.
+// Consecutive rows read the same B rows, and blocks go to the 8 XCDs in turn: XCD x (blocks x, x + 8, ...)
+// walks its own stretch of the list, in proportion to its blocks, so neighbours meet in one L2.
+struct XcdStretch {
+    int begin, end, step;
+};
+static __device__ __forceinline__ XcdStretch xcd_stretch(int count) {
+    int lo = 0, hi = count, first = blockIdx.x, step = gridDim.x;
+    if (gridDim.x >= 8) {
+        const int xcd = blockIdx.x & 7;
+        int before = 0;
+        for (int y = 0; y < xcd; ++y) before += (gridDim.x - y + 7) >> 3;
+        step = (gridDim.x - xcd + 7) >> 3;
+        first = blockIdx.x >> 3;
+        lo = (int)((long long)count * before / gridDim.x);
+        hi = (int)((long long)count * (before + step) / gridDim.x);
+    }
+    return {lo + first, hi, step};
+}
+
+// The row frame of the LDS classes.  A row's LDS slice is `region` bytes: span-indexed FP64 (direct), or
+// region / 12 FP64 and as many columns behind them (search).  The guards below are all that stands
+// between a pattern that is not the plan's and an overrun of the slice: such a row is left alone.
+struct ValSlice {
+    double* val;
+    int* cols;  // (search)
+    int ne;     // entries the slice holds (search)
+};
+static __device__ __forceinline__ ValSlice search_slice(char* base, int region) {
+    const int ne = region / 12;
+    return {(double*)base, (int*)((double*)base + ne), ne};
+}
+// A wave's or a block's row: body(s, n, first, span, val, cols) for C's segment [s, s + n) of `row`,
+// when it has entries and fits (direct: columns first .. first + span - 1; search: first = span = 0).
+template <bool DIRECT, class Args, class Body>
+__device__ __forceinline__ void val_row(const Args& p, int row, char* base, int region, Body body) {
+    const int s = p.C.ptr[row], n = p.C.ptr[row + 1] - s;
+    if (n <= 0) return;
+    if constexpr (DIRECT) {
+        const int first = p.C.col[s];
+        const long long span = (long long)p.C.col[s + n - 1] - first + 1;
+        if (span <= 0 || span * 8 > region) return;
+        body(s, n, first, (int)span, (double*)base, (int*)nullptr);
+    } else {
+        const ValSlice sl = search_slice(base, region);
+        if (n > sl.ne) return;
+        body(s, n, 0, 0, sl.val, sl.cols);
+    }
+}
+// A team's row: position idx of the list (-1 past its end), C's segment in s and n (n = 0: nothing to do).
+template <class Args>
+__device__ __forceinline__ int val_team_row(const Args& p, const int* list, int count, int idx, int ne, int& s, int& n) {
+    const int row = idx < count ? list[idx] : -1;
+    s = n = 0;
+    if (row >= 0) {
+        s = p.C.ptr[row];
+        n = p.C.ptr[row + 1] - s;
+        if (n > ne) n = 0;
+    }
+    return row;
+}
+
 // Up to CH staged A entries of a row as (B row start, length, A value); entry e of the stage that
 // began at A position k0 is A entry k0 + e.
 template <int CH>
@@ -33,5 +150,31 @@ struct ValStage {
     double av[CH];
 };
 constexpr int VAL_PIECES = 8;  // G-wide pieces of a B row a lane group loads before its first sum
+
+// ---------------------------------------------------------------- launch ---
+// The kernel of a launch over an LDS class's list, nullptr for the other kernels.  K names a direction's
+// kernels: K::Fn, K::team(), K::wave<DIRECT>(), K::block<T, DIRECT>().
+template <class K>
+typename K::Fn val_lds_kernel(int kernel, int block) {
+    const bool big = block == 1024;
+    switch (kernel) {
+    case VK_TEAM: return K::team();
+    case VK_WAVE_DIRECT: return K::template wave<true>();
+    case VK_WAVE_SEARCH: return K::template wave<false>();
+    case VK_BLOCK_DIRECT: return big ? K::template block<1024, true>() : K::template block<256, true>();
+    case VK_BLOCK_SEARCH: return big ? K::template block<1024, false>() : K::template block<256, false>();
+    default: return nullptr;
+    }
+}
+// The 1024-thread block kernels may take the whole 160 KiB (the 256-thread ones run at most VAL_BLOCK_SMALL).
+template <class K>
+hipError_t val_allow_max_lds() {
+    for (int kernel : {VK_BLOCK_DIRECT, VK_BLOCK_SEARCH}) {
+        const hipError_t e = hipFuncSetAttribute((const void*)val_lds_kernel<K>(kernel, 1024),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, VAL_BLOCK_BYTES);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 }  // namespace mhs

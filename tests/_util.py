@@ -282,6 +282,60 @@ def near_zoo(seed: int = 4):
     return A, (B.M, B.N, B.ptr, B.col, B.val)
 
 
+# ---------------------- helpers of the values-plan GPU tests (values, masked, backward) ---
+RTOL, ATOL = 1e-6, 1e-12  # the project's value tolerance (tests/test_gpu_parity.py)
+
+
+def new_values(n, seed, signed=False):
+    rng = np.random.default_rng(seed)
+    v = rng.uniform(0.1, 1.0, n)
+    if signed:
+        v *= rng.choice([-1.0, 1.0], n)
+    return v
+
+
+def upload(tool, v):
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(f"cuda:{tool.device}")
+    torch.cuda.synchronize()
+    return t
+
+
+def filled(tool, n, value=float("nan")):
+    import torch
+    out = torch.full((n,), value, dtype=torch.float64, device=f"cuda:{tool.device}")
+    torch.cuda.synchronize()
+    return out
+
+
+def csr_of(t):
+    import mhspgemm
+    M, N, p, c, v = t
+    return mhspgemm.CSR(M, N, p, c, v)
+
+
+def device_csr(tool, M, N, ptr, col, val=None):
+    import mhspgemm
+    X = mhspgemm.CSR(M, N, ptr, col, np.zeros(len(col)) if val is None else val)
+    X.H2D(tool.device)
+    return X
+
+
+def assert_values(Cp, Ci, Cv, p, c, v, absv=None):
+    """(p, c, v) is (Cp, Ci, Cv): the pattern exactly, every value written, and within 1e-6 relative / 1e-12
+    absolute and the reference's 1e-9 rule -- or, with mixed signs, 1e-6 of the product on absolute values."""
+    import mhspgemm
+    from oracle import oracle as orc
+    assert np.array_equal(p, Cp) and np.array_equal(c, Ci), "the pattern is C's own"
+    assert v.shape == Cv.shape and not np.isnan(v).any(), "every entry is written"
+    if absv is not None:
+        assert np.all(np.abs(v - Cv) <= 1e-6 * absv + 1e-300)
+        return
+    ok, _, _, bv, mr = mhspgemm.compare_tol(Cp, Ci, Cv, p, c, v, RTOL, ATOL)
+    assert ok, f"{bv} values outside 1e-6 relative (max {mr:.3e})"
+    assert orc.compare_ref(Cp, Ci, Cv, p, c, v) == 1, "reference 1e-9 rule"
+
+
 # ------------------------------------------- the values backward's reference ---
 def keys(ptr, col, N):
     rows = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))

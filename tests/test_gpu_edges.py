@@ -17,7 +17,7 @@ import torch
 
 import mhspgemm
 from oracle import oracle as orc
-from _util import EDGE_COPIES, edge_case, edge_rows, edge_values, expand, load_edges, ref_grad
+from _util import EDGE_COPIES, edge_case, edge_rows, edge_values, expand, filled, load_edges, ref_grad, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -80,18 +80,6 @@ def test_edge_full_call(tool, group, name, side):
 
 
 # ---------------------------------- the values-only call and its backward on a kept plan ---
-def upload(tool, v):
-    x = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(f"cuda:{tool.device}")
-    torch.cuda.synchronize()
-    return x
-
-
-def nan_filled(tool, n):
-    x = torch.full((n,), float("nan"), dtype=torch.float64, device=f"cuda:{tool.device}")
-    torch.cuda.synchronize()
-    return x
-
-
 @functools.lru_cache(maxsize=None)
 def plan_reference(group, name, side):
     """Fresh integer values and cotangent, the oracle's C values for them and the bincount gradients."""
@@ -115,7 +103,7 @@ def test_edge_values_plan(tool, group, name, side):
     try:
         info = plan.info()
         dav, dbv = upload(tool, av), upload(tool, bv)
-        out, oA, oB = nan_filled(tool, len(Ci)), nan_filled(tool, A.nnz), nan_filled(tool, B.nnz)
+        out, oA, oB = filled(tool, len(Ci)), filled(tool, A.nnz), filled(tool, B.nnz)
         plan.run(dav, dbv, out=out)
         dA, dB = plan.grad(upload(tool, G), dav, dbv, out_A=oA, out_B=oB)
         torch.cuda.synchronize()

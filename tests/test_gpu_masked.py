@@ -13,37 +13,12 @@ import torch
 import mhspgemm
 from mhspgemm import _lib
 from oracle import oracle as orc
-from _util import GOLDEN, PRODUCT_CASES, bin_zoo, load_golden, random_csr, tiny_zoo
+from _util import (GOLDEN, PRODUCT_CASES, assert_values, bin_zoo, csr_of, device_csr, filled, keys, load_golden, new_values,
+                   random_csr, tiny_zoo, upload)
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-6, 1e-12
 TEAM, WAVE_DIRECT, WAVE_SEARCH, BLOCK_DIRECT, BLOCK_SEARCH, GLOBAL, DOT = 1, 2, 3, 4, 5, 6, 7
-
-
-def new_values(n, seed, signed=False):
-    rng = np.random.default_rng(seed)
-    v = rng.uniform(0.1, 1.0, n)
-    if signed:
-        v *= rng.choice([-1.0, 1.0], n)
-    return v
-
-
-def upload(tool, v):
-    t = torch.from_numpy(np.ascontiguousarray(v)).to(f"cuda:{tool.device}")
-    torch.cuda.synchronize()
-    return t
-
-
-def nan_out(tool, n):
-    out = torch.full((n,), float("nan"), dtype=torch.float64, device=f"cuda:{tool.device}")
-    torch.cuda.synchronize()
-    return out
-
-
-def keys(ptr, col, N):
-    rows = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
-    return rows * N + col
 
 
 def on_mask(Cp, Ci, Cv, Mp, Mc, N):
@@ -64,22 +39,6 @@ def kept_products(A, B, Mp, Mc):
     return int(round(n.sum()))
 
 
-def assert_values(Mp, Mc, want, got, absv=None):
-    assert got.shape == want.shape and not np.isnan(got).any(), "every mask entry is written"
-    if absv is not None:
-        assert np.all(np.abs(got - want) <= 1e-6 * absv + 1e-300)
-        return
-    ok, _, _, bv, mr = mhspgemm.compare_tol(Mp, Mc, want, Mp, Mc, got, RTOL, ATOL)
-    assert ok, f"{bv} values outside 1e-6 relative (max {mr:.3e})"
-    assert orc.compare_ref(Mp, Mc, want, Mp, Mc, got) == 1, "reference 1e-9 rule"
-
-
-def device_csr(tool, M, N, ptr, col, val=None):
-    X = mhspgemm.CSR(M, N, ptr, col, np.zeros(len(col)) if val is None else val)
-    X.H2D(tool.device)
-    return X
-
-
 def run_masked(tool, A, B, Mp, Mc, form, av=None, bv=None, calls=1):
     """A masked plan of A*B (both on the device) on the mask, `calls` calls into NaN-filled outputs.
     Returns (the values of each call, info())."""
@@ -91,7 +50,7 @@ def run_masked(tool, A, B, Mp, Mc, form, av=None, bv=None, calls=1):
         dB = None if bv is None else upload(tool, bv)
         got = []
         for _ in range(calls):
-            out = nan_out(tool, C.nnz)
+            out = filled(tool, C.nnz)
             plan.run(dA, dB, out=out)
             torch.cuda.synchronize()
             got.append(out.cpu().numpy())
@@ -99,11 +58,6 @@ def run_masked(tool, A, B, Mp, Mc, form, av=None, bv=None, calls=1):
         plan.close()
     assert info["nnzC"] == len(Mc) and sum(info["rows"]) == A.M
     return got, info
-
-
-def csr_of(t):
-    M, N, p, c, v = t
-    return mhspgemm.CSR(M, N, p, c, v)
 
 
 def check_forms(tool, A, B, Mp, Mc, forms, seed=1, signed=False):
@@ -122,7 +76,7 @@ def check_forms(tool, A, B, Mp, Mc, forms, seed=1, signed=False):
     infos = {}
     for form in forms:
         (got,), info = run_masked(tool, A, B, Mp, Mc, form, av, bv)
-        assert_values(Mp, Mc, want, got, absv)
+        assert_values(Mp, Mc, want, Mp, Mc, got, absv)
         assert np.all(got[~hit] == 0.0), "mask entries no product reaches are exactly 0.0"
         assert info["products"] == products and info["kept_products"] == kept, (form, info, kept)
         infos[form] = info
@@ -171,7 +125,7 @@ def test_masked_auto_on_containing_mask_is_product_form(tool):
     assert info["plan_bytes"] == plain_info["plan_bytes"], "B^T is freed again when no row chose the dot class"
     assert plain_info["kept_products"] == plain_info["products"] == info["kept_products"]
     want, _ = on_mask(*orc.spgemm(p, c, v, Bp, Bc, Bv, B.N), Cp, Ci, B.N)
-    assert_values(Cp, Ci, want, got)
+    assert_values(Cp, Ci, want, Cp, Ci, got)
 
 
 # 3. triangle counting: L*L on L's pattern, all values 1.0 -- small integers, so exact
@@ -312,7 +266,7 @@ def test_masked_dot_edges_bit_identical(tool):
     absv, _ = on_mask(*orc.spgemm(Ap, Ac, np.abs(av), Bp, Bc, np.abs(bv), N), Mp, Mc, N)
     (g1, g2), info = run_masked(tool, A, B, Mp, Mc, "dot", calls=2)
     assert info["rows"][DOT] == M and info["plan_bytes"] >= 4 * (N + 1) + 8 * len(Bc)
-    assert_values(Mp, Mc, want, g1, absv)
+    assert_values(Mp, Mc, want, Mp, Mc, g1, absv)
     assert np.all(g1[~hit] == 0.0) and (~hit).sum() >= 30
     assert np.array_equal(g1, g2), "a dot row's sum order is fixed: two calls give the same bits"
     assert info["kept_products"] == kept_products(A, B, Mp, Mc)
@@ -344,8 +298,8 @@ def test_masked_auto_picks_dot(tool):
     assert auto["rows"][DOT] == 512 and auto["dot"] == 512 and prod["rows"][DOT] == 0
     assert auto["products"] == prod["products"] == 512 * 32768
     assert auto["kept_products"] == prod["kept_products"] == 512 * 8 * 2
-    assert_values(Mp, Mc, want, ga)
-    assert_values(Mp, Mc, want, gp)
+    assert_values(Mp, Mc, want, Mp, Mc, ga)
+    assert_values(Mp, Mc, want, Mp, Mc, gp)
     assert prod["plan_bytes"] + 8 * len(Bc) <= auto["plan_bytes"], "the product form keeps no B^T"
 
 
@@ -360,7 +314,7 @@ def test_masked_stream_ordered_and_survives_trim(tool):
     plan = mhspgemm.ValuesPlan(tool, A, B, C, masked=True, form="auto")
     try:
         assert plan.info()["rows"][DOT] == 512
-        out = nan_out(tool, C.nnz)
+        out = filled(tool, C.nnz)
         tool.set_option(_lib.MHS_OPT_SYNC, 0)
         tool.set_stream(torch.cuda.current_stream(tool.device).cuda_stream)
         try:
@@ -376,14 +330,14 @@ def test_masked_stream_ordered_and_survives_trim(tool):
         finally:
             Z.release()
         tool.release()  # mhs_ctx_trim: the workspace goes, the plan's B^T stays
-        out2 = nan_out(tool, C.nnz)
+        out2 = filled(tool, C.nnz)
         plan.run(out=out2)
         torch.cuda.synchronize()
         g2 = out2.cpu().numpy()
     finally:
         plan.close()
-    assert_values(Mp, Mc, want, g1)
-    assert_values(Mp, Mc, want, g2)
+    assert_values(Mp, Mc, want, Mp, Mc, g1)
+    assert_values(Mp, Mc, want, Mp, Mc, g2)
     assert np.array_equal(g1, g2)
     Zp, Zi, Zv = orc.spgemm(q, d, w, Yp, Yc, Yv, 4000)
     assert np.array_equal(zp, Zp) and np.array_equal(zc, Zi) and orc.compare_ref(Zp, Zi, Zv, zp, zc, zv) == 1
@@ -411,4 +365,4 @@ def test_masked_rejections_at_create(tool):
         mhspgemm.ValuesPlan(tool, A, B, device_csr(tool, A.M, B.N, Cp, Ci), masked=True, form=7)
     assert e.value.status == 3
     (got,), _ = run_masked(tool, A, B, Cp, Ci, "dot")  # the context is still usable
-    assert_values(Cp, Ci, Cv, got)
+    assert_values(Cp, Ci, Cv, Cp, Ci, got)

@@ -12,26 +12,12 @@ import torch
 import mhspgemm
 from mhspgemm import _lib, synth
 from oracle import oracle as orc
-from _util import GOLDEN, PRODUCT_CASES, bin_zoo, load_golden, random_csr, tiny_zoo
+from _util import (GOLDEN, PRODUCT_CASES, assert_values, bin_zoo, csr_of, load_golden, new_values, random_csr, tiny_zoo,
+                   upload)
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-6, 1e-12
 TEAM, WAVE_DIRECT, WAVE_SEARCH, BLOCK_DIRECT, BLOCK_SEARCH, GLOBAL = 1, 2, 3, 4, 5, 6
-
-
-def new_values(n, seed, signed=False):
-    rng = np.random.default_rng(seed)
-    v = rng.uniform(0.1, 1.0, n)
-    if signed:
-        v *= rng.choice([-1.0, 1.0], n)
-    return v
-
-
-def upload(tool, v):
-    t = torch.from_numpy(np.ascontiguousarray(v)).to(f"cuda:{tool.device}")
-    torch.cuda.synchronize()
-    return t
 
 
 def product(tool, A, B):
@@ -41,17 +27,6 @@ def product(tool, A, B):
         B.H2D(tool.device)
     C, _ = mhspgemm.spgemm(tool, A, B, timing=False)
     return C
-
-
-def assert_values(Cp, Ci, Cv, p, c, v, absv=None):
-    assert np.array_equal(p, Cp) and np.array_equal(c, Ci), "the pattern is C's own"
-    assert not np.isnan(v).any()
-    if absv is not None:
-        assert np.all(np.abs(v - Cv) <= 1e-6 * absv + 1e-300)
-        return
-    ok, _, _, bv, mr = mhspgemm.compare_tol(Cp, Ci, Cv, p, c, v, RTOL, ATOL)
-    assert ok, f"{bv} values outside 1e-6 relative (max {mr:.3e})"
-    assert orc.compare_ref(Cp, Ci, Cv, p, c, v) == 1, "reference 1e-9 rule"
 
 
 def values_check(tool, A, B, seed=1, signed=False):
@@ -78,11 +53,6 @@ def values_check(tool, A, B, seed=1, signed=False):
     assert info["nnzC"] == Cp[-1] and info["products"] == orc.flop(A.col, B.ptr)
     assert sum(info["rows"]) == A.M and info["plan_bytes"] >= 4 * A.M
     return info
-
-
-def csr_of(t):
-    M, N, p, c, v = t
-    return mhspgemm.CSR(M, N, p, c, v)
 
 
 # 1. golden products: empty product, duplicates in A / B, rectangular, dense row and column, tile edges

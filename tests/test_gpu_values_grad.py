@@ -14,32 +14,12 @@ import torch
 import mhspgemm
 from mhspgemm import _lib, synth
 from oracle import oracle as orc
-from _util import GOLDEN, PRODUCT_CASES, bin_zoo, expand, load_golden, random_csr, ref_grad, tiny_zoo
+from _util import (ATOL, GOLDEN, PRODUCT_CASES, RTOL, bin_zoo, csr_of, device_csr, expand, filled, load_golden, new_values,
+                   random_csr, ref_grad, tiny_zoo, upload)
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-6, 1e-12
 TEAM, WAVE_DIRECT, WAVE_SEARCH, BLOCK_DIRECT, BLOCK_SEARCH, GLOBAL, DOT = 1, 2, 3, 4, 5, 6, 7
-
-
-def new_values(n, seed, signed=False):
-    rng = np.random.default_rng(seed)
-    v = rng.uniform(0.1, 1.0, n)
-    if signed:
-        v *= rng.choice([-1.0, 1.0], n)
-    return v
-
-
-def upload(tool, v):
-    t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(f"cuda:{tool.device}")
-    torch.cuda.synchronize()
-    return t
-
-
-def filled(tool, n, value=float("nan")):
-    out = torch.full((n,), value, dtype=torch.float64, device=f"cuda:{tool.device}")
-    torch.cuda.synchronize()
-    return out
 
 
 def assert_grad(got, want, absw, reached, what):
@@ -51,12 +31,6 @@ def assert_grad(got, want, absw, reached, what):
     err = np.abs(got - want)
     bad = err > RTOL * np.abs(want) + ATOL
     assert not bad.any(), f"{what}: {bad.sum()} entries outside 1e-6 relative (max abs error {err.max():.3e})"
-
-
-def device_csr(tool, M, N, ptr, col):
-    X = mhspgemm.CSR(M, N, ptr, col, np.zeros(len(col)))
-    X.H2D(tool.device)
-    return X
 
 
 def grad_check(tool, A, B, Cp, Ci, seed=1, signed=False, masked=False, form="auto"):
@@ -86,11 +60,6 @@ def grad_check(tool, A, B, Cp, Ci, seed=1, signed=False, masked=False, form="aut
     assert_grad(gA, wA, absA, np.bincount(pqs[0], minlength=A.nnz) > 0, "dA")
     assert_grad(gB, wB, absB, np.bincount(pqs[1], minlength=B.nnz) > 0, "dB")
     return info, gA, gB
-
-
-def csr_of(t):
-    M, N, p, c, v = t
-    return mhspgemm.CSR(M, N, p, c, v)
 
 
 def pattern_of(A, B):

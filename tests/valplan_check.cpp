@@ -1,6 +1,7 @@
 // valplan_check.cpp -- the values-only row classes and launch plan (csrc/mhs_valplan.hpp) on the host:
 // the class of rows one below, at and one above every threshold on the n, span and product axes,
-// each class's LDS need, and plan_values' launches, against hand-computed literals.
+// each class's LDS need, and plan_values' launches, against hand-computed literals; and the layout of
+// plan creation's counter block and status words (fields inside the block, disjoint, 64-bit counts aligned).
 // Built by tests/test_values_host.py with -fsanitize=address,undefined; prints "valplan ok".
 #include "../mh-spgemm_amd/csrc/mhs_valplan.hpp"
 
@@ -176,6 +177,34 @@ int main() {
     CHECK(plan_values(one(VC_BLOCK_DIRECT, 70000, 8800)).launch[0].grid == 4096);
     CHECK(plan_values(one(VC_BLOCK_SEARCH, 39, 8800)).launch[0].grid == 39);  // a block per hub row
     CHECK(plan_values(one(VC_GLOBAL, 70000, 0)).launch[0].grid == 1024);
+
+    // ---- the counter block of plan creation: every field inside VAL_CNT_INTS, no two overlapping (the 32-bit
+    // counters one int, the two 64-bit counts two), the 64-bit counts on 8-byte boundaries
+    {
+        struct Field {
+            int at, ints;
+        };
+        Field f[3 * VAL_NCLASS + 2];
+        int nf = 0;
+        for (int c = 0; c < VAL_NCLASS; ++c) {
+            f[nf++] = {val_cnt_rows(c), 1};
+            f[nf++] = {val_cnt_cursor(c), 1};
+            f[nf++] = {val_cnt_need(c), 1};
+        }
+        f[nf++] = {VAL_CNT_PRODUCTS, 2};
+        f[nf++] = {VAL_CNT_KEPT, 2};
+        CHECK(nf == 3 * VAL_NCLASS + 2);
+        for (int i = 0; i < nf; ++i) {
+            CHECK(f[i].at >= 0 && f[i].at + f[i].ints <= VAL_CNT_INTS);
+            for (int j = 0; j < i; ++j) CHECK(f[i].at + f[i].ints <= f[j].at || f[j].at + f[j].ints <= f[i].at);
+        }
+        CHECK(VAL_CNT_PRODUCTS % 2 == 0 && VAL_CNT_KEPT % 2 == 0);
+        CHECK(val_cnt_rows(0) == 0 && val_cnt_rows(1) == BINCNT_STRIDE);  // one counter per stride
+        // the status words: one per check, inside VAL_STATUS_INTS, which is whole 8-byte words
+        CHECK(VS_APTR == 0 && VS_BPTR == 1 && VS_CPTR == 2 && VS_ACOL == 3 && VS_CCOL == 4 && VS_PRODUCTS == 5 &&
+              VS_BCOL == 6 && VS_COUNT == 7);
+        CHECK(VS_COUNT <= VAL_STATUS_INTS && VAL_STATUS_INTS % 2 == 0 && VAL_STATUS_INTS == 8);
+    }
 
     if (failures) return 1;
     std::printf("valplan ok\n");
