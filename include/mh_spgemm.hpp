@@ -252,6 +252,17 @@ public:
             throw std::runtime_error(mhs_last_error(ctx));
         }
     }
+    // The typed constructor (mhs_values_plan_create_typed): a plan for values of `dtype`, MHS_F64 or MHS_F32.
+    // An MHS_F32 plan runs through the float overloads of MH_spgemm_values and MH_spgemm_values_grad.
+    ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C, bool masked, int form, mhs_dtype dtype) : ctx(tools.ctx) {
+        mhs_csr a{A.M, A.N, A.nnz, A.d_ptr, A.d_col, A.d_val};
+        mhs_csr b{B.M, B.N, B.nnz, B.d_ptr, B.d_col, B.d_val};
+        mhs_csr c{C.M, C.N, C.nnz, C.d_ptr, C.d_col, C.d_val};
+        if (mhs_values_plan_create_typed(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, &plan) != MHS_OK) {
+            std::printf("%s\n", mhs_last_error(ctx));
+            throw std::runtime_error(mhs_last_error(ctx));
+        }
+    }
     ValuesPlan(const ValuesPlan&) = delete;
     ValuesPlan& operator=(const ValuesPlan&) = delete;
     ~ValuesPlan() { mhs_values_plan_destroy(ctx, plan); }
@@ -265,6 +276,12 @@ public:
         int64_t k = 0;
         mhs_values_plan_kept(plan, &k);
         return (long long)k;
+    }
+    // the plan's value type
+    mhs_dtype dtype() const {
+        int d = MHS_F64;
+        mhs_values_plan_dtype(plan, &d);
+        return (mhs_dtype)d;
     }
     // the hipEvent time of the last MH_spgemm_values call through this plan (ms)
     double last_ms = 0;
@@ -287,6 +304,24 @@ inline void MH_spgemm_values(const CSR& A, const CSR& B, CSR& C, mhs_shim::Value
 inline void MH_spgemm_values_grad(const CSR& A, const CSR& B, const double* dC, double* dA, double* dB,
                                   mhs_shim::ValuesPlan& plan) {
     const int rc = mhs_spgemm_values_grad(plan.ctx, plan.plan, A.d_val, B.d_val, dC, dA, dB, &plan.last_ms);
+    if (rc != MHS_OK) {
+        std::printf("%s\n", mhs_last_error(plan.ctx));
+        throw std::runtime_error(mhs_last_error(plan.ctx));
+    }
+}
+
+// The same two calls on an MHS_F32 plan (mhs_spgemm_values_f32, mhs_spgemm_values_grad_f32): the values are the
+// caller's float arrays on the device -- nnz(A), nnz(B), nnz(C) entries -- as a CSR's d_val is double.
+inline void MH_spgemm_values(const float* Aval, const float* Bval, float* Cval, mhs_shim::ValuesPlan& plan) {
+    const int rc = mhs_spgemm_values_f32(plan.ctx, plan.plan, Aval, Bval, Cval, &plan.last_ms);
+    if (rc != MHS_OK) {
+        std::printf("%s\n", mhs_last_error(plan.ctx));
+        throw std::runtime_error(mhs_last_error(plan.ctx));
+    }
+}
+inline void MH_spgemm_values_grad(const float* Aval, const float* Bval, const float* dC, float* dA, float* dB,
+                                  mhs_shim::ValuesPlan& plan) {
+    const int rc = mhs_spgemm_values_grad_f32(plan.ctx, plan.plan, Aval, Bval, dC, dA, dB, &plan.last_ms);
     if (rc != MHS_OK) {
         std::printf("%s\n", mhs_last_error(plan.ctx));
         throw std::runtime_error(mhs_last_error(plan.ctx));

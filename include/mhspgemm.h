@@ -265,6 +265,36 @@ int mhs_values_plan_kept(const mhs_values_plan *plan, int64_t *kept_products);
 int mhs_spgemm_values_grad(mhs_ctx *ctx, mhs_values_plan *plan, const double *Aval, const double *Bval,
                            const double *dCval, double *dAval, double *dBval, double *ms);
 
+/* ---- FP32 values plans: forward, masked and backward on float values -------------------------
+ * For callers whose values are float (a sparse-sparse product inside a float32 model): no casts around the
+ * call, half the value bytes, and rows in cheaper classes -- a plan's classes are LDS arithmetic on the
+ * value's size (FP32: a wave holds 2048 direct columns or 1024 searched entries, a block 39,936 or 19,968).
+ * A plan has one value type, fixed at creation: classes, row lists and both launch plans are computed for
+ * it.  mhs_values_plan_create_typed with MHS_F64 is exactly mhs_values_plan_create (masked == 0; form is
+ * then ignored) or mhs_values_plan_create_masked (masked != 0); any other dtype: MHS_ERR_INVALID.  Plan
+ * creation reads no val array, so the mhs_csr arguments serve as they are, whatever their val points at.
+ * mhs_spgemm_values_f32 and mhs_spgemm_values_grad_f32 are mhs_spgemm_values and mhs_spgemm_values_grad on
+ * float arrays: the same null handling, ms and MHS_OPT_SYNC, no allocation and no read-back in a hot call,
+ * every entry of a requested output written, entries no kept product reaches exactly 0.0f.  Sums are float:
+ * an entry of m kept products is within m * 2^-24 * (the sum of the products' absolute values) of the exact
+ * sum, in any order; LDS and memory atomics may flush subnormal sums to zero.  dAval keeps its fixed order
+ * (two calls give the same bits), dBval is summed by FP32 atomics.
+ * A call of the wrong type -- an _f32 call on an FP64 plan, a double call on an FP32 plan -- returns
+ * MHS_ERR_INVALID with a message naming both types, before any HIP call; nothing is written.
+ * Cost on MI355X: the backward gains from the halved value bytes; the forward does not
+ * where LDS sums carry the call (many products per C entry) -- the LDS float add is far slower than the
+ * double one there, and such an FP32 forward is slower than the FP64 forward of the same pattern.
+ * Additions to ABI version 10, like the entries above. */
+typedef enum mhs_dtype { MHS_F64 = 0, MHS_F32 = 1 } mhs_dtype;
+int mhs_values_plan_create_typed(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
+                                 int masked, int form, int dtype, mhs_values_plan **plan);
+/* The plan's value type (mhs_dtype). */
+int mhs_values_plan_dtype(const mhs_values_plan *plan, int *dtype);
+int mhs_spgemm_values_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float *Aval, const float *Bval,
+                          float *Cval, double *ms);
+int mhs_spgemm_values_grad_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float *Aval, const float *Bval,
+                               const float *dCval, float *dAval, float *dBval, double *ms);
+
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).
  * At->M = A->N, At->N = A->M; rows of At list their columns ascending; arrays are

@@ -29,6 +29,16 @@
 // A launch declares what its class's largest row needs (ValCounts::need, k_val_classify's maximum),
 // not the cap, so banded matrices run at the occupancy their own spans allow.
 //
+// The value type.  A plan has one, FP64 or FP32, and everything above that is bytes is a function of its
+// size vb (8 or 4; the names without a vb argument are the FP64 figures).  FP32: a direct sum is 4 B, a
+// searched entry 8 B (sum, then column), so
+//   team    8 B x n <= 512 B per row
+//   wave    span <= 2048 direct, n <= 1024 searched
+//   block   span <= 39,936 direct, n <= 19,968 searched
+// and rows move to cheaper classes.  Counts are not bytes and do not move: VAL_TEAM_NMAX, the product caps,
+// VAL_DENSE_RATIO, VAL_BLOCK_SMALL, VAL_GROUP, the grid caps.  val_slice_entries / val_slice_fits are the
+// guards of a row's LDS slice, for the kernels' row frame (mhs_valwalk.hpp) and for the host alike.
+//
 // plan_values(counts) is the whole launch plan of a hot call; issue_values (mhs_values.hip) turns one
 // ValLaunch and the call's arrays into a kernel launch.  No pointer and no HIP type in here:
 // tests/valplan_check.cpp runs it on the host.  plan_grad(counts) is the launch plan of the backward
@@ -67,32 +77,59 @@ constexpr int VAL_GROUP = 16;          // lanes that share one A entry in the wa
 // (a search step is a dependent HBM / L2 load, a product a streamed one: DESIGN section 11 has the sweep)
 constexpr int VAL_DOT_RATIO = 2;
 
+// Bytes of a value: vb, 8 (FP64) or 4 (FP32)
+constexpr int VAL_VB_F64 = 8, VAL_VB_F32 = 4;
+__host__ __device__ constexpr bool val_vb_ok(int vb) { return vb == VAL_VB_F64 || vb == VAL_VB_F32; }
+__host__ __device__ constexpr int val_search_entry(int vb) { return vb + 4; }  // a searched entry: its sum and its column
+
 // LDS bytes of one row, per method
-__host__ __device__ constexpr long long val_lds_search(long long n) { return 12 * ((n + 1) & ~1LL); }  // sums, then columns
-__host__ __device__ constexpr long long val_lds_direct(long long span) { return 8 * span; }
+__host__ __device__ constexpr long long val_lds_search(long long n, int vb = VAL_VB_F64) {  // sums, then columns
+    return val_search_entry(vb) * ((n + 1) & ~1LL);
+}
+__host__ __device__ constexpr long long val_lds_direct(long long span, int vb = VAL_VB_F64) { return vb * span; }
 
-constexpr int VAL_WAVE_DIRECT_SPAN = VAL_WAVE_BYTES / 8;      // 1024
-constexpr int VAL_WAVE_SEARCH_N = VAL_WAVE_BYTES / 12 & ~1;   // 682
-constexpr int VAL_BLOCK_DIRECT_SPAN = VAL_BLOCK_BYTES / 8;    // 19968
-constexpr int VAL_BLOCK_SEARCH_N = VAL_BLOCK_BYTES / 12 & ~1; // 13312
-static_assert(val_lds_search(VAL_TEAM_NMAX) * VAL_TEAM_ROWS <= 65536, "team launch below the attribute threshold");
-static_assert(val_lds_direct(VAL_WAVE_DIRECT_SPAN) <= VAL_WAVE_BYTES && val_lds_search(VAL_WAVE_SEARCH_N) <= VAL_WAVE_BYTES,
-              "wave rows fit the wave slice");
-static_assert(val_lds_direct(VAL_BLOCK_DIRECT_SPAN) <= VAL_BLOCK_BYTES &&
-                  val_lds_search(VAL_BLOCK_SEARCH_N) <= VAL_BLOCK_BYTES && VAL_BLOCK_BYTES + VAL_STAGE_BYTES <= 163840,
-              "block rows fit one workgroup");
+// The largest rows of the wave and block classes
+__host__ __device__ constexpr int val_wave_direct_span(int vb) { return VAL_WAVE_BYTES / vb; }
+__host__ __device__ constexpr int val_wave_search_n(int vb) { return VAL_WAVE_BYTES / val_search_entry(vb) & ~1; }
+__host__ __device__ constexpr int val_block_direct_span(int vb) { return VAL_BLOCK_BYTES / vb; }
+__host__ __device__ constexpr int val_block_search_n(int vb) { return VAL_BLOCK_BYTES / val_search_entry(vb) & ~1; }
+constexpr int VAL_WAVE_DIRECT_SPAN = val_wave_direct_span(VAL_VB_F64);    // 1024   (FP32: 2048)
+constexpr int VAL_WAVE_SEARCH_N = val_wave_search_n(VAL_VB_F64);          // 682    (FP32: 1024)
+constexpr int VAL_BLOCK_DIRECT_SPAN = val_block_direct_span(VAL_VB_F64);  // 19968  (FP32: 39936)
+constexpr int VAL_BLOCK_SEARCH_N = val_block_search_n(VAL_VB_F64);        // 13312  (FP32: 19968)
+constexpr bool val_caps_fit(int vb) {
+    return val_lds_search(VAL_TEAM_NMAX, vb) * VAL_TEAM_ROWS <= 65536 &&  // team launch below the attribute threshold
+           val_lds_direct(val_wave_direct_span(vb), vb) <= VAL_WAVE_BYTES &&
+           val_lds_search(val_wave_search_n(vb), vb) <= VAL_WAVE_BYTES &&
+           val_lds_direct(val_block_direct_span(vb), vb) <= VAL_BLOCK_BYTES &&
+           val_lds_search(val_block_search_n(vb), vb) <= VAL_BLOCK_BYTES;
+}
+static_assert(val_caps_fit(VAL_VB_F64) && val_caps_fit(VAL_VB_F32), "rows fit their team, wave and block slices");
+static_assert(VAL_BLOCK_BYTES + VAL_STAGE_BYTES <= 163840, "block rows fit one workgroup");
+static_assert(VAL_WAVE_DIRECT_SPAN == 1024 && VAL_WAVE_SEARCH_N == 682 && VAL_BLOCK_DIRECT_SPAN == 19968 &&
+                  VAL_BLOCK_SEARCH_N == 13312 && val_wave_direct_span(4) == 2048 && val_wave_search_n(4) == 1024 &&
+                  val_block_direct_span(4) == 39936 && val_block_search_n(4) == 19968,
+              "the class table of the header comment");
 
-// The class of a row: n C entries over `span` columns, `products` products (saturated).
-__host__ __device__ inline int val_class(int n, long long span, long long products) {
+// The guards of a row's LDS slice of `region` bytes (val_row, search_slice, the team kernels: mhs_valwalk.hpp).
+// Searched: the entries the slice holds, sums first and as many columns behind them; a row of more is left alone.
+__host__ __device__ constexpr int val_slice_entries(int region, int vb) { return region / val_search_entry(vb); }
+// Direct: whether span-indexed sums of `span` columns fit.
+__host__ __device__ constexpr bool val_slice_fits(long long span, int region, int vb) {
+    return span > 0 && span <= region / vb;
+}
+
+// The class of a row: n C entries over `span` columns, `products` products (saturated); vb: the value's bytes.
+__host__ __device__ inline int val_class(int n, long long span, long long products, int vb = VAL_VB_F64) {
     if (n <= 0) return VC_NONE;
     if (n <= VAL_TEAM_NMAX && products <= VAL_TEAM_PMAX) return VC_TEAM;
     if (products <= 0) return VC_GLOBAL;  // zero fill only: no LDS, nothing staged
     const bool wave = products <= VAL_WAVE_PMAX;
-    if (wave && span <= VAL_WAVE_DIRECT_SPAN) return VC_WAVE_DIRECT;
-    if (span <= VAL_BLOCK_DIRECT_SPAN && span <= (long long)VAL_DENSE_RATIO * n) return VC_BLOCK_DIRECT;
-    if (wave && n <= VAL_WAVE_SEARCH_N) return VC_WAVE_SEARCH;
-    if (span <= VAL_BLOCK_DIRECT_SPAN) return VC_BLOCK_DIRECT;
-    if (n <= VAL_BLOCK_SEARCH_N) return VC_BLOCK_SEARCH;
+    if (wave && span <= val_wave_direct_span(vb)) return VC_WAVE_DIRECT;
+    if (span <= val_block_direct_span(vb) && span <= (long long)VAL_DENSE_RATIO * n) return VC_BLOCK_DIRECT;
+    if (wave && n <= val_wave_search_n(vb)) return VC_WAVE_SEARCH;
+    if (span <= val_block_direct_span(vb)) return VC_BLOCK_DIRECT;
+    if (n <= val_block_search_n(vb)) return VC_BLOCK_SEARCH;
     return VC_GLOBAL;
 }
 // How a masked plan may compute its rows (mhs_mask_form of the C ABI)
@@ -113,26 +150,26 @@ __host__ __device__ inline long long val_sat_mul(long long a, long long b) {
 // The class of a masked plan's row: nA entries in A's row, dot_cost = nA x the sum of val_dot_steps
 // over the row's mask entries (saturated).  ratio: VAL_DOT_RATIO, or the diagnostic override.
 __host__ __device__ inline int val_class_masked(int n, long long span, long long products, int nA, long long dot_cost,
-                                                int form, int ratio = VAL_DOT_RATIO) {
+                                                int form, int ratio = VAL_DOT_RATIO, int vb = VAL_VB_F64) {
     const bool can = n > 0 && nA > 0;
     if (can && form == VM_DOT) return VC_DOT;
     if (can && form == VM_AUTO && val_sat_mul(ratio, dot_cost) < products) return VC_DOT;
-    return val_class(n, span, products);
+    return val_class(n, span, products, vb);
 }
 // LDS bytes a row needs in its class (0: none)
-__host__ __device__ inline int val_row_need(int cls, int n, long long span) {
+__host__ __device__ inline int val_row_need(int cls, int n, long long span, int vb = VAL_VB_F64) {
     switch (cls) {
     case VC_TEAM:
     case VC_WAVE_SEARCH:
-    case VC_BLOCK_SEARCH: return (int)val_lds_search(n);
+    case VC_BLOCK_SEARCH: return (int)val_lds_search(n, vb);
     case VC_WAVE_DIRECT:
-    case VC_BLOCK_DIRECT: return (int)val_lds_direct(span);
+    case VC_BLOCK_DIRECT: return (int)val_lds_direct(span, vb);
     default: return 0;
     }
 }
 // The most a row of the class can need
-constexpr int val_class_cap(int cls) {
-    return cls == VC_TEAM ? (int)val_lds_search(VAL_TEAM_NMAX)
+constexpr int val_class_cap(int cls, int vb = VAL_VB_F64) {
+    return cls == VC_TEAM ? (int)val_lds_search(VAL_TEAM_NMAX, vb)
            : cls == VC_WAVE_DIRECT || cls == VC_WAVE_SEARCH ? VAL_WAVE_BYTES
            : cls == VC_BLOCK_DIRECT || cls == VC_BLOCK_SEARCH ? VAL_BLOCK_BYTES
                                                               : 0;
@@ -202,8 +239,8 @@ inline int val_round(int need, int step, int cap) {
     return need <= 0 || b > cap ? cap : b;
 }
 
-// The launches of a hot call, heaviest rows first (they all go on the call's stream).
-inline ValPlan plan_values(const ValCounts& c) {
+// The launches of a hot call, heaviest rows first (they all go on the call's stream).  c: counted at vb.
+inline ValPlan plan_values(const ValCounts& c, int vb = VAL_VB_F64) {
     ValPlan p{};
     auto add = [&](int kernel, int cls, long long blocks, int cap, int threads, int lds, int region) {
         if (p.n >= VAL_PLAN_MAX) return;
@@ -233,7 +270,7 @@ inline ValPlan plan_values(const ValCounts& c) {
             region);
     }
     if (c.rows[VC_TEAM] > 0) {
-        const int region = val_round(c.need[VC_TEAM], 24, val_class_cap(VC_TEAM));
+        const int region = val_round(c.need[VC_TEAM], 2 * val_search_entry(vb), val_class_cap(VC_TEAM, vb));
         add(VK_TEAM, VC_TEAM, ((long long)c.rows[VC_TEAM] + VAL_TEAM_ROWS - 1) / VAL_TEAM_ROWS, VAL_TEAM_GRID, 256,
             VAL_TEAM_ROWS * region, region);
     }
@@ -243,8 +280,8 @@ inline ValPlan plan_values(const ValCounts& c) {
 // The launches of a backward call (mhs_spgemm_values_grad): the forward's, each run by its class's backward
 // kernel (mhs_values_grad.hip), but for the dot rows of a masked plan -- there is no dot-form backward: their
 // list goes to the global-form kernel, a wave per row (block 256; the global class runs it 1024 threads a row).
-inline ValPlan plan_grad(const ValCounts& c) {
-    ValPlan p = plan_values(c);
+inline ValPlan plan_grad(const ValCounts& c, int vb = VAL_VB_F64) {
+    ValPlan p = plan_values(c, vb);
     for (int i = 0; i < p.n; ++i)
         if (p.launch[i].kernel == VK_DOT) p.launch[i].kernel = VK_GLOBAL;  // (cls stays VC_DOT: the list it walks)
     return p;

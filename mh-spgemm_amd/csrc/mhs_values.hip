@@ -6,7 +6,8 @@
 // Hot call: one value kernel per non-empty class.  Each walks A's row, then B's rows, reads
 // Aval / Bval only for values, and -- told the row's sorted columns -- only finds each product's
 // slot: by subtraction (direct classes) or by binary search (team, search and global classes).
-// Sums are FP64 atomics: ds_add_f64 in LDS, global_atomic_add_f64 in the global class.
+// Every value kernel is a template on the plan's value type V (double or float: ValArgs<V>); sums are
+// atomics of that type: ds_add_f64 / ds_add_f32 in LDS, global_atomic_add_f64 / _f32 in the global class.
 // Masked plans (mhs_values_plan_create_masked: C's pattern is a mask, products outside it are dropped)
 // classify by val_class_masked, count the kept products in place of the verify walk, and may send rows
 // to the dot class: k_val_dot, the inner-product form over B^T's pattern (no sums shared, no atomics).
@@ -19,12 +20,12 @@ namespace {
 
 // The products of row `row`: group g of ng groups takes A entries g, g + ng, ...; its G lanes
 // stride over the B row.  add(column, value) per product.
-template <int G, class F>
-__device__ __forceinline__ void walk_products(const ValArgs& a, int row, int g, int ng, int t, F add) {
+template <int G, class V, class F>
+__device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int g, int ng, int t, F add) {
     const int ae = a.A.ptr[row + 1];
     for (int k = a.A.ptr[row] + g; k < ae; k += ng) {
         const int ac = a.A.col[k];
-        const double av = a.A.val[k];
+        const V av = a.A.val[k];
         const int be = a.B.ptr[ac + 1];
         for (int j = a.B.ptr[ac] + t; j < be; j += G) add(a.B.col[j], av * a.B.val[j]);
     }
@@ -35,9 +36,9 @@ __device__ __forceinline__ void walk_products(const ValArgs& a, int row, int g, 
 // lanes takes staged entries g, g + ng, ... and reads its B row VAL_PIECES G-wide pieces at a time,
 // every load issued before the first sum.  pre() runs once, between the first stage's loads and the
 // sync that publishes them (the row's zero fill rides on that sync).
-template <int G, int CH, class Sync, class Pre, class F>
-__device__ __forceinline__ void walk_staged(const ValArgs& a, int row, int t, int lanes, ValStage<CH>& d, Sync sync, Pre pre,
-                                            F add) {
+template <int G, int CH, class V, class Sync, class Pre, class F>
+__device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t, int lanes, ValStage<CH, V>& d, Sync sync,
+                                            Pre pre, F add) {
     const int g = t / G, ng = lanes / G, tl = t % G;
     const int ae = a.A.ptr[row + 1], a0 = a.A.ptr[row];
     if (a0 >= ae) {
@@ -58,16 +59,16 @@ __device__ __forceinline__ void walk_staged(const ValArgs& a, int row, int t, in
         sync();
         for (int e = g; e < cnt; e += ng) {
             const int bs = d.bs[e], len = d.len[e];
-            const double av = d.av[e];
+            const V av = d.av[e];
             for (int j = tl; j < len; j += VAL_PIECES * G) {
                 int c[VAL_PIECES];
-                double v[VAL_PIECES];
+                V v[VAL_PIECES];
 #pragma unroll
                 for (int u = 0; u < VAL_PIECES; ++u) {
                     const int jj = j + u * G;
                     const bool in = jj < len;
                     c[u] = in ? a.B.col[bs + jj] : -1;
-                    v[u] = in ? a.B.val[bs + jj] : 0.0;
+                    v[u] = in ? a.B.val[bs + jj] : V(0);
                 }
 #pragma unroll
                 for (int u = 0; u < VAL_PIECES; ++u)
@@ -120,8 +121,10 @@ __global__ __launch_bounds__(256) void k_val_check_cols(const int* __restrict__ 
 // reservation per block and class; cnt is the counter block of mhs_valplan.hpp).  FILL true: write the rows into
 // their class lists, class c's list at the prefix of the counts before it.
 // MASKED: the class by val_class_masked -- the row's A entries and, with B^T's row pointer, its dot cost.
+// vb: the bytes of the plan's value type, which the classes and the LDS needs depend on.
 template <bool FILL, bool MASKED>
-__global__ __launch_bounds__(256) void k_val_classify(ValPattern p, ValMask m, int* __restrict__ cnt, int* __restrict__ lists) {
+__global__ __launch_bounds__(256) void k_val_classify(ValPattern p, ValMask m, int vb, int* __restrict__ cnt,
+                                                      int* __restrict__ lists) {
     __shared__ int s_cnt[VAL_NCLASS], s_need[VAL_NCLASS], s_base[VAL_NCLASS];
     __shared__ unsigned long long s_prod;
     for (int base = blockIdx.x * 256; base < p.M; base += gridDim.x * 256) {
@@ -149,13 +152,13 @@ __global__ __launch_bounds__(256) void k_val_classify(ValPattern p, ValMask m, i
                         const int j = p.Ccol[q];
                         steps = val_sat_add(steps, val_dot_steps(m.tptr[j + 1] - m.tptr[j]));
                     }
-                cls = val_class_masked(n, span, products, nA, val_sat_mul(nA, steps), m.tptr ? m.form : VM_PRODUCT, m.ratio);
+                cls = val_class_masked(n, span, products, nA, val_sat_mul(nA, steps), m.tptr ? m.form : VM_PRODUCT, m.ratio, vb);
             } else {
-                cls = val_class(n, span, products);
+                cls = val_class(n, span, products, vb);
             }
             rank = atomicAdd(&s_cnt[cls], 1);
             if (!FILL) {
-                atomicMax(&s_need[cls], val_row_need(cls, n, span));
+                atomicMax(&s_need[cls], val_row_need(cls, n, span, vb));
                 if (products > 0) atomicAdd(&s_prod, (unsigned long long)products);
             }
         }
@@ -215,35 +218,35 @@ __global__ __launch_bounds__(256) void k_val_count_kept(ValPattern p, unsigned l
 // Searched sums of one row by `lanes` lanes (lane t): cols / acc are the row's LDS slice.
 // walk(pre, add) runs pre() and a sync, then add(column, value) per product; sync orders the steps
 // (a wave's or a block's).
-template <class Sync, class Walk>
-__device__ __forceinline__ void row_search(const ValArgs& a, int s, int n, double* acc, int* cols, int t, int lanes, Sync sync,
+template <class V, class Sync, class Walk>
+__device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V* acc, int* cols, int t, int lanes, Sync sync,
                                            Walk walk) {
     walk(
         [&] {
             for (int p = t; p < n; p += lanes) {
                 cols[p] = a.C.col[s + p];
-                acc[p] = 0.0;
+                acc[p] = V(0);
             }
         },
-        [&](int c, double v) {
+        [&](int c, V v) {
             const int slot = find_slot(cols, n, c);
-            if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64
+            if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64 / ds_add_f32
         });
     sync();
     for (int p = t; p < n; p += lanes) a.C.val[s + p] = acc[p];
     sync();
 }
 // Span-indexed sums of one row: acc[col - first], gathered through C.col afterwards.
-template <class Sync, class Walk>
-__device__ __forceinline__ void row_direct(const ValArgs& a, int s, int n, int first, int span, double* acc, int t, int lanes,
+template <class V, class Sync, class Walk>
+__device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, int first, int span, V* acc, int t, int lanes,
                                            Sync sync, Walk walk) {
     walk(
         [&] {
-            for (int p = t; p < span; p += lanes) acc[p] = 0.0;
+            for (int p = t; p < span; p += lanes) acc[p] = V(0);
         },
-        [&](int c, double v) {
+        [&](int c, V v) {
             const unsigned slot = (unsigned)(c - first);
-            if (slot < (unsigned)span) atomicAdd(&acc[slot], v);  // ds_add_f64
+            if (slot < (unsigned)span) atomicAdd(&acc[slot], v);  // ds_add_f64 / ds_add_f32
         });
     sync();
     for (int p = t; p < n; p += lanes) a.C.val[s + p] = acc[a.C.col[s + p] - first];
@@ -251,10 +254,10 @@ __device__ __forceinline__ void row_direct(const ValArgs& a, int s, int n, int f
 }
 
 // One row of a wave or block class in the row frame: direct or searched sums over the staged walk.
-template <bool DIRECT, int CH, class Sync>
-__device__ __forceinline__ void row_sums(const ValArgs& a, int row, char* base, int region, int t, int lanes, ValStage<CH>& d,
-                                         Sync sync) {
-    val_row<DIRECT>(a, row, base, region, [&](int s, int n, int first, int span, double* acc, int* cols) {
+template <bool DIRECT, int CH, class V, class Sync>
+__device__ __forceinline__ void row_sums(const ValArgs<V>& a, int row, char* base, int region, int t, int lanes,
+                                         ValStage<CH, V>& d, Sync sync) {
+    val_row<DIRECT>(a, row, base, region, [&](int s, int n, int first, int span, V* acc, int* cols) {
         auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP>(a, row, t, lanes, d, sync, pre, add); };
         if constexpr (DIRECT) row_direct(a, s, n, first, span, acc, t, lanes, sync, walk);
         else row_search(a, s, n, acc, cols, t, lanes, sync, walk);
@@ -262,24 +265,25 @@ __device__ __forceinline__ void row_sums(const ValArgs& a, int row, char* base, 
 }
 
 // Team class: VAL_TEAM_LANES lanes per row, the teams of a wave in step (wave-level ordering).
-__global__ __launch_bounds__(256) void k_val_team(ValArgs a, const int* __restrict__ list, int count, int region) {
+template <class V>
+__global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     const int team = threadIdx.x / VAL_TEAM_LANES, t = threadIdx.x % VAL_TEAM_LANES;
-    const ValSlice sl = search_slice(lds + (size_t)team * region, region);
-    double* acc = sl.val;
+    const ValSlice<V> sl = search_slice<V>(lds + (size_t)team * region, region);
+    V* acc = sl.val;
     int* cols = sl.cols;
     for (int base = blockIdx.x * VAL_TEAM_ROWS; base < count; base += gridDim.x * VAL_TEAM_ROWS) {
         int s, n;
         const int row = val_team_row(a, list, count, base + team, sl.ne, s, n);
         for (int p = t; p < n; p += VAL_TEAM_LANES) {
             cols[p] = a.C.col[s + p];
-            acc[p] = 0.0;
+            acc[p] = V(0);
         }
         vwave_sync();
         if (n > 0)
-            walk_products<VAL_TEAM_LANES>(a, row, 0, 1, t, [&](int c, double v) {
+            walk_products<VAL_TEAM_LANES>(a, row, 0, 1, t, [&](int c, V v) {
                 const int slot = find_slot(cols, n, c);
-                if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64
+                if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64 / ds_add_f32
             });
         vwave_sync();
         for (int p = t; p < n; p += VAL_TEAM_LANES) a.C.val[s + p] = acc[p];
@@ -288,10 +292,10 @@ __global__ __launch_bounds__(256) void k_val_team(ValArgs a, const int* __restri
 }
 
 // Wave classes: one wave64 per row, WPB rows per block.
-template <bool DIRECT>
-__global__ __launch_bounds__(256) void k_val_wave(ValArgs a, const int* __restrict__ list, int count, int region) {
+template <class V, bool DIRECT>
+__global__ __launch_bounds__(256) void k_val_wave(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
-    __shared__ ValStage<64> stage[WPB];
+    __shared__ ValStage<64, V> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     auto sync = [] { vwave_sync(); };
     for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB)
@@ -299,10 +303,10 @@ __global__ __launch_bounds__(256) void k_val_wave(ValArgs a, const int* __restri
 }
 
 // Block classes: one block of T threads per row, up to the whole 160 KiB (VAL_BLOCK_BYTES dynamic + the stage).
-template <int T, bool DIRECT>
-__global__ __launch_bounds__(T) void k_val_block(ValArgs a, const int* __restrict__ list, int count, int region) {
+template <class V, int T, bool DIRECT>
+__global__ __launch_bounds__(T) void k_val_block(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
-    __shared__ ValStage<VAL_STAGE> stage;
+    __shared__ ValStage<VAL_STAGE, V> stage;
     auto sync = [] { __syncthreads(); };
     const XcdStretch x = xcd_stretch(count);
     for (int idx = x.begin; idx < x.end; idx += x.step)
@@ -310,17 +314,18 @@ __global__ __launch_bounds__(T) void k_val_block(ValArgs a, const int* __restric
 }
 
 // Global class: the row's Cval segment is the accumulator.
-__global__ __launch_bounds__(1024) void k_val_global(ValArgs a, const int* __restrict__ list, int count) {
+template <class V>
+__global__ __launch_bounds__(1024) void k_val_global(ValArgs<V> a, const int* __restrict__ list, int count) {
     const int t = threadIdx.x;
     for (int idx = blockIdx.x; idx < count; idx += gridDim.x) {
         const int row = list[idx];
         const int s = a.C.ptr[row], n = a.C.ptr[row + 1] - s;
-        for (int p = t; p < n; p += 1024) a.C.val[s + p] = 0.0;
+        for (int p = t; p < n; p += 1024) a.C.val[s + p] = V(0);
         __threadfence();
         __syncthreads();
-        walk_products<VAL_GROUP>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, double v) {
+        walk_products<VAL_GROUP>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, V v) {
             const int slot = find_slot(a.C.col + s, n, c);
-            if (slot >= 0) unsafeAtomicAdd(&a.C.val[s + slot], v);  // global_atomic_add_f64
+            if (slot >= 0) unsafeAtomicAdd(&a.C.val[s + slot], v);  // global_atomic_add_f64 / _f32
         });
     }
 }
@@ -330,15 +335,17 @@ __global__ __launch_bounds__(1024) void k_val_global(ValArgs a, const int* __res
 // every A entry of the row -- staged 64 at a time as (column, value) in the wave's static LDS -- finds
 // the A column's lower bound in trow[lo0, hi0) and adds av * Bval[tperm[q]] over the equal run (B's
 // duplicates, in B's order).  One sum per entry in a register, in A's entry order: no atomics, the
-// same bits on every call; the entry is stored once, reached or not.
+// same bits on every call; the entry is stored once, reached or not.  The register sum is a V.
+template <class V>
 struct DotStage {
     int col[64];
-    double av[64];
+    V av[64];
 };
-__global__ __launch_bounds__(256) void k_val_dot(ValArgs a, ValTrans tr, const int* __restrict__ list, int count) {
-    __shared__ DotStage stage[WPB];
+template <class V>
+__global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, const int* __restrict__ list, int count) {
+    __shared__ DotStage<V> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    DotStage& d = stage[wave];
+    DotStage<V>& d = stage[wave];
     for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB) {
         const int row = list[idx];
         const int s = a.C.ptr[row], n = a.C.ptr[row + 1] - s;
@@ -351,7 +358,7 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs a, ValTrans tr, const i
                 lo0 = tr.tptr[j];
                 hi0 = tr.tptr[j + 1];
             }
-            double sum = 0.0;
+            V sum = V(0);
             for (int k0 = a0; k0 < ae; k0 += 64) {
                 const int cnt = ae - k0 < 64 ? ae - k0 : 64;
                 if (lane < cnt) {
@@ -383,20 +390,22 @@ int blocks_for(long long items, int per, int cap) {
     return (int)(b < cap ? b : cap);
 }
 
-// The forward's kernels over the LDS classes' lists (val_lds_kernel)
+// The forward's kernels over the LDS classes' lists (val_lds_kernel), for the value type V
+template <class V>
 struct ValKernels {
-    using Fn = void (*)(ValArgs, const int*, int, int);
-    static Fn team() { return k_val_team; }
+    using Fn = void (*)(ValArgs<V>, const int*, int, int);
+    static Fn team() { return k_val_team<V>; }
     template <bool DIRECT>
-    static Fn wave() { return k_val_wave<DIRECT>; }
+    static Fn wave() { return k_val_wave<V, DIRECT>; }
     template <int T, bool DIRECT>
-    static Fn block() { return k_val_block<T, DIRECT>; }
+    static Fn block() { return k_val_block<V, T, DIRECT>; }
 };
 
 }  // namespace
 
 hipError_t init_values_attributes() {
-    hipError_t e = val_allow_max_lds<ValKernels>();
+    hipError_t e = val_allow_max_lds<ValKernels<double>>();
+    if (e == hipSuccess) e = val_allow_max_lds<ValKernels<float>>();
     if (e == hipSuccess) e = init_values_grad_attributes();  // their backward (mhs_values_grad.hip)
     return e;
 }
@@ -410,17 +419,17 @@ void launch_val_check_cols(const int* ptr, const int* col, int M, int ncols, boo
     hipLaunchKernelGGL(k_val_check_cols, dim3(blocks_for(M, WPB, 16384)), dim3(256), 0, s, ptr, col, M, ncols, strict ? 1 : 0,
                        bad);
 }
-void launch_val_classify(const ValPattern& p, int* cnt, int* lists, hipStream_t s) {
+void launch_val_classify(const ValPattern& p, int vb, int* cnt, int* lists, hipStream_t s) {
     if (p.M <= 0) return;
     const int grid = blocks_for(p.M, 256, 16384);
-    hipLaunchKernelGGL((k_val_classify<false, false>), dim3(grid), dim3(256), 0, s, p, ValMask{}, cnt, lists);
-    hipLaunchKernelGGL((k_val_classify<true, false>), dim3(grid), dim3(256), 0, s, p, ValMask{}, cnt, lists);
+    hipLaunchKernelGGL((k_val_classify<false, false>), dim3(grid), dim3(256), 0, s, p, ValMask{}, vb, cnt, lists);
+    hipLaunchKernelGGL((k_val_classify<true, false>), dim3(grid), dim3(256), 0, s, p, ValMask{}, vb, cnt, lists);
 }
-void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int* cnt, int* lists, hipStream_t s) {
+void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int vb, int* cnt, int* lists, hipStream_t s) {
     if (p.M <= 0) return;
     const int grid = blocks_for(p.M, 256, 16384);
-    hipLaunchKernelGGL((k_val_classify<false, true>), dim3(grid), dim3(256), 0, s, p, m, cnt, lists);
-    hipLaunchKernelGGL((k_val_classify<true, true>), dim3(grid), dim3(256), 0, s, p, m, cnt, lists);
+    hipLaunchKernelGGL((k_val_classify<false, true>), dim3(grid), dim3(256), 0, s, p, m, vb, cnt, lists);
+    hipLaunchKernelGGL((k_val_classify<true, true>), dim3(grid), dim3(256), 0, s, p, m, vb, cnt, lists);
 }
 void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s) {
     if (p.M <= 0) return;
@@ -432,12 +441,15 @@ void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s) {
     hipLaunchKernelGGL(k_val_verify, dim3(blocks_for(p.M, WPB, 16384)), dim3(256), 0, s, p, bad);
 }
 
-void issue_values(const ValLaunch& l, const ValArgs& a, const ValTrans& t, const int* list, hipStream_t s) {
+template <class V>
+void issue_values(const ValLaunch& l, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s) {
     const dim3 g(l.grid), b(l.block);
-    if (const ValKernels::Fn k = val_lds_kernel<ValKernels>(l.kernel, l.block))
+    if (const typename ValKernels<V>::Fn k = val_lds_kernel<ValKernels<V>>(l.kernel, l.block))
         hipLaunchKernelGGL(k, g, b, l.lds, s, a, list, l.count, l.region);
-    else if (l.kernel == VK_GLOBAL) hipLaunchKernelGGL(k_val_global, g, b, 0, s, a, list, l.count);
-    else if (l.kernel == VK_DOT) hipLaunchKernelGGL(k_val_dot, g, b, 0, s, a, t, list, l.count);
+    else if (l.kernel == VK_GLOBAL) hipLaunchKernelGGL(k_val_global<V>, g, b, 0, s, a, list, l.count);
+    else if (l.kernel == VK_DOT) hipLaunchKernelGGL(k_val_dot<V>, g, b, 0, s, a, t, list, l.count);
 }
+template void issue_values<double>(const ValLaunch&, const ValArgs<double>&, const ValTrans&, const int*, hipStream_t);
+template void issue_values<float>(const ValLaunch&, const ValArgs<float>&, const ValTrans&, const int*, hipStream_t);
 
 }  // namespace mhs

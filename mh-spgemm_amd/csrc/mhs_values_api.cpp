@@ -5,8 +5,10 @@
 //   1 the three row_ptr arrays -> 2 A's and C's columns -> 3 classify and verify (3m, a mask: B's
 //   columns, B^T, classify, count the kept products) -> one read-back of counters and status
 // on the context's stream, each check read back before the next step indexes through what it checked.
-// A hot call (mhs_spgemm_values, mhs_spgemm_values_grad) is its argument checks and run_values: the
-// plan's launch list issued on the context's stream, timed by the plan's event pair when asked.
+// A hot call (mhs_spgemm_values, mhs_spgemm_values_grad and their _f32 forms) is its argument checks and
+// run_values: the plan's launch list issued on the context's stream, timed by the plan's event pair when asked.
+// A plan has one value type (mhs_dtype), fixed at creation: its classes, lists and launch plans are computed
+// for that type's size, and a call of the other type is refused before any HIP call.
 // Kernels and launchers: mhs_values.hip, mhs_values_grad.hip (declared in mhs_valwalk.hpp); classes,
 // launch plans, counter block and status words: mhs_valplan.hpp.
 #include "mhs_ctx.hpp"
@@ -22,6 +24,7 @@ using namespace mhs;
 // mhs_ctx_trim on the same context leave it alone.
 struct mhs_values_plan {
     int device = 0;
+    int dtype = MHS_F64;    // mhs_dtype: the type of every value array of its calls
     ValPattern pat{};
     long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
     long long kept = 0;    // products that land in C's pattern (masked plans count them; else = products)
@@ -40,6 +43,14 @@ struct mhs_values_plan {
 };
 
 namespace {
+
+constexpr int dtype_bytes(int dtype) { return dtype == MHS_F32 ? VAL_VB_F32 : VAL_VB_F64; }
+const char* dtype_name(int dtype) { return dtype == MHS_F32 ? "FP32" : "FP64"; }
+template <class V>
+constexpr int dtype_of() {
+    static_assert(sizeof(V) == VAL_VB_F64 || sizeof(V) == VAL_VB_F32, "double or float");
+    return sizeof(V) == VAL_VB_F32 ? MHS_F32 : MHS_F64;
+}
 
 static_assert((int)MHS_MASK_AUTO == (int)VM_AUTO && (int)MHS_MASK_PRODUCT == (int)VM_PRODUCT && (int)MHS_MASK_DOT == (int)VM_DOT,
               "mhs_mask_form is ValMaskForm");
@@ -122,7 +133,7 @@ struct PlanBuild {
     }
     // 3. classes, lists, and every product's column looked up in its C row
     void classify_and_verify() {
-        launch_val_classify(p->pat, d_cnt, p->lists, s);
+        launch_val_classify(p->pat, dtype_bytes(p->dtype), d_cnt, p->lists, s);
         launch_val_verify(p->pat, d_status + VS_PRODUCTS, s);
     }
     // 3m. a mask: B^T's pattern for the dot class (its sort indexes by B's columns: checked first; its scratch
@@ -153,7 +164,8 @@ struct PlanBuild {
             if (const int rc = hip(e, "mhs_values_plan_create: B^T")) return rc;
             p->trans = ValTrans{tptr, trow, tperm};
         }
-        launch_val_classify_masked(p->pat, ValMask{p->trans.tptr, form, val_dot_ratio()}, d_cnt, p->lists, s);
+        launch_val_classify_masked(p->pat, ValMask{p->trans.tptr, form, val_dot_ratio()}, dtype_bytes(p->dtype), d_cnt, p->lists,
+                                   s);
         launch_val_count_kept(p->pat, d_cnt, s);
         return MHS_OK;
     }
@@ -181,19 +193,21 @@ struct PlanBuild {
             p->tmem_bytes = 0;
             p->trans = ValTrans{};
         }
-        p->plan = plan_values(p->counts);
-        p->gplan = plan_grad(p->counts);
+        p->plan = plan_values(p->counts, dtype_bytes(p->dtype));
+        p->gplan = plan_grad(p->counts, dtype_bytes(p->dtype));
         return MHS_OK;
     }
 };
 
 // mhs_values_plan_create (masked false: C must contain the product's pattern) and
-// mhs_values_plan_create_masked (C is a mask; form: mhs_mask_form).
-int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form,
+// mhs_values_plan_create_masked (C is a mask; form: mhs_mask_form), for values of `dtype` (mhs_dtype).
+int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form, int dtype,
                        mhs_values_plan** out) {
     if (!ctx) return MHS_ERR_INVALID;
     if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
     *out = nullptr;
+    if (dtype != MHS_F64 && dtype != MHS_F32)
+        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: dtype is not an mhs_dtype (MHS_F64 or MHS_F32)");
     if (masked && (form < MHS_MASK_AUTO || form > MHS_MASK_DOT))
         return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: form is not an mhs_mask_form");
     if (A->M < 0 || A->N < 0 || A->nnz < 0 || B->M < 0 || B->N < 0 || B->nnz < 0 || C->M < 0 || C->N < 0 || C->nnz < 0)
@@ -207,6 +221,7 @@ int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const m
     MHS_HIP(hipSetDevice(ctx->device));
     mhs_values_plan* p = new mhs_values_plan();
     p->device = ctx->device;
+    p->dtype = dtype;
     p->pat = ValPattern{A->M, A->ptr, A->col, B->ptr, B->col, C->ptr, C->col};
     p->nnzA = A->nnz, p->nnzB = B->nnz, p->nnzC = C->nnz;
     Scratch sort_tmp;  // (B^T's sort scratch: it outlives the build's last step, which syncs the stream either way)
@@ -251,15 +266,75 @@ int run_values(mhs_ctx* ctx, mhs_values_plan* p, const ValPlan& plan, double* ms
     return MHS_OK;
 }
 
+// Whether a call on values of V may run on the plan: its type is the plan's
+template <class V>
+int check_dtype(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
+    if (p->dtype == dtype_of<V>()) return MHS_OK;
+    return fail(ctx, MHS_ERR_INVALID,
+                std::string(call) + ": the plan's values are " + dtype_name(p->dtype) + ", the call's " + dtype_name(dtype_of<V>()) +
+                    " (the value type is fixed at plan creation: mhs_values_plan_create_typed)");
+}
+
+// mhs_spgemm_values and mhs_spgemm_values_f32
+template <class V>
+int spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V* Bval, V* Cval, double* ms, const char* call) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
+    if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if ((p->nnzA > 0 && !Aval) || (p->nnzB > 0 && !Bval) || (p->nnzC > 0 && !Cval))
+        return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null value array");
+    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
+    const ValArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, Cval}};
+    return run_values(
+        ctx, p, p->plan, ms, [](hipStream_t) { return MHS_OK; },
+        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values(l, a, p->trans, list, s); });
+}
+
+// mhs_spgemm_values_grad and mhs_spgemm_values_grad_f32
+template <class V>
+int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V* Bval, const V* dCval, V* dAval, V* dBval,
+                       double* ms, const char* call) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
+    if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (!dCval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null dCval");
+    if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": no output (dAval and dBval are both null)");
+    if ((dAval && !Bval) || (dBval && !Aval))
+        return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": dAval needs Bval, dBval needs Aval");
+    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
+    const ValGradArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, dCval},
+                           dAval, dBval};
+    return run_values(
+        ctx, p, p->gplan, ms,
+        [&](hipStream_t s) {
+            // dB is summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
+            if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(V) * (size_t)p->nnzA, s));
+            if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(V) * (size_t)p->nnzB, s));
+            return (int)MHS_OK;
+        },
+        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_grad(l, a, list, s); });
+}
+
 }  // namespace
 
 int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, out);
+    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, out);
 }
 
 int mhs_values_plan_create_masked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int form,
                                   mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, true, form, out);
+    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, out);
+}
+
+int mhs_values_plan_create_typed(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
+                                 int dtype, mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, out);
+}
+
+int mhs_values_plan_dtype(const mhs_values_plan* p, int* dtype) {
+    if (!p || !dtype) return MHS_ERR_INVALID;
+    *dtype = p->dtype;
+    return MHS_OK;
 }
 
 int mhs_values_plan_kept(const mhs_values_plan* p, int64_t* kept_products) {
@@ -269,37 +344,21 @@ int mhs_values_plan_kept(const mhs_values_plan* p, int64_t* kept_products) {
 }
 
 int mhs_spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, double* Cval, double* ms) {
-    if (!ctx) return MHS_ERR_INVALID;
-    if (!p) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: null plan");
-    if ((p->nnzA > 0 && !Aval) || (p->nnzB > 0 && !Bval) || (p->nnzC > 0 && !Cval))
-        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: null value array");
-    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values: the plan belongs to another device");
-    const ValArgs a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, Cval}};
-    return run_values(
-        ctx, p, p->plan, ms, [](hipStream_t) { return MHS_OK; },
-        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values(l, a, p->trans, list, s); });
+    return spgemm_values<double>(ctx, p, Aval, Bval, Cval, ms, "mhs_spgemm_values");
+}
+
+int mhs_spgemm_values_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, float* Cval, double* ms) {
+    return spgemm_values<float>(ctx, p, Aval, Bval, Cval, ms, "mhs_spgemm_values_f32");
 }
 
 int mhs_spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* dCval,
                            double* dAval, double* dBval, double* ms) {
-    if (!ctx) return MHS_ERR_INVALID;
-    if (!p) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: null plan");
-    if (!dCval) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: null dCval");
-    if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: no output (dAval and dBval are both null)");
-    if ((dAval && !Bval) || (dBval && !Aval))
-        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: dAval needs Bval, dBval needs Aval");
-    if (p->device != ctx->device)
-        return fail(ctx, MHS_ERR_INVALID, "mhs_spgemm_values_grad: the plan belongs to another device");
-    const ValGradArgs a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, dCval}, dAval, dBval};
-    return run_values(
-        ctx, p, p->gplan, ms,
-        [&](hipStream_t s) {
-            // dB is summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
-            if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(double) * (size_t)p->nnzA, s));
-            if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(double) * (size_t)p->nnzB, s));
-            return (int)MHS_OK;
-        },
-        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_grad(l, a, list, s); });
+    return spgemm_values_grad<double>(ctx, p, Aval, Bval, dCval, dAval, dBval, ms, "mhs_spgemm_values_grad");
+}
+
+int mhs_spgemm_values_grad_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, const float* dCval,
+                               float* dAval, float* dBval, double* ms) {
+    return spgemm_values_grad<float>(ctx, p, Aval, Bval, dCval, dAval, dBval, ms, "mhs_spgemm_values_grad_f32");
 }
 
 int mhs_values_plan_info(const mhs_values_plan* p, mhs_values_info* info) {

@@ -19,20 +19,26 @@ struct ValPattern {
     const int *Aptr, *Acol, *Bptr, *Bcol, *Cptr, *Ccol;
 };
 // ... and what a hot call's kernels take: each matrix as its pattern and the call's value array for it.
+// V is the plan's value type, double or float: the type of every value array, of the LDS sums and of the
+// atomics of a call.
 template <class V>
 struct ValCsr {
     const int *ptr, *col;
     V* val;
 };
+template <class V>
 struct ValArgs {
-    ValCsr<const double> A, B;
-    ValCsr<double> C;
+    using Value = V;
+    ValCsr<const V> A, B;
+    ValCsr<V> C;
 };
 // The backward's (mhs_spgemm_values_grad).  C.val is G, the cotangent on C's pattern; dA / dB: the gradients,
 // zero-filled by the caller, either nullptr (that side is not computed, and B.val / A.val is then not read).
+template <class V>
 struct ValGradArgs {
-    ValCsr<const double> A, B, C;
-    double *dA, *dB;
+    using Value = V;
+    ValCsr<const V> A, B, C;
+    V *dA, *dB;
 };
 // A masked plan's B^T pattern (transpose_pattern of B), read by the dot class only; tptr null: none
 struct ValTrans {
@@ -47,17 +53,20 @@ struct ValMask {
 void launch_val_check_ptr(const int* ptr, int M, int nnz, int* bad, hipStream_t s);
 void launch_val_check_cols(const int* ptr, const int* col, int M, int ncols, bool strict, int* bad, hipStream_t s);
 // cnt: the counter block of mhs_valplan.hpp (VAL_CNT_INTS ints), zeroed by the caller; lists: M ints,
-// class c's rows at the prefix of the counts before it
-void launch_val_classify(const ValPattern& p, int* cnt, int* lists, hipStream_t s);
+// class c's rows at the prefix of the counts before it; vb: the bytes of the plan's value type
+void launch_val_classify(const ValPattern& p, int vb, int* cnt, int* lists, hipStream_t s);
 void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s);
 // Masked plans: the same two classify passes by val_class_masked, and in place of the verify walk a
 // count of the products that land in the mask, into the counter block's kept count
-void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int* cnt, int* lists, hipStream_t s);
+void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int vb, int* cnt, int* lists, hipStream_t s);
 void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s);
 // One launch of a values plan (plan_values) over its class's row list, on `s` (t: read by VK_DOT only).
-void issue_values(const ValLaunch& l, const ValArgs& a, const ValTrans& t, const int* list, hipStream_t s);
-// One launch of a values plan's backward (plan_grad) over its class's row list, on `s`.
-void issue_values_grad(const ValLaunch& l, const ValGradArgs& a, const int* list, hipStream_t s);
+// V (double or float, both instantiated in mhs_values.hip) must be the type the plan was classified for.
+template <class V>
+void issue_values(const ValLaunch& l, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s);
+// One launch of a values plan's backward (plan_grad) over its class's row list, on `s` (mhs_values_grad.hip).
+template <class V>
+void issue_values_grad(const ValLaunch& l, const ValGradArgs<V>& a, const int* list, hipStream_t s);
 hipError_t init_values_grad_attributes();  // (called by init_values_attributes)
 
 // -------------------------------------------------------- device helpers ---
@@ -100,31 +109,35 @@ static __device__ __forceinline__ XcdStretch xcd_stretch(int count) {
     return {lo + first, hi, step};
 }
 
-// The row frame of the LDS classes.  A row's LDS slice is `region` bytes: span-indexed FP64 (direct), or
-// region / 12 FP64 and as many columns behind them (search).  The guards below are all that stands
-// between a pattern that is not the plan's and an overrun of the slice: such a row is left alone.
+// The row frame of the LDS classes.  A row's LDS slice is `region` bytes: span-indexed sums of V (direct), or
+// val_slice_entries sums and as many columns behind them (search).  The guards -- val_slice_entries and
+// val_slice_fits of mhs_valplan.hpp, at sizeof(V) -- are all that stands between a pattern that is not the
+// plan's and an overrun of the slice: such a row is left alone.
+template <class V>
 struct ValSlice {
-    double* val;
+    V* val;
     int* cols;  // (search)
     int ne;     // entries the slice holds (search)
 };
-static __device__ __forceinline__ ValSlice search_slice(char* base, int region) {
-    const int ne = region / 12;
-    return {(double*)base, (int*)((double*)base + ne), ne};
+template <class V>
+static __device__ __forceinline__ ValSlice<V> search_slice(char* base, int region) {
+    const int ne = val_slice_entries(region, (int)sizeof(V));
+    return {(V*)base, (int*)((V*)base + ne), ne};
 }
 // A wave's or a block's row: body(s, n, first, span, val, cols) for C's segment [s, s + n) of `row`,
 // when it has entries and fits (direct: columns first .. first + span - 1; search: first = span = 0).
 template <bool DIRECT, class Args, class Body>
 __device__ __forceinline__ void val_row(const Args& p, int row, char* base, int region, Body body) {
+    using V = typename Args::Value;
     const int s = p.C.ptr[row], n = p.C.ptr[row + 1] - s;
     if (n <= 0) return;
     if constexpr (DIRECT) {
         const int first = p.C.col[s];
         const long long span = (long long)p.C.col[s + n - 1] - first + 1;
-        if (span <= 0 || span * 8 > region) return;
-        body(s, n, first, (int)span, (double*)base, (int*)nullptr);
+        if (!val_slice_fits(span, region, (int)sizeof(V))) return;
+        body(s, n, first, (int)span, (V*)base, (int*)nullptr);
     } else {
-        const ValSlice sl = search_slice(base, region);
+        const ValSlice<V> sl = search_slice<V>(base, region);
         if (n > sl.ne) return;
         body(s, n, 0, 0, sl.val, sl.cols);
     }
@@ -143,12 +156,15 @@ __device__ __forceinline__ int val_team_row(const Args& p, const int* list, int 
 }
 
 // Up to CH staged A entries of a row as (B row start, length, A value); entry e of the stage that
-// began at A position k0 is A entry k0 + e.
-template <int CH>
+// began at A position k0 is A entry k0 + e.  16 B an entry in FP64, 12 B in FP32.
+template <int CH, class V>
 struct ValStage {
     int bs[CH], len[CH];
-    double av[CH];
+    V av[CH];
 };
+static_assert(sizeof(ValStage<VAL_STAGE, double>) <= VAL_STAGE_BYTES && sizeof(ValStage<VAL_STAGE, float>) <= VAL_STAGE_BYTES &&
+                  sizeof(ValStage<64, double>) <= 1024 && sizeof(ValStage<64, float>) <= 1024,
+              "the stage: VAL_STAGE_BYTES per block, 1 KiB per wave");
 constexpr int VAL_PIECES = 8;  // G-wide pieces of a B row a lane group loads before its first sum
 
 // ---------------------------------------------------------------- launch ---

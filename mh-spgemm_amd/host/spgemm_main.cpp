@@ -1,7 +1,7 @@
 // spgemm_main.cpp -- the `spgemm <file.mtx>` driver (reference src/main.cu:74-217)
 // on top of the C-ABI, printing the reference's stdout lines.
 //
-//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] <file.mtx>
+//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -27,6 +27,13 @@
 //             cotangent G on it, N values calls and N backward calls (mhs_spgemm_values_grad, both
 //             gradients); the two median times on a line of its own, and with --check the adjoint
 //             identities <G, C> = <dA, Aval> = <dB, Bval> (the product is bilinear) on host-computed sums
+//   --f32     a modifier of --reuse, --masked and --grad: after them, each chosen mode once more with an FP32
+//             plan (mhs_values_plan_create_typed, MHS_F32) on the operands' values rounded to float, N calls
+//             of mhs_spgemm_values_f32 / mhs_spgemm_values_grad_f32 beside N calls of an FP64 plan on the
+//             same rounded values: one more line per mode with both times, and with --check every FP32
+//             entry against the FP64 call's: within 1.01 m 2^-24 S for an entry of m kept products whose
+//             absolute values sum to S (m and S from FP64 calls on all-ones and on absolute values), and
+//             exactly 0 where m = 0.  Without --f32 nothing is added to the output.
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -167,9 +174,102 @@ static void run_grad(Tool& tools, const CSR& A, const CSR& B, CSR& C, int calls,
     (void)hipFree(dB);
 }
 
+// ---- --f32: the values modes once more on float values, beside an FP64 plan on the same rounded values
+template <class T>
+struct DevArr {  // a device array of n entries (at least one allocated)
+    T* p = nullptr;
+    size_t n;
+    explicit DevArr(size_t n_) : n(n_) { mhs_shim::hip_check(hipMalloc((void**)&p, sizeof(T) * (n ? n : 1)), "hipMalloc (--f32)"); }
+    DevArr(const DevArr&) = delete;
+    DevArr& operator=(const DevArr&) = delete;
+    ~DevArr() { (void)hipFree(p); }
+    void put(const std::vector<T>& v) { mhs_shim::hip_check(hipMemcpy(p, v.data(), sizeof(T) * n, hipMemcpyHostToDevice), "H2D (--f32)"); }
+    std::vector<T> get() const {
+        std::vector<T> v(n ? n : 1);
+        mhs_shim::hip_check(hipMemcpy(v.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost), "D2H (--f32)");
+        v.resize(n);
+        return v;
+    }
+};
+
+static void f32_ok(mhs_ctx* ctx, int rc) {
+    if (rc != MHS_OK) throw std::runtime_error(mhs_last_error(ctx));
+}
+
+// |got - ref| <= 1.01 m 2^-24 S per entry, exactly 0 where m = 0, no NaN (m, S: the FP64 call on ones / on absolute values)
+static bool f32_within(const std::vector<float>& got, const std::vector<double>& ref, const std::vector<double>& m,
+                       const std::vector<double>& S) {
+    for (size_t i = 0; i < got.size(); ++i) {
+        const double mm = std::floor(m[i] + 0.5), d = std::fabs((double)got[i] - ref[i]);
+        if (mm == 0 ? got[i] != 0.0f : !(d <= 1.01 * mm * 5.9604644775390625e-8 * S[i])) return false;
+    }
+    return true;
+}
+
+// One mode: plans of both types for A * B on P's pattern (masked: a mask), `calls` calls of each -- the values
+// call, or (backward) the backward call with both gradients on a seeded cotangent -- and the check.
+static void run_f32(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool masked, bool backward, int calls, bool check,
+                    const char* label, const char* tag) {
+    try {
+        const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)P.nnz;
+        auto rounded = [](const double* v, size_t n) {
+            std::vector<float> f(n);
+            for (size_t i = 0; i < n; ++i) f[i] = (float)v[i];
+            return f;
+        };
+        std::vector<double> G(nC);
+        unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
+        for (size_t s = 0; s < nC; ++s) {
+            state = state * 6364136223846793005ULL + 1442695040888963407ULL;
+            G[s] = 0.1 + 0.9 * (double)(state >> 11) / 9007199254740992.0;
+        }
+        const std::vector<float> a32 = rounded(A.val, nA), b32 = rounded(B.val, nB), g32 = rounded(G.data(), nC);
+        mhs_shim::ValuesPlan p32(tools, A, B, P, masked, MHS_MASK_AUTO, MHS_F32), p64(tools, A, B, P, masked, MHS_MASK_AUTO, MHS_F64);
+        DevArr<float> fa(nA), fb(nB), fg(nC), fc(nC), fda(nA), fdb(nB);
+        DevArr<double> da(nA), db(nB), dg(nC), dc(nC), dda(nA), ddb(nB);
+        fa.put(a32), fb.put(b32), fg.put(g32);
+        // the FP64 call on values made of the rounded ones by f: what it returns, per output
+        struct Out {
+            std::vector<double> c, a, b;
+        };
+        auto call64 = [&](double (*f)(float), double* ms) {
+            std::vector<double> va(nA), vb(nB), vg(nC);
+            for (size_t i = 0; i < nA; ++i) va[i] = f(a32[i]);
+            for (size_t i = 0; i < nB; ++i) vb[i] = f(b32[i]);
+            for (size_t i = 0; i < nC; ++i) vg[i] = f(g32[i]);
+            da.put(va), db.put(vb), dg.put(vg);
+            if (backward) f32_ok(p64.ctx, mhs_spgemm_values_grad(p64.ctx, p64.plan, da.p, db.p, dg.p, dda.p, ddb.p, ms));
+            else f32_ok(p64.ctx, mhs_spgemm_values(p64.ctx, p64.plan, da.p, db.p, dc.p, ms));
+            return backward ? Out{{}, dda.get(), ddb.get()} : Out{dc.get(), {}, {}};
+        };
+        std::vector<double> t32, t64;
+        Out ref;
+        for (int i = 0; i < calls; ++i) {
+            if (backward) MH_spgemm_values_grad(fa.p, fb.p, fg.p, fda.p, fdb.p, p32);
+            else MH_spgemm_values(fa.p, fb.p, fc.p, p32);
+            t32.push_back(p32.last_ms);
+        }
+        for (int i = 0; i < calls; ++i) {
+            double ms = 0;
+            ref = call64([](float x) { return (double)x; }, &ms);
+            t64.push_back(ms);
+        }
+        std::printf("MH-SpGEMM %s FP32 median of %d calls is %.3lf ms, FP64 on the same rounded values %.3lf ms\n", label, calls,
+                    median(t32), median(t64));
+        if (check) {
+            const Out m = call64([](float) { return 1.0; }, nullptr), S = call64([](float x) { return std::fabs((double)x); }, nullptr);
+            const bool ok = backward ? f32_within(fda.get(), ref.a, m.a, S.a) && f32_within(fdb.get(), ref.b, m.b, S.b)
+                                     : f32_within(fc.get(), ref.c, m.c, S.c);
+            std::printf("%s f32 %s\n", tag, ok ? "pass" : "error");
+        }
+    } catch (const std::exception&) {
+        std::printf("%s f32 error\n", tag);
+    }
+}
+
 int main(int argc, char** argv) {
     int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0;
-    bool aat = false, vendor = false, check = false, cache = false;
+    bool aat = false, vendor = false, check = false, cache = false, f32 = false;
     std::string csv;
     const char* filename = nullptr;
     bool bad = false;
@@ -184,12 +284,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--reuse") && i + 1 < argc) reuse = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--grad") && i + 1 < argc) grad = std::atoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--f32")) f32 = true;
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
     if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0 || grad < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -301,6 +402,17 @@ int main(int argc, char** argv) {
         if (masked > 0 && A.M != A.N) std::puts("masked: A's pattern as the mask must have rowA = colA. Skipped.");
         else if (masked > 0) run_masked(tools, A, B, C, masked, check);
         if (grad > 0) run_grad(tools, A, B, C, grad, check);
+        if (f32) {
+            if (reuse > 0) run_f32(tools, A, B, C, false, false, reuse, check, "values-only (pattern reused)", "values");
+            if (masked > 0 && A.M == A.N) {
+                CSR mask;  // A's pattern, borrowed (a plan reads no values)
+                mask.M = A.M, mask.N = B.N, mask.nnz = A.nnz;
+                mask.d_ptr = A.d_ptr, mask.d_col = A.d_col;
+                run_f32(tools, A, B, mask, true, false, masked, check, "masked (A's pattern)", "masked");
+                mask.d_ptr = mask.d_col = nullptr;  // A's
+            }
+            if (grad > 0) run_f32(tools, A, B, C, false, true, grad, check, "values backward (both gradients)", "grad");
+        }
         C.d_release_csr();
     } catch (const std::exception&) {
         std::printf("MH-SpGEMM failed!!!\n");

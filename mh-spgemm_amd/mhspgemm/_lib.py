@@ -32,6 +32,9 @@ MHS_OPT_GROUP_GRID = 6
 MHS_MASK_AUTO = 0
 MHS_MASK_PRODUCT = 1
 MHS_MASK_DOT = 2
+# mhs_dtype: the value type of a values plan
+MHS_F64 = 0
+MHS_F32 = 1
 
 STATUS_NAMES = {0: "MHS_OK", 1: "MHS_ERR_HIP", 2: "MHS_ERR_OOM", 3: "MHS_ERR_INVALID",
                 4: "MHS_ERR_OVERFLOW", 5: "MHS_ERR_IO"}
@@ -162,6 +165,17 @@ def lib() -> ctypes.CDLL:
             L.mhs_spgemm_values_grad.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                  P(ctypes.c_double)]
             L.mhs_spgemm_values_grad.restype = c_int
+        if hasattr(L, "mhs_values_plan_create_typed"):  # (FP32 values plans: a later addition to ABI 10)
+            L.mhs_values_plan_create_typed.argtypes = [c_void_p, P(mhs_csr), P(mhs_csr), P(mhs_csr), c_int, c_int, c_int,
+                                                       P(c_void_p)]
+            L.mhs_values_plan_create_typed.restype = c_int
+            L.mhs_values_plan_dtype.argtypes = [c_void_p, P(c_int)]
+            L.mhs_values_plan_dtype.restype = c_int
+            L.mhs_spgemm_values_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(ctypes.c_double)]
+            L.mhs_spgemm_values_f32.restype = c_int
+            L.mhs_spgemm_values_grad_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     P(ctypes.c_double)]
+            L.mhs_spgemm_values_grad_f32.restype = c_int
     if hasattr(L, "mhs_ctx_fence_default_stream"):  # (a later addition to ABI 10)
         L.mhs_ctx_fence_default_stream.argtypes = [c_void_p, c_int]
         L.mhs_ctx_fence_default_stream.restype = c_int

@@ -369,6 +369,16 @@ def spgemm(tool: Tool, A: CSR, B: CSR, timing: bool = True):
 
 VALUES_CLASSES = ("none", "team", "wave_direct", "wave_search", "block_direct", "block_search", "global", "dot")
 MASK_FORMS = {"auto": L.MHS_MASK_AUTO, "product": L.MHS_MASK_PRODUCT, "dot": L.MHS_MASK_DOT}
+VALUES_DTYPES = {"float64": L.MHS_F64, "float32": L.MHS_F32}
+
+
+def values_dtype_name(dtype) -> str:
+    """``"float64"`` or ``"float32"`` for a values plan's ``dtype`` argument: one of those names (also ``"f64"`` /
+    ``"f32"``) or the torch dtype.  ValueError for anything else."""
+    name = {"f64": "float64", "f32": "float32"}.get(dtype, dtype) if isinstance(dtype, str) else str(dtype).replace("torch.", "")
+    if name not in VALUES_DTYPES:
+        raise ValueError(f"dtype: torch.float64 or torch.float32 (or their names), not {dtype!r}")
+    return name
 
 
 class ValuesPlan:
@@ -388,13 +398,22 @@ class ValuesPlan:
     or ``"auto"`` (per row, the cheaper).  An integer ``form`` is passed to the library as it is.
 
     ``grad`` is the backward of ``run`` on the same plan (mhs_spgemm_values_grad) and ``apply`` the pair as a
-    ``torch.autograd.Function``, for products inside a differentiable program."""
+    ``torch.autograd.Function``, for products inside a differentiable program.
 
-    def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto"):
+    ``dtype`` (``torch.float64``, the default, or ``torch.float32``; also by name) is the plan's value type,
+    fixed at creation (mhs_values_plan_create_typed): rows are classified for its size, every tensor of
+    ``run``, ``grad`` and ``apply`` must have it (``ValueError`` otherwise) and outputs are allocated in it.
+    On a float32 plan ``Aval`` and ``Bval`` must be given: the operands' own ``d_val`` is FP64."""
+
+    def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto", dtype="float64"):
         if not hasattr(L.lib(), "mhs_values_plan_create"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no values-only entry points")
         if masked and not hasattr(L.lib(), "mhs_values_plan_create_masked"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no masked entry points")
+        self.dtype_name = values_dtype_name(dtype)
+        self.f32 = self.dtype_name == "float32"
+        if self.f32 and not hasattr(L.lib(), "mhs_values_plan_create_typed"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no FP32 values entry points")
         if isinstance(form, str):
             if form not in MASK_FORMS:
                 raise ValueError(f"form: one of {sorted(MASK_FORMS)}, not {form!r}")
@@ -410,7 +429,11 @@ class ValuesPlan:
         self.nnzA, self.nnzB, self.nnzC = int(a.nnz), int(b.nnz), int(c.nnz)
         self.plan = ctypes.c_void_p()
         self._pad = None
-        if masked:
+        if self.f32:
+            rc = L.lib().mhs_values_plan_create_typed(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                      int(self.masked), self.form, L.MHS_F32, ctypes.byref(self.plan))
+            _check(tool.ctx, rc, "mhs_values_plan_create_typed")
+        elif masked:
             rc = L.lib().mhs_values_plan_create_masked(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
                                                        self.form, ctypes.byref(self.plan))
             _check(tool.ctx, rc, "mhs_values_plan_create_masked")
@@ -419,29 +442,46 @@ class ValuesPlan:
                                                 ctypes.byref(self.plan))
             _check(tool.ctx, rc, "mhs_values_plan_create")
 
-    @staticmethod
-    def _ptr(t, n, what):
+    @property
+    def dtype(self):
+        """The plan's value type as a torch dtype."""
+        return getattr(_torch(), self.dtype_name)
+
+    def _ptr(self, t, n, what):
         if t is None:
             return None
         torch = _torch()
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == self.dtype and t.is_contiguous()
                 and t.numel() == n):
-            raise ValueError(f"{what}: needs a contiguous float64 device tensor of {n} entries")
+            got = f" (got {t.dtype})" if isinstance(t, torch.Tensor) and t.dtype != self.dtype else ""
+            raise ValueError(f"{what}: a {self.dtype_name} plan needs a contiguous {self.dtype_name} device tensor of {n} "
+                             f"entries{got}")
         return t.data_ptr() if n else None
 
+    def _own(self, X, given, n, what):
+        """The value pointer of an operand: the tensor given, or (FP64 plans) the operand's own ``d_val``."""
+        if given is not None:
+            return self._ptr(given, n, what)
+        if self.f32:
+            raise ValueError(f"{what}: a float32 plan needs the values as a tensor (the operand's own d_val is float64)")
+        return X.c_view().val
+
     def run(self, Aval=None, Bval=None, out=None, timed: bool = False):
-        """C's values of A*B for the values ``Aval`` / ``Bval`` (torch FP64 device tensors of
-        nnz(A) / nnz(B) entries; default: the operands' own ``d_val``) into ``out`` (nnz(C)
-        entries; default: C's own ``val``).  Returns the call's hipEvent time in ms when
+        """C's values of A*B for the values ``Aval`` / ``Bval`` (torch device tensors of the plan's dtype,
+        nnz(A) / nnz(B) entries; default, FP64 plans only: the operands' own ``d_val``) into ``out`` (nnz(C)
+        entries; default, FP64 plans only: C's own ``val``).  Returns the call's hipEvent time in ms when
         ``timed``, else None (the call then follows MHS_OPT_SYNC)."""
         if not self.plan:
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "ValuesPlan.run: the plan is closed")
-        av = self.A.c_view().val if Aval is None else self._ptr(Aval, self.nnzA, "Aval")
-        bv = self.B.c_view().val if Bval is None else self._ptr(Bval, self.nnzB, "Bval")
+        av = self._own(self.A, Aval, self.nnzA, "Aval")
+        bv = self._own(self.B, Bval, self.nnzB, "Bval")
+        if out is None and self.f32:
+            raise ValueError("out: a float32 plan needs an output tensor (C's own val is float64)")
         cv = self._c.val if out is None else self._ptr(out, self.nnzC, "out")
         ms = ctypes.c_double(0.0)
-        rc = L.lib().mhs_spgemm_values(self.tool.ctx, self.plan, av, bv, cv, ctypes.byref(ms) if timed else None)
-        _check(self.tool.ctx, rc, "mhs_spgemm_values")
+        call = L.lib().mhs_spgemm_values_f32 if self.f32 else L.lib().mhs_spgemm_values
+        rc = call(self.tool.ctx, self.plan, av, bv, cv, ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, "mhs_spgemm_values_f32" if self.f32 else "mhs_spgemm_values")
         return float(ms.value) if timed else None
 
     def grad(self, dC, Aval=None, Bval=None, need_A: bool = True, need_B: bool = True, out_A=None, out_B=None,
@@ -463,22 +503,22 @@ class ValuesPlan:
         gp = self._ptr(dC, self.nnzC, "dC")
         # (an empty array has no address; the library wants one for every array it is given: nothing reads it)
         if self._pad is None:
-            self._pad = torch.zeros(1, dtype=torch.float64, device=dev)
+            self._pad = torch.zeros(1, dtype=self.dtype, device=dev)
         pad = self._pad.data_ptr()
         av = bv = pa = pb = None
         dA = dB = None
         if need_A:
-            bv = (self.B.c_view().val if Bval is None else self._ptr(Bval, self.nnzB, "Bval")) or pad
-            dA = torch.empty(self.nnzA, dtype=torch.float64, device=dev) if out_A is None else out_A
+            bv = self._own(self.B, Bval, self.nnzB, "Bval") or pad
+            dA = torch.empty(self.nnzA, dtype=self.dtype, device=dev) if out_A is None else out_A
             pa = self._ptr(dA, self.nnzA, "out_A") or pad
         if need_B:
-            av = (self.A.c_view().val if Aval is None else self._ptr(Aval, self.nnzA, "Aval")) or pad
-            dB = torch.empty(self.nnzB, dtype=torch.float64, device=dev) if out_B is None else out_B
+            av = self._own(self.A, Aval, self.nnzA, "Aval") or pad
+            dB = torch.empty(self.nnzB, dtype=self.dtype, device=dev) if out_B is None else out_B
             pb = self._ptr(dB, self.nnzB, "out_B") or pad
         ms = ctypes.c_double(0.0)
-        rc = L.lib().mhs_spgemm_values_grad(self.tool.ctx, self.plan, av, bv, gp or pad, pa, pb,
-                                            ctypes.byref(ms) if timed else None)
-        _check(self.tool.ctx, rc, "mhs_spgemm_values_grad")
+        call = L.lib().mhs_spgemm_values_grad_f32 if self.f32 else L.lib().mhs_spgemm_values_grad
+        rc = call(self.tool.ctx, self.plan, av, bv, gp or pad, pa, pb, ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, "mhs_spgemm_values_grad_f32" if self.f32 else "mhs_spgemm_values_grad")
         return (dA, dB, float(ms.value)) if timed else (dA, dB)
 
     def apply(self, Aval, Bval):
@@ -505,7 +545,8 @@ class ValuesPlan:
 
     def info(self) -> dict:
         """Rows per class (by name and as the ``rows`` list indexed by class id), products, nnzC, plan_bytes,
-        and kept_products: the products that land in C's pattern (all of them unless the plan is masked)."""
+        kept_products: the products that land in C's pattern (all of them unless the plan is masked), and dtype:
+        the plan's value type by name (as the library reports it)."""
         i = L.mhs_values_info()
         _check(self.tool.ctx, L.lib().mhs_values_plan_info(self.plan, ctypes.byref(i)), "mhs_values_plan_info")
         rows = [int(x) for x in i.rows]
@@ -516,6 +557,11 @@ class ValuesPlan:
             kept = ctypes.c_int64(0)
             _check(self.tool.ctx, L.lib().mhs_values_plan_kept(self.plan, ctypes.byref(kept)), "mhs_values_plan_kept")
             d["kept_products"] = int(kept.value)
+        d["dtype"] = "float64"
+        if hasattr(L.lib(), "mhs_values_plan_dtype"):
+            dt = ctypes.c_int(0)
+            _check(self.tool.ctx, L.lib().mhs_values_plan_dtype(self.plan, ctypes.byref(dt)), "mhs_values_plan_dtype")
+            d["dtype"] = {v: k for k, v in VALUES_DTYPES.items()}[int(dt.value)]
         return d
 
     def close(self):
@@ -545,7 +591,7 @@ def _values_function():
     class ValuesProduct(torch.autograd.Function):
         @staticmethod
         def forward(ctx, plan, Aval, Bval):
-            out = torch.empty(plan.nnzC, dtype=torch.float64, device=f"cuda:{plan.tool.device}")
+            out = torch.empty(plan.nnzC, dtype=plan.dtype, device=f"cuda:{plan.tool.device}")
             plan._ordered_on_current_stream(lambda: plan.run(Aval, Bval, out=out))
             ctx.plan = plan
             ctx.save_for_backward(Aval, Bval)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """grad_bench.py -- the values backward against the values call on the same plan, one workload per run.
 
-    python tools/grad_bench.py [--workload cant|scircuit|triangle] [--blocks 5] [--window 0.4]
+    python tools/grad_bench.py [--workload cant|scircuit|triangle] [--blocks 5] [--window 0.4] [--dtype f32|f64]
 
 Workloads: `cant` and `scircuit` are A*A on the product's own pattern (the stand-ins of
 mhspgemm.synth unless the real matrices are present); `triangle` is L*L on L's pattern, a masked plan
@@ -17,6 +17,10 @@ synchronises; per kind the median of the blocks' per-call times and the spread m
 Before timing, every output is checked against the forward through the adjoint identity: with X, Y
 fresh positive values, <G, run(X, Bval)> = <grad_A, X> and <G, run(Aval, Y)> = <grad_B, Y> to 1e-9
 relative (the same terms summed in another order), for the one-sided calls and for the call with both.
+--dtype f32: an FP32 plan on float32 values.  The identities then hold to 2.02 m 2^-24 relative, m the most
+products any output entry sums (the values are positive, so each side is within m 2^-24 of the exact sum; m
+from an FP64 plan on all-ones values, B's longest row and A's fullest column); that plan's rows by class are
+reported as `classes_f64`, and the dB side's atomic bytes are 4 a product.
 Also reported: the dB side's atomic bytes per second, 8 * kept_products / the grad_B time, and
 `masked_alternative_products`: what the two gradients would walk as masked products of their own,
 dA = (G*B^T)<A>: the sum over C's entries (i, j) of len(B^T row j), and dB = (A^T*G)<B>: the sum over
@@ -58,7 +62,10 @@ def main():
     ap.add_argument("--blocks", type=int, default=5, help="timed blocks per kind")
     ap.add_argument("--window", type=float, default=0.4, help="seconds a timed block should last")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dtype", default="f64", choices=("f32", "f64"), help="the plan's value type")
     args = ap.parse_args()
+    f32 = args.dtype == "f32"
+    tdtype = torch.float32 if f32 else torch.float64
 
     dev = 0
     torch.cuda.set_device(dev)
@@ -77,15 +84,30 @@ def main():
         torch.cuda.synchronize(dev)
 
     out = {"workload": args.workload, "source": source, "M": A.M, "nnzA": A.nnz, "products": int(flop),
-           "blocks": args.blocks, "lib": lib_name()}
+           "blocks": args.blocks, "lib": lib_name(), "dtype": args.dtype}
+    kw = {"dtype": "float32"} if f32 else {}  # (an older library's wrapper has no dtype argument)
     if masked:
         C = mhspgemm.CSR(A.M, A.N, A.ptr, A.col, np.zeros(A.nnz))
         C.H2D(dev)
-        plan = mhspgemm.ValuesPlan(tool, A, A, C, masked=True, form="auto")
+        plan = mhspgemm.ValuesPlan(tool, A, A, C, masked=True, form="auto", **kw)
     else:
         C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
-        plan = mhspgemm.ValuesPlan(tool, A, A, C)
+        plan = mhspgemm.ValuesPlan(tool, A, A, C, **kw)
     info = plan.info()
+    tol = 1e-9
+    if f32:
+        plan64 = mhspgemm.ValuesPlan(tool, A, A, C, masked=True, form="auto") if masked else mhspgemm.ValuesPlan(tool, A, A, C)
+        i64 = plan64.info()
+        out["classes_f64"] = {k: i64[k] for k in mhspgemm.core.VALUES_CLASSES}
+        ones = torch.ones(A.nnz, dtype=torch.float64, device=device)
+        cnt = torch.empty(info["nnzC"], dtype=torch.float64, device=device)
+        torch.cuda.synchronize(dev)
+        plan64.run(ones, ones, out=cnt)
+        torch.cuda.synchronize(dev)
+        most = max(int(cnt.max().item()) if info["nnzC"] else 0, int(np.diff(A.ptr).max()), int(np.bincount(A.col).max()))
+        plan64.close()
+        tol = 2.02 * most * 2.0 ** -24
+        out["most_products_per_entry"] = most
     out.update({"nnzC": info["nnzC"], "kept_products": info["kept_products"], "plan_bytes": info["plan_bytes"],
                 "classes": {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}})
     Cp, Ci = (A.ptr, A.col) if masked else C.to_host()[:2]
@@ -97,17 +119,18 @@ def main():
           file=sys.stderr, flush=True)
 
     gen = torch.Generator(device=device).manual_seed(17)
-    rnd = lambda n: torch.rand(n, dtype=torch.float64, device=device, generator=gen) * 0.9 + 0.1  # noqa: E731
+    rnd = lambda n: (torch.rand(n, dtype=torch.float64, device=device, generator=gen) * 0.9 + 0.1).to(tdtype)  # noqa: E731
     av, bv, X, Y, G = rnd(A.nnz), rnd(A.nnz), rnd(A.nnz), rnd(A.nnz), rnd(info["nnzC"])
-    res_c = torch.empty(info["nnzC"], dtype=torch.float64, device=device)
-    gA, gB = (torch.full((A.nnz,), float("nan"), dtype=torch.float64, device=device) for _ in range(2))
+    res_c = torch.empty(info["nnzC"], dtype=tdtype, device=device)
+    gA, gB = (torch.full((A.nnz,), float("nan"), dtype=tdtype, device=device) for _ in range(2))
+    dot = lambda x, y: float((x.double() * y.double()).sum())  # noqa: E731
     sync()  # (torch's default stream has the handle 0: the tool runs on its own stream, ordered by device synchronises)
 
     # ---- the check: the adjoint identity against the forward, for every kind of call
     plan.run(X, bv, out=res_c)
-    lhs_a = float((G * res_c).sum())
+    lhs_a = dot(G, res_c)
     plan.run(av, Y, out=res_c)
-    lhs_b = float((G * res_c).sum())
+    lhs_b = dot(G, res_c)
     worst = 0.0
     for need_a, need_b in ((True, False), (False, True), (True, True)):
         gA.fill_(float("nan"))
@@ -119,8 +142,8 @@ def main():
             if not need:
                 continue
             assert not torch.isnan(g).any().item(), "an entry of a requested output was not written"
-            rel = abs(float((g * other).sum()) - lhs) / lhs
-            assert rel <= 1e-9, f"adjoint identity off by {rel:.3e} (need_A={need_a}, need_B={need_b})"
+            rel = abs(dot(g, other) - lhs) / lhs
+            assert rel <= tol, f"adjoint identity off by {rel:.3e} (need_A={need_a}, need_B={need_b})"
             worst = max(worst, rel)
     out["checked"] = f"adjoint identity against the forward, one-sided and two-sided calls: worst relative gap {worst:.2e}"
 
@@ -164,7 +187,7 @@ def main():
                      "blocks_ms": [round(x, 5) for x in r]}
     fwd = out["forward"]["ms_median"]
     out["over_forward"] = {k: round(out[k]["ms_median"] / fwd, 3) for k in ("grad_A", "grad_B", "grad_AB")}
-    out["grad_B_atomic_GBps"] = round(8.0 * info["kept_products"] / (out["grad_B"]["ms_median"] * 1e-3) / 1e9, 1)
+    out["grad_B_atomic_GBps"] = round((4.0 if f32 else 8.0) * info["kept_products"] / (out["grad_B"]["ms_median"] * 1e-3) / 1e9, 1)
     plan.close()
     if not masked:
         C.release()

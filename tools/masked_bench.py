@@ -2,6 +2,7 @@
 """masked_bench.py -- the masked product against the full call a user makes today, one workload per run.
 
     python tools/masked_bench.py [--workload triangle|cant|scircuit] [--blocks 5] [--window 0.4] [--full-only]
+                                [--dtype f32|f64]
 
 Workloads: `triangle` is L*L on L's pattern, L the strictly lower triangle of a symmetrised
 synth.powerlaw graph with all values 1.0; `cant` and `scircuit` are A*A on A's pattern.
@@ -14,6 +15,10 @@ synchronises; per kind the median of the blocks' per-call times and the spread m
   auto@R        the masked plan in AUTO with MHS_VAL_DOT_RATIO=R at its creation, R in 1 .. 64
 Before timing, every masked plan's output is checked against the full product filtered to the mask
 (the reference 1e-9 rule; mask entries outside the product exactly 0.0).
+
+--dtype f32 makes every masked plan an FP32 plan on A's values rounded to float.  The check is then against an
+FP64 masked plan (product form) on the same rounded values: every entry within 1.01 m 2^-24 S, m and S from that
+plan on all-ones and on absolute values, unreached entries exactly 0.0.
 
 --full-only times `full` alone and needs none of the masked entry points, so it runs against an
 older library (MHS_LIB=/path/to/libmhspgemm.so): the parent commit's, for the comparison the table
@@ -70,7 +75,9 @@ def main():
     ap.add_argument("--window", type=float, default=0.4, help="seconds a timed block should last")
     ap.add_argument("--warmup", type=int, default=5, help="warm-up calls per kind (1 for a kind slower than 0.1 s a call)")
     ap.add_argument("--full-only", action="store_true", help="time the repeated full call alone")
+    ap.add_argument("--dtype", default="f64", choices=("f32", "f64"), help="the masked plans' value type")
     args = ap.parse_args()
+    f32 = args.dtype == "f32"
 
     dev = 0
     torch.cuda.set_device(dev)
@@ -87,12 +94,27 @@ def main():
         torch.cuda.synchronize(dev)
 
     out = {"workload": args.workload, "source": source, "M": A.M, "nnzA": A.nnz, "products": int(flop),
-           "blocks": args.blocks, "lib": L.lib_path()}
+           "blocks": args.blocks, "lib": L.lib_path(), "dtype": args.dtype}
     C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
     out["nnzC"] = C.nnz
     print(f"{args.workload}: nnz(A) {A.nnz}, {flop} products, nnz(C) {C.nnz}", file=sys.stderr, flush=True)
 
     plans = {}
+    a32 = res32 = None
+    if not args.full_only and f32:  # the FP32 plans' operands, and their reference: an FP64 plan on the rounded values
+        a32 = torch.from_numpy(A.val.astype(np.float32)).to(f"cuda:{dev}")
+        res32 = torch.empty(A.nnz, dtype=torch.float32, device=f"cuda:{dev}")
+        mask64 = mhspgemm.CSR(A.M, A.N, A.ptr, A.col, np.zeros(A.nnz))
+        mask64.H2D(dev)
+        plan64 = mhspgemm.ValuesPlan(tool, A, A, mask64, masked=True, form="product")
+        ref, cnt, sab = (torch.empty(A.nnz, dtype=torch.float64, device=f"cuda:{dev}") for _ in range(3))
+        ones = torch.ones(A.nnz, dtype=torch.float64, device=f"cuda:{dev}")
+        sync()
+        plan64.run(a32.double(), a32.double(), out=ref)
+        plan64.run(ones, ones, out=cnt)
+        plan64.run(a32.double().abs(), a32.double().abs(), out=sab)
+        sync()
+        plan64.close()
     if not args.full_only:
         Cp, Ci, Cv = C.to_host()
         want, hit = filtered(Cp, Ci, Cv, A.ptr, A.col, A.N)
@@ -107,14 +129,23 @@ def main():
                 os.environ.pop("MHS_VAL_DOT_RATIO", None)
             else:
                 os.environ["MHS_VAL_DOT_RATIO"] = str(ratio)  # read by the library at plan creation
-            plan = mhspgemm.ValuesPlan(tool, A, A, mask, masked=True, form=form)
+            plan = mhspgemm.ValuesPlan(tool, A, A, mask, masked=True, form=form, dtype="float32" if f32 else "float64")
             info = plan.info()
-            res = torch.full((A.nnz,), float("nan"), dtype=torch.float64, device=f"cuda:{dev}")
-            plan.run(out=res)
-            sync()
-            got = res.cpu().numpy()
-            assert mhspgemm.compare_ref(A.ptr, A.col, want, A.ptr, A.col, got), f"{name}: outside the 1e-9 rule"
-            assert np.all(got[~hit] == 0.0), f"{name}: an unreached mask entry is not 0.0"
+            if f32:
+                res32.fill_(float("nan"))
+                sync()
+                plan.run(a32, a32, out=res32)
+                sync()
+                assert not torch.isnan(res32).any().item(), f"{name}: an entry was not written"
+                assert torch.all((res32.double() - ref).abs() <= 1.01 * cnt * 2.0 ** -24 * sab).item(), f"{name}: outside m 2^-24 S"
+                assert torch.all(res32[cnt == 0] == 0).item(), f"{name}: an unreached mask entry is not 0.0"
+            else:
+                res = torch.full((A.nnz,), float("nan"), dtype=torch.float64, device=f"cuda:{dev}")
+                plan.run(out=res)
+                sync()
+                got = res.cpu().numpy()
+                assert mhspgemm.compare_ref(A.ptr, A.col, want, A.ptr, A.col, got), f"{name}: outside the 1e-9 rule"
+                assert np.all(got[~hit] == 0.0), f"{name}: an unreached mask entry is not 0.0"
             plans[name] = plan
             print(f"{name}: checked, dot rows {info['dot']}", file=sys.stderr, flush=True)
             out["plans"][name] = {"dot_rows": info["dot"], "kept_products": info["kept_products"],
@@ -122,6 +153,9 @@ def main():
                                   "classes": {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}}
         os.environ.pop("MHS_VAL_DOT_RATIO", None)
         out["checked"] = "every plan against the full product filtered to the mask: the reference 1e-9 rule, misses exactly 0.0"
+        if f32:
+            out["checked"] = ("every plan against an FP64 masked plan on the same rounded values: every entry within "
+                              "1.01 m 2^-24 S, misses exactly 0.0")
 
     # ---- timing
     tool.set_option(L.MHS_OPT_SYNC, 0)
@@ -136,7 +170,7 @@ def main():
     def masked_calls(plan):
         def fn(n):
             for _ in range(n):
-                plan.run()
+                plan.run(a32, a32, out=res32)  # (FP64: all None, the operands' and the mask's own values)
         return fn
 
     def timed(fn, n):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """values_bench.py -- the repeated full call against the values-only call, one config per run.
 
-    python tools/values_bench.py [--config cant] [--blocks 5] [--window 0.4] [--full-only]
+    python tools/values_bench.py [--config cant] [--blocks 5] [--window 0.4] [--full-only] [--dtype f32|f64]
 
 (a) the repeated full call, timed as bench.py times its steps: mhs_spgemm on one pair of
     operands, speculation on, MHS_OPT_SYNC 0 on torch's current stream, each C handed back to
@@ -15,6 +15,10 @@ alternating blocks; a block is enough calls for its window to last `--window` se
 host clock read after a device synchronise and one after the next.  Reported per kind: the median
 of the blocks' per-call times and the spread (max - min) between blocks of that kind.  (b) counts
 as faster only when it is below (a) by more than the larger spread.
+
+--dtype f32 runs (b) through an FP32 plan on float32 values.  Its check is then against an FP64 plan on the same
+rounded values: every entry within 1.01 m 2^-24 S, m and S from the FP64 plan on all-ones and on absolute
+values; the FP64 plan's rows by class are reported beside the FP32 plan's (`classes_f64`).
 
 --full-only times (a) alone and needs nothing of the values-only entry points, so it also runs
 against an older library (MHS_LIB=/path/to/libmhspgemm.so).  Prints one JSON line."""
@@ -47,7 +51,9 @@ def main():
     ap.add_argument("--window", type=float, default=0.4, help="seconds a timed block should last")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--full-only", action="store_true", help="time the repeated full call alone")
+    ap.add_argument("--dtype", default="f64", choices=("f32", "f64"), help="the values plan's value type")
     args = ap.parse_args()
+    f32 = args.dtype == "f32"
 
     dev = 0
     torch.cuda.set_device(dev)
@@ -61,14 +67,40 @@ def main():
         torch.cuda.synchronize(dev)
 
     out = {"config": args.config, "source": source, "M": A.M, "nnzA": A.nnz, "flop": int(flop), "blocks": args.blocks,
-           "lib": L.lib_path()}
+           "lib": L.lib_path(), "dtype": args.dtype}
 
     # ---- the pattern, and (b)'s check against the full product of the same new operands
     C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
     out["nnzC"] = C.nnz
     plan = None
     vals = []
-    if not args.full_only:
+    res32 = None
+    if not args.full_only and f32:
+        plan = mhspgemm.ValuesPlan(tool, A, A, C, dtype="float32")
+        info = plan.info()
+        out["classes"] = {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}
+        out["plan_bytes"] = info["plan_bytes"]
+        rng = np.random.default_rng(17)
+        for _ in range(2):
+            vals.append(tuple(torch.from_numpy(rng.uniform(0.1, 1.0, A.nnz).astype(np.float32)).to(f"cuda:{dev}")
+                              for _ in range(2)))
+        res32 = torch.full((C.nnz,), float("nan"), dtype=torch.float32, device=f"cuda:{dev}")
+        ref, cnt = (torch.empty(C.nnz, dtype=torch.float64, device=f"cuda:{dev}") for _ in range(2))
+        ones = torch.ones(A.nnz, dtype=torch.float64, device=f"cuda:{dev}")
+        sync()
+        plan64 = mhspgemm.ValuesPlan(tool, A, A, C)
+        i64 = plan64.info()
+        out["classes_f64"] = {k: i64[k] for k in mhspgemm.core.VALUES_CLASSES}
+        plan64.run(ones, ones, out=cnt)
+        for av, bv in vals:
+            plan64.run(av.double(), bv.double(), out=ref)  # (positive values: S is the reference itself)
+            plan.run(av, bv, out=res32)
+            sync()
+            assert not torch.isnan(res32).any().item(), "an entry was not written"
+            assert torch.all((res32.double() - ref).abs() <= 1.01 * cnt * 2.0 ** -24 * ref).item(), "outside m 2^-24 S"
+        plan64.close()
+        out["checked"] = "against an FP64 plan on the same rounded values: every entry within 1.01 m 2^-24 S (2 value sets)"
+    elif not args.full_only:
         plan = mhspgemm.ValuesPlan(tool, A, A, C)
         info = plan.info()
         out["classes"] = {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}
@@ -106,7 +138,7 @@ def main():
     def values_calls(n):
         for i in range(n):
             av, bv = vals[i & 1]
-            plan.run(av, bv)
+            plan.run(av, bv, out=res32)  # (FP64: out None, C's own val)
 
     def timed(fn, n):
         sync()
