@@ -568,10 +568,6 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
     return MHS_OK;
 }
 
-// What the hand-off says about a speculated plan: none launched, the call's own Stats are the
-// plan's, or they are not (the plan's kernels returned at once: k_scan wrote go = 0).
-enum PlanVerdict { PLAN_NONE, PLAN_HIT, PLAN_MISS };
-
 // Phase results beside the MHS_* codes: the row-chunked path has completed the call; the call
 // runs again without speculation.
 enum : int { CALL_DONE = -1, CALL_RERUN = -2 };
@@ -582,6 +578,7 @@ struct Call {
     const mhs_csr *const A, *const B;
     mhs_csr* const C;
     mhs_timing* const t;  // (null: no per-phase events)
+    const bool rerun;     // the second attempt of a user call, after a speculation miss: not counted again
     const hipStream_t s;
     const std::chrono::steady_clock::time_point T0 = std::chrono::steady_clock::now();
     const Csr a, b;
@@ -601,14 +598,15 @@ struct Call {
     NumPlan nplan{};  // the numeric launches (a speculated call: built by phase A, finished by phase B)
     int seq = 0;            // k_scan's publication
     bool launched = false;  // the plan's phase A went out
-    PlanVerdict verdict = PLAN_NONE;
+    SpecOutcome outcome = SPEC_PROCEED;  // spec_outcome (mhs_shape.hpp), set by finish_speculated
     hipEvent_t nev0 = nullptr, nev1 = nullptr;  // this call's slot of the numeric event ring
     double t_alloc = 0, t_malloc = 0;
     hipError_t alloc_err = hipSuccess;  // alloc_c's, from prepare_numeric
     Owner own;
 
-    Call(mhs_ctx* x, const mhs_csr* A_, const mhs_csr* B_, mhs_csr* C_, mhs_timing* t_)
-        : ctx(x), A(A_), B(B_), C(C_), t(t_), s(x->stream), a{A_->M, A_->N, A_->nnz, A_->ptr, A_->col, A_->val},
+    Call(mhs_ctx* x, const mhs_csr* A_, const mhs_csr* B_, mhs_csr* C_, mhs_timing* t_, bool rerun_)
+        : ctx(x), A(A_), B(B_), C(C_), t(t_), rerun(rerun_), s(x->stream),
+          a{A_->M, A_->N, A_->nnz, A_->ptr, A_->col, A_->val},
           b{B_->M, B_->N, B_->nnz, B_->ptr, B_->col, B_->val}, M(A_->M), own(x, true) {
         own.out.M = M;
         own.out.N = b.N;
@@ -767,7 +765,7 @@ int Call::launch_symbolic() {
     const int N = b.N;
     const Stats* plan_h = spec ? &ph : nullptr;
     if (fork_sym) {
-        ++ctx->stat[MHS_STAT_SYM_FORK];
+        ctx->stat[MHS_STAT_SYM_FORK] += !rerun;  // (once per user call: a miss has counted its first attempt)
         MHS_HIP(hipEventRecord(ctx->fork_ev, s));
         if (ctx->fork_common_first) {  // (the call stream's launch first: no host launch ahead of it)
             launch_symbolic_common(a, b, w, M, N, Cptr, s, plan_h);
@@ -790,6 +788,7 @@ int Call::launch_symbolic() {
                           ph.sym_count[SYM_GLOBAL] > 0 || (L.near && ph.near_heads > 0);
         if (rare) launch_symbolic_rare(a, w, M, N, Cptr, s, true);  // (+ near row groups)
         if (!spec || ph.sym_count[SYM_B256] > 0) launch_symbolic_b256(a, w, M, N, Cptr, s);
+        // (a rerun does not speculate -- it leaves nothing out and adds nothing here)
         ctx->stat[MHS_STAT_SPEC_SKIPPED] += (!rare) + (spec && ph.sym_count[SYM_B256] == 0);
     }
     MHS_HIP(hipGetLastError());
@@ -849,9 +848,9 @@ int Call::run_or_stamp(const Stats& of, int phase) {
 int Call::speculate_numeric() {
     if (!spec) return MHS_OK;
     const auto T5 = std::chrono::steady_clock::now();
-    bool no_room = false;
-    int rc = prepare_numeric(ph, &no_room);
-    if (no_room) {  // (no room for the plan's C: the hand-off path decides)
+    bool no_room = ctx->spec_no_room;  // (MHS_SPEC_NO_ROOM, tests: the branch below without filling the device)
+    int rc = no_room ? MHS_OK : prepare_numeric(ph, &no_room);
+    if (no_room) {  // (no room for the plan's C: phase A stays in, finish_speculated decides what follows)
         own.give_back_cols();
         (void)hipGetLastError();
         return MHS_OK;
@@ -883,19 +882,24 @@ int Call::handoff() {
     return MHS_OK;
 }
 
-// The plan's verdict, decided here and nowhere else.  A hit: the plan's aux-stream launches and
-// joins (phase B).  A miss: every array is rewritten by a call without speculation -- unless the
-// Stats carry an error, which is then the call's result.
+// What the hand-off makes of the call: spec_outcome (mhs_shape.hpp) decides, here and nowhere else.
+// A hit: the plan's aux-stream launches and joins (phase B).  A rerun (the miss): every array is
+// rewritten by a call without speculation -- also when phase A never went out, and when the Stats
+// carry an error: a speculated call left symbolic launches out, so Stats that are not the plan's
+// may hold stale counts, and the rerun reports a genuine error again.
 int Call::finish_speculated() {
-    verdict = !launched ? PLAN_NONE : !h.err && stats_same_plan(h, ph) ? PLAN_HIT : PLAN_MISS;
-    if (verdict == PLAN_NONE) return MHS_OK;
-    if (verdict == PLAN_HIT)
+    outcome = spec_outcome(spec, launched, h.err != 0, spec && stats_same_plan(h, ph));
+    switch (outcome) {
+    case SPEC_PROCEED:
+        return MHS_OK;
+    case SPEC_HIT:
         return ph.nnzC > 0 ? run_numeric(ctx, a, b, w, ph, own.out, nplan, nev0, nev1, NUM_SPEC_B) : MHS_OK;
+    case SPEC_RERUN:
+        break;
+    }
     MHS_HIP(hipStreamSynchronize(s));
-    own.give_back_cols();
-    ++ctx->stat[MHS_STAT_SPEC_MISS];
-    if (h.err) return MHS_OK;  // (numeric_after_handoff reports it)
     own.give_back();
+    ++ctx->stat[MHS_STAT_SPEC_MISS];  // (once per user call: the rerun does not speculate)
     return CALL_RERUN;  // (plan_valid is false: no speculation)
 }
 
@@ -907,7 +911,7 @@ int Call::numeric_after_handoff() {
     own.out.nnz = (int)h.nnzC;
     ctx->stat[MHS_STAT_NFT] += w.nft != 0;
     ctx->stat[MHS_STAT_NEAR] += L.near && h.near_verified > 0;
-    if (verdict == PLAN_HIT) return MHS_OK;
+    if (outcome == SPEC_HIT) return MHS_OK;
     const auto T5 = std::chrono::steady_clock::now();
     bool no_room = false;
     int rc = prepare_numeric(h, &no_room);
@@ -968,10 +972,10 @@ int Call::finish_call() {
     return MHS_OK;
 }
 
-// One attempt at the call; CALL_RERUN after a speculation miss.
-int spgemm_attempt(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C, mhs_timing* t) {
+// One attempt at the call; CALL_RERUN after a speculation miss (`rerun`: the attempt that follows it).
+int spgemm_attempt(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C, mhs_timing* t, bool rerun) {
     MHS_HIP(hipSetDevice(ctx->device));
-    Call c(ctx, A, B, C, t);
+    Call c(ctx, A, B, C, t, rerun);
     int rc = c.plan_workspace();
     if (rc == MHS_OK) rc = c.analyze_rows();
     if (rc == MHS_OK) c.choose_plan();
@@ -1044,6 +1048,7 @@ int mhs_ctx_create(mhs_ctx** out, int device) {
         if (atoi(e) == 0) ctx->cus = 0;
     if (const char* e = getenv("MHS_GROUP_GRID")) ctx->group_cap = std::max(0, atoi(e));  // (MHS_OPT_GROUP_GRID, A/B)
     if (const char* e = getenv("MHS_SPEC_NSS")) ctx->spec_nss = std::max(1, std::min(atoi(e), mhs_ctx::NAUX + 1));
+    if (const char* e = getenv("MHS_SPEC_NO_ROOM")) ctx->spec_no_room = atoi(e) != 0;
     *out = ctx;
     return MHS_OK;
 }
@@ -1138,8 +1143,8 @@ void mhs_ctx_recycle(mhs_ctx* ctx, mhs_csr* C) {
 
 int mhs_spgemm(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C, mhs_timing* t) {
     if (const int rc = check_args(ctx, A, B, C)) return rc;
-    for (;;) {  // (a rerun finds plan_valid false: it cannot speculate, so cannot miss again)
-        const int rc = spgemm_attempt(ctx, A, B, C, t);
+    for (bool rerun = false;; rerun = true) {  // (a rerun finds plan_valid false: it cannot speculate, so cannot miss again)
+        const int rc = spgemm_attempt(ctx, A, B, C, t, rerun);
         if (rc != CALL_RERUN) return rc;
     }
 }

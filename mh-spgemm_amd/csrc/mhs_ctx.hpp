@@ -89,6 +89,9 @@ struct mhs_ctx {
     // MHS_FORK_ORDER=0: the rare rows first
     bool fork_common_first = true;
     int spec_nss = mhs_ctx::NAUX + 1;  // streams of a speculated numeric phase (MHS_SPEC_NSS: a cap, A/B)
+    // MHS_SPEC_NO_ROOM=1 (tests): a speculated call behaves as if the plan's C had not fitted -- its phase A
+    // stays in (a budget cannot force that: the first call's C fitted under it); other calls are not touched
+    bool spec_no_room = false;
     // the grouped numeric bin's cursor walk (plan_numeric): the device's compute units size its
     // resident set (MHS_GROUP_WALK=0: cus stays 0, the static walk); MHS_OPT_GROUP_GRID caps its blocks
     int cus = 0;

@@ -209,6 +209,19 @@ __host__ __device__ inline bool stats_same_plan(const Stats& a, const Stats& b) 
              a.num_block_big[k] == b.num_block_big[k] && a.num_wave_need[k] == b.num_wave_need[k];
     return eq;
 }
+// What becomes of a call after the hand-off (host only; tests/spec_outcome_check.cpp holds the table).
+// `spec`: the call trimmed its symbolic pass to the previous call's plan (launches of bins the plan had
+// empty were left out, so rows that now fall in one kept stale counts); `launched`: the plan's phase A
+// went out (false: no room for the plan's C); `err`: the call's Stats carry an error bit; `same`:
+// stats_same_plan(call's, plan's).  HIT: phase B of the plan.  PROCEED: the ordinary numeric phase from
+// the call's own Stats, which also reports their error.  RERUN: the call again without speculation --
+// whenever a speculated call's Stats are not the plan's, phase A or not, and whenever they carry an
+// error: with launches left out neither C's size nor an overflow of it can be trusted, and a genuine
+// input error shows up again on the rerun.
+enum SpecOutcome : int { SPEC_PROCEED = 0, SPEC_HIT = 1, SPEC_RERUN = 2 };
+constexpr SpecOutcome spec_outcome(bool spec, bool launched, bool err, bool same) {
+    return !spec ? SPEC_PROCEED : (err || !same) ? SPEC_RERUN : launched ? SPEC_HIT : SPEC_PROCEED;
+}
 struct SpecArgs {
     int* go;       // nullptr: the call does not speculate
     Stats expect;  // the plan's Stats

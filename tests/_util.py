@@ -282,6 +282,33 @@ def near_zoo(seed: int = 4):
     return A, (B.M, B.N, B.ptr, B.col, B.val)
 
 
+def with_hub_row(ptr, col, N, n_hub, feed=0):
+    """A pattern changed in place: the same M and nnz, so it fits the device arrays of (ptr, col).  Row 0 becomes a
+    hub row of n_hub columns (its own and every other column of [0, N) until there are n_hub), paid for by
+    shortening the last rows; rows 1..feed get 0 as their first column, so in A*A their C rows take the hub's."""
+    M = len(ptr) - 1
+    rows = [col[ptr[i]:ptr[i + 1]] for i in range(M)]
+    hub = np.unique(np.concatenate([rows[0], np.arange(0, N, 2)]))[:n_hub]
+    extra = len(hub) - len(rows[0])
+    rows[0] = hub
+    i = M - 1
+    while extra > 0:
+        take = min(extra, len(rows[i]))
+        rows[i] = rows[i][:len(rows[i]) - take]
+        extra -= take
+        i -= 1
+    assert i > feed, "the shortened rows stay clear of the fed ones"
+    for r in range(1, feed + 1):
+        if len(rows[r]):
+            rows[r] = rows[r].copy()
+            rows[r][0] = 0
+    p2 = np.zeros(M + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=p2[1:])
+    c2 = np.concatenate(rows).astype(np.int32)
+    assert len(c2) == len(col) and p2[-1] == ptr[-1]
+    return p2.astype(np.int32), c2
+
+
 # ---------------------- helpers of the values-plan GPU tests (values, masked, backward) ---
 RTOL, ATOL = 1e-6, 1e-12  # the project's value tolerance (tests/test_gpu_parity.py)
 

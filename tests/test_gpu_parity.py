@@ -845,11 +845,13 @@ def test_speculated_plan_miss_and_values(tool, monkeypatch):
     t2 = mhspgemm.Tool(tool.device)
     try:
         def run_and_check(Ah, Bh):
-            C, _ = mhspgemm.spgemm(t2, A, B)
+            C, t = mhspgemm.spgemm(t2, A, B)
             p, c, v = _host_c(C)
             Cp, Ci, Cv = orc.spgemm(Ah[0], Ah[1], Ah[2], Bh[0], Bh[1], Bh[2], N)
             assert np.array_equal(p, Cp) and np.array_equal(c, Ci)
             assert mhspgemm.compare_tol(Cp, Ci, Cv, p, c, v, RTOL, ATOL)[0]
+            # both patterns have rows in the rare symbolic bins (1024-thread, global, 10 KiB wave)
+            assert t.sym_bins[3] + t.sym_bins[4] + t.sym_bins[11] > 0, t.sym_bins
 
         run_and_check((Ap, Ac, Av), (Bp, Bc, Bv))
         run_and_check((Ap, Ac, Av), (Bp, Bc, Bv))
@@ -871,8 +873,10 @@ def test_speculated_plan_miss_and_values(tool, monkeypatch):
         assert t2.stat("spec") == 3 and t2.stat("spec_miss") == 1
         run_and_check((Ap, Ac2, Av2), (Bp, Bc, Bv))  # the rerun left its own plan: a hit
         assert t2.stat("spec") == 4 and t2.stat("spec_miss") == 1
-        # the plan skipped empty rare symbolic bins somewhere in these calls, or it had none
-        assert t2.stat("spec_skipped") >= 0
+        # every plan here has rows in the rare symbolic bins, so each of the four speculated attempts (the
+        # missed call's first one included; its rerun does not speculate) forked them beside k_sym_common,
+        # and a forked pass leaves no launch out (launch_symbolic)
+        assert t2.stat("sym_fork") == 4 and t2.stat("spec_skipped") == 0, (t2.stat("sym_fork"), t2.stat("spec_skipped"))
     finally:
         t2.close()
 
