@@ -21,7 +21,10 @@
  *     sorted ascending per row, duplicates in A or B are summed.
  *   - Values are FP64; summation order on the GPU is not fixed, so values
  *     match a sequential reference to rounding (the north-star bound is
- *     1e-6 relative), row_ptr and col_idx match bit-exactly.
+ *     1e-6 relative), row_ptr and col_idx match bit-exactly.  Sums are double
+ *     on every FP64 path (the full call, the values plans and their backward):
+ *     an entry of m kept products is within m * 2^-53 * (the sum of the
+ *     products' absolute values) of the exact sum, in any order.
  */
 #ifndef MHSPGEMM_H
 #define MHSPGEMM_H

@@ -390,6 +390,77 @@ def ref_grad(pqs, av, bv, G, nnzA, nnzB):
     return np.bincount(p, bv[q] * G[s], nnzA), np.bincount(q, av[p] * G[s], nnzB)
 
 
+# ------------------------------------------------- the FP64 rounding bound ---
+# The contract of every FP64 value path (include/mhspgemm.h): an output entry summed from m kept products, S the
+# sum of their absolute values, is within gamma_m * S of the exact sum, gamma_m = m u / (1 - m u), u = 2^-53 --
+# the any-order bound of a float64 sum of m rounded (or fused) products, whether the sum runs in LDS, through
+# global atomics, over lanes or sequentially.  The tests hold 1.01 * m * 2^-53 * S: the 1.01 covers gamma_m
+# against m u (m < 2^20) and the reference's own error, m * 2^-64 * S in long double (2^-11 of the bound).  It
+# is the factor of tests/test_gpu_values_f32.py; no number in it is measured.  The explicit 0 * b products that
+# near groups and union rows add are exact and do not count in m.  m = 0: exactly 0.0.
+assert np.finfo(np.longdouble).nmant >= 63, "the FP64 bound's reference needs a long double of at least 64 bits of mantissa"
+U64 = 2.0 ** -53
+
+
+def seg_sum_ld(idx, w, n):
+    """Per-slot sums of the long-double weights w: out[k] = sum of w[idx == k], k in [0, n).  (np.bincount would
+    cast the weights to double.)"""
+    w = np.asarray(w, np.longdouble)
+    out = np.zeros(n, np.longdouble)
+    if len(idx) == 0:
+        return out
+    order = np.argsort(idx, kind="stable")
+    si = np.asarray(idx)[order]
+    slots, starts = np.unique(si, return_index=True)
+    out[slots] = np.add.reduceat(w[order], starts)
+    return out
+
+
+def _exact_sums(idx, x, y, n):
+    """(sum, count, absolute sum) per slot of the products x * y, formed and summed in long double."""
+    w = np.asarray(x, np.longdouble) * np.asarray(y, np.longdouble)
+    return seg_sum_ld(idx, w, n), np.bincount(idx, minlength=n).astype(np.int64), seg_sum_ld(idx, np.abs(w), n)
+
+
+def exact_forward(A, B, Cp, Ci, av, bv):
+    """(ref_ld, m, S) of A*B with the values (av, bv) on the pattern (Cp, Ci), which may be a mask: per entry
+    the long-double sum of its kept products, their count and the sum of their absolute values."""
+    p, q, s = expand(A.ptr, A.col, B.ptr, B.col, Cp, Ci, B.N)
+    return _exact_sums(s, av[p], bv[q], len(Ci))
+
+
+def exact_grad(pqs, av, bv, G, nnzA, nnzB):
+    """The (ref_ld, m, S) triples of dA and of dB for the cotangent G over the kept products pqs."""
+    p, q, s = pqs
+    return _exact_sums(p, bv[q], G[s], nnzA), _exact_sums(q, av[p], G[s], nnzB)
+
+
+def assert_f64_bound(got, ref_ld, m, S, what):
+    """got (float64) against the long-double reference within 1.01 m 2^-53 S; m = 0: exactly 0.0; no NaN.
+    Prints and returns the worst err / bound (0.0 where every entry is exact)."""
+    got = np.asarray(got)
+    assert got.dtype == np.float64 and got.shape == ref_ld.shape == m.shape == S.shape, f"{what}: shape"
+    assert not np.isnan(got).any(), f"{what}: every entry is written"
+    assert np.all(got[m == 0] == 0.0), f"{what}: entries no kept product reaches are exactly 0.0"
+    assert m.max(initial=0) < 2 ** 20
+    err = np.abs(got.astype(np.longdouble) - ref_ld)
+    bound = np.longdouble(1.01 * U64) * m.astype(np.longdouble) * S
+    ratio = np.zeros(len(got), np.longdouble)
+    np.divide(err, bound, out=ratio, where=bound > 0)
+    worst = float(ratio.max(initial=0.0))
+    print(f"f64 bound, {what}: worst err / bound {worst:.3f} over {len(got)} entries, max m {m.max(initial=0)}")
+    bad = err > bound
+    assert not bad.any(), f"{what}: {bad.sum()} of {len(got)} entries outside 1.01 m 2^-53 S (worst err / bound {worst:.3e})"
+    return worst
+
+
+def wide_values(n, seed):
+    """uniform(0.5, 1) * 2^k, k an integer of [-20, 20], with a random sign: full 53-bit mantissas over 41 binades.
+    Magnitudes lie in [2^-21, 2^20) and products of two in [2^-42, 2^40): nothing is subnormal, nothing overflows."""
+    rng = np.random.default_rng(seed)
+    return np.ldexp(rng.uniform(0.5, 1.0, n), rng.integers(-20, 21, n)) * rng.choice([-1.0, 1.0], n)
+
+
 # ------------------------------------------------------------ the edge ladder ---
 # Rows that sit exactly on a bin or class edge of csrc/mhs_shape.hpp / mhs_valplan.hpp.  The edges themselves
 # come from tests/golden/shape_edges.json (printed by tests/shape_edges.cpp from the headers); the families

@@ -3,7 +3,8 @@ C<M> = A*B on a given pattern, in the product form (walk the products, drop the 
 form (per mask entry, A's row against B's column through B^T's pattern).  Expected values are the CPU
 oracle's full product restricted to the mask with numpy; mask entries outside the product expect
 exactly 0.0.  Tolerances are those of tests/test_gpu_values.py: 1e-6 relative / 1e-12 absolute and the
-reference's 1e-9 rule; with mixed signs 1e-6 of the same product on absolute values."""
+reference's 1e-9 rule; with mixed signs 1e-6 of the same product on absolute values.  Beside them every form
+that check_forms runs is held to the FP64 rounding bound on the mask, 1.01 m 2^-53 S per entry (tests/_util.py)."""
 import functools
 
 import numpy as np
@@ -13,8 +14,8 @@ import torch
 import mhspgemm
 from mhspgemm import _lib
 from oracle import oracle as orc
-from _util import (GOLDEN, PRODUCT_CASES, assert_values, bin_zoo, csr_of, device_csr, filled, keys, load_golden, new_values,
-                   random_csr, tiny_zoo, upload)
+from _util import (GOLDEN, PRODUCT_CASES, assert_f64_bound, assert_values, bin_zoo, csr_of, device_csr, exact_forward, filled,
+                   keys, load_golden, new_values, random_csr, tiny_zoo, upload)
 
 pytestmark = pytest.mark.gpu
 
@@ -73,10 +74,13 @@ def check_forms(tool, A, B, Mp, Mc, forms, seed=1, signed=False):
     if signed:
         absv, _ = on_mask(*orc.spgemm(A.ptr, A.col, np.abs(av), B.ptr, B.col, np.abs(bv), B.N), Mp, Mc, B.N)
     kept, products = kept_products(A, B, Mp, Mc), orc.flop(A.col, B.ptr)
+    exact = exact_forward(A, B, Mp, Mc, av, bv)  # the FP64 contract on the mask: 1.01 m 2^-53 S, m = 0 exactly 0.0
+    assert np.array_equal(exact[1] > 0, hit) and exact[1].sum() == kept
     infos = {}
     for form in forms:
         (got,), info = run_masked(tool, A, B, Mp, Mc, form, av, bv)
         assert_values(Mp, Mc, want, Mp, Mc, got, absv)
+        assert_f64_bound(got, *exact, f"masked plan, {form} form, C")
         assert np.all(got[~hit] == 0.0), "mask entries no product reaches are exactly 0.0"
         assert info["products"] == products and info["kept_products"] == kept, (form, info, kept)
         infos[form] = info

@@ -2,7 +2,8 @@
 mhs_spgemm_values): C's values recomputed on a kept pattern, against the oracle on the new
 operands.  Pattern equal by construction (it is C's own); values within the project's two
 tolerances (tests/test_gpu_parity.py): 1e-6 relative / 1e-12 absolute, and the reference's 1e-9
-rule.  With mixed signs the bound is 1e-6 of the same product on absolute values."""
+rule.  With mixed signs the bound is 1e-6 of the same product on absolute values.  Beside them every values
+call of the shared checker is held to the FP64 rounding bound, 1.01 m 2^-53 S per entry (tests/_util.py)."""
 import functools
 
 import numpy as np
@@ -12,8 +13,8 @@ import torch
 import mhspgemm
 from mhspgemm import _lib, synth
 from oracle import oracle as orc
-from _util import (GOLDEN, PRODUCT_CASES, assert_values, bin_zoo, csr_of, load_golden, new_values, random_csr, tiny_zoo,
-                   upload)
+from _util import (GOLDEN, PRODUCT_CASES, assert_f64_bound, assert_values, bin_zoo, csr_of, exact_forward, load_golden,
+                   new_values, random_csr, tiny_zoo, upload)
 
 pytestmark = pytest.mark.gpu
 
@@ -50,6 +51,7 @@ def values_check(tool, A, B, seed=1, signed=False):
     if signed:
         _, _, absv = orc.spgemm(A.ptr, A.col, np.abs(av), B.ptr, B.col, np.abs(bv), B.N)
     assert_values(Cp, Ci, Cv, p, c, v, absv)
+    assert_f64_bound(v, *exact_forward(A, B, Cp, Ci, av, bv), "values plan, C")  # the FP64 contract: 1.01 m 2^-53 S
     assert info["nnzC"] == Cp[-1] and info["products"] == orc.flop(A.col, B.ptr)
     assert sum(info["rows"]) == A.M and info["plan_bytes"] >= 4 * A.M
     return info

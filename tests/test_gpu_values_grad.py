@@ -2,8 +2,9 @@
 gradients of Aval and Bval for a cotangent on C's pattern, against a numpy reference that expands every
 product as index arrays and sums with bincount -- independent of the library.  Tolerances are the
 project's (tests/test_gpu_values.py): 1e-6 relative / 1e-12 absolute; with mixed signs 1e-6 of the same
-gradient computed on absolute values.  Every call writes into NaN-filled buffers; entries that no kept
-product reaches must come back exactly 0.0."""
+gradient computed on absolute values; beside them grad_check holds dA and dB to the FP64 rounding bound,
+1.01 m 2^-53 S per entry against sums in long double (tests/_util.py).  Every call writes into NaN-filled
+buffers; entries that no kept product reaches must come back exactly 0.0."""
 import ctypes
 import functools
 
@@ -14,8 +15,8 @@ import torch
 import mhspgemm
 from mhspgemm import _lib, synth
 from oracle import oracle as orc
-from _util import (ATOL, GOLDEN, PRODUCT_CASES, RTOL, bin_zoo, csr_of, device_csr, expand, filled, load_golden, new_values,
-                   random_csr, ref_grad, tiny_zoo, upload)
+from _util import (ATOL, GOLDEN, PRODUCT_CASES, RTOL, assert_f64_bound, bin_zoo, csr_of, device_csr, exact_grad, expand, filled,
+                   load_golden, new_values, random_csr, ref_grad, tiny_zoo, upload)
 
 pytestmark = pytest.mark.gpu
 
@@ -59,6 +60,10 @@ def grad_check(tool, A, B, Cp, Ci, seed=1, signed=False, masked=False, form="aut
         absA, absB = ref_grad(pqs, np.abs(av), np.abs(bv), np.abs(G), A.nnz, B.nnz)
     assert_grad(gA, wA, absA, np.bincount(pqs[0], minlength=A.nnz) > 0, "dA")
     assert_grad(gB, wB, absB, np.bincount(pqs[1], minlength=B.nnz) > 0, "dB")
+    exA, exB = exact_grad(pqs, av, bv, G, A.nnz, B.nnz)  # the FP64 contract: 1.01 m 2^-53 S, m = 0 exactly 0.0
+    kind = f"masked plan, {form} form" if masked else "values plan"
+    assert_f64_bound(gA, *exA, f"{kind}, dA")
+    assert_f64_bound(gB, *exB, f"{kind}, dB")
     return info, gA, gB
 
 
