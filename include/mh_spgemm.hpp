@@ -10,6 +10,7 @@
 // and, beyond the reference, the values-only call on a kept pattern:
 //   class mhs_shim::ValuesPlan                               owns an mhs_values_plan
 //   void MH_spgemm_values(const CSR&, const CSR&, CSR&, mhs_shim::ValuesPlan&)
+//   void MH_spgemm_values_batched(nb, Aval, strideA, Bval, strideB, Cval, strideC, mhs_shim::ValuesPlan&)
 //
 // Errors: the C-ABI returns codes; this shim rethrows as std::runtime_error so a
 // caller's try { MH_spgemm(...) } catch (...) { "MH-SpGEMM failed!!!" } behaves as
@@ -263,6 +264,18 @@ public:
             throw std::runtime_error(mhs_last_error(ctx));
         }
     }
+    // The batched constructor (mhs_values_plan_create_batched): a plan of `width` (1, 2 or 4) value sets per walk,
+    // for MH_spgemm_values_batched.  Width 1 is the typed constructor's plan.
+    ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C, bool masked, int form, mhs_dtype dtype, int width)
+        : ctx(tools.ctx) {
+        mhs_csr a{A.M, A.N, A.nnz, A.d_ptr, A.d_col, A.d_val};
+        mhs_csr b{B.M, B.N, B.nnz, B.d_ptr, B.d_col, B.d_val};
+        mhs_csr c{C.M, C.N, C.nnz, C.d_ptr, C.d_col, C.d_val};
+        if (mhs_values_plan_create_batched(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, width, &plan) != MHS_OK) {
+            std::printf("%s\n", mhs_last_error(ctx));
+            throw std::runtime_error(mhs_last_error(ctx));
+        }
+    }
     ValuesPlan(const ValuesPlan&) = delete;
     ValuesPlan& operator=(const ValuesPlan&) = delete;
     ~ValuesPlan() { mhs_values_plan_destroy(ctx, plan); }
@@ -282,6 +295,12 @@ public:
         int d = MHS_F64;
         mhs_values_plan_dtype(plan, &d);
         return (mhs_dtype)d;
+    }
+    // the plan's width: the value sets one walk sums
+    int width() const {
+        int w = 1;
+        mhs_values_plan_width(plan, &w);
+        return w;
     }
     // the hipEvent time of the last MH_spgemm_values call through this plan (ms)
     double last_ms = 0;
@@ -322,6 +341,27 @@ inline void MH_spgemm_values(const float* Aval, const float* Bval, float* Cval, 
 inline void MH_spgemm_values_grad(const float* Aval, const float* Bval, const float* dC, float* dA, float* dB,
                                   mhs_shim::ValuesPlan& plan) {
     const int rc = mhs_spgemm_values_grad_f32(plan.ctx, plan.plan, Aval, Bval, dC, dA, dB, &plan.last_ms);
+    if (rc != MHS_OK) {
+        std::printf("%s\n", mhs_last_error(plan.ctx));
+        throw std::runtime_error(mhs_last_error(plan.ctx));
+    }
+}
+
+// nb value sets in one call (mhs_spgemm_values_batched / _f32): set b reads Aval + b * strideA and
+// Bval + b * strideB and writes Cval + b * strideC (device arrays, strides in elements; an input stride of 0: one
+// array shared by all sets).  Any plan runs it; a plan of width W shares each walk of the patterns among W sets.
+inline void MH_spgemm_values_batched(int nb, const double* Aval, int64_t strideA, const double* Bval, int64_t strideB,
+                                     double* Cval, int64_t strideC, mhs_shim::ValuesPlan& plan) {
+    const int rc = mhs_spgemm_values_batched(plan.ctx, plan.plan, nb, Aval, strideA, Bval, strideB, Cval, strideC, &plan.last_ms);
+    if (rc != MHS_OK) {
+        std::printf("%s\n", mhs_last_error(plan.ctx));
+        throw std::runtime_error(mhs_last_error(plan.ctx));
+    }
+}
+inline void MH_spgemm_values_batched(int nb, const float* Aval, int64_t strideA, const float* Bval, int64_t strideB, float* Cval,
+                                     int64_t strideC, mhs_shim::ValuesPlan& plan) {
+    const int rc =
+        mhs_spgemm_values_batched_f32(plan.ctx, plan.plan, nb, Aval, strideA, Bval, strideB, Cval, strideC, &plan.last_ms);
     if (rc != MHS_OK) {
         std::printf("%s\n", mhs_last_error(plan.ctx));
         throw std::runtime_error(mhs_last_error(plan.ctx));

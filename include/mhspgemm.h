@@ -298,6 +298,49 @@ int mhs_spgemm_values_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float *Aval
 int mhs_spgemm_values_grad_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float *Aval, const float *Bval,
                                const float *dCval, float *dAval, float *dBval, double *ms);
 
+/* ---- batched values calls: several value sets in one walk of the pattern ---------------------
+ * For callers with nb value sets on one pattern triple (the heads of a sparse attention layer, an ensemble
+ * over one mesh, a batch of matrices from one stencil, many A's against one fixed B).  A plan has a third
+ * fixed property beside its value type, its width W (1, 2 or 4): the value sets one walk of the patterns
+ * sums.  The pattern work of a product -- the B column, the A entry, the slot in C's row -- is done once for
+ * W sets, only the value loads and the sums W times.  A row's class is LDS arithmetic on the sum bytes
+ * W * sizeof(value): at 16 B (FP64 W=2, FP32 W=4) a wave holds 512 direct columns or 408 searched entries and
+ * a block 9,984 or 7,986; at 32 B (FP64 W=4) 256 / 226 and 4,992 / 4,436 (FP32 W=2 is the FP64 table).
+ * Rows therefore move to costlier classes as W grows.  Cost on MI355X against nb unbatched calls (DESIGN section
+ * 14, nb = 8): where loads and searches carry the call batching divides it (scircuit-like 0.64x at W = 2, 0.49x at
+ * FP32 W = 4; masked triangle 0.6x, 0.33x at FP32 W = 4); where one LDS add per product and set carries it there is
+ * only the walk to save (cant-like W = 2: 0.99x), and FP64 W = 4 is then 1.5x slower than the loop -- its
+ * block-direct rows declare four times the LDS of the unbatched launch and run on wider kernels.  Use W <= 2 on
+ * such patterns.
+ * mhs_values_plan_create_batched with width 1 is exactly mhs_values_plan_create_typed; a width other than
+ * 1, 2 or 4 returns MHS_ERR_INVALID before any HIP call.  Validation, borrowing and plan memory as for any plan.
+ * mhs_spgemm_values_batched / _f32: set b (0 <= b < nb) reads Aval + b * strideA and Bval + b * strideB and
+ * writes Cval + b * strideC.  Strides are in elements.  An input stride of 0 means one array shared by all
+ * sets; otherwise it is >= that matrix's nnz.  strideC >= nnz(C) whenever nb > 1.  Outputs must not overlap
+ * inputs or each other.  Every set has the contract of the unbatched call: every entry written, entries no
+ * kept product reaches exactly 0, the any-order bound of the plan's type.  Nothing outside the nb segments of
+ * nnz(C) values is written.  On the dot rows of a masked plan a set has the bits of the unbatched call on its
+ * values.  Any nb >= 1 runs on any plan: ceil(nb / W) passes of the plan's launch list, the last with the
+ * remaining sets (on a width-1 plan: nb runs of the unbatched kernels).  mhs_spgemm_values / _f32 on a plan of
+ * any width is the nb = 1 batched call.  ms and MHS_OPT_SYNC as in mhs_spgemm_values (a timed call brackets
+ * all passes); with ms == NULL and MHS_OPT_SYNC 0 the call allocates nothing, reads nothing back and does not
+ * synchronise.  Refused with MHS_ERR_INVALID and a message before any HIP call, writing nothing: nb < 1, a
+ * negative stride, an input stride between 1 and nnz - 1, strideC < nnz(C) with nb > 1, a needed array NULL,
+ * a call of the wrong type, a plan of another device.  mhs_spgemm_values_grad / _f32 on a plan of width > 1 is
+ * refused likewise: the backward of batched plans is not built (the next step); use a width-1 plan.
+ * Additions to ABI version 10, like the entries above. */
+#define MHS_VAL_WIDTH_MAX 4
+int mhs_values_plan_create_batched(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
+                                   int masked, int form, int dtype, int width, mhs_values_plan **plan);
+/* The plan's width. */
+int mhs_values_plan_width(const mhs_values_plan *plan, int *width);
+int mhs_spgemm_values_batched(mhs_ctx *ctx, mhs_values_plan *plan, int nb,
+                              const double *Aval, int64_t strideA, const double *Bval, int64_t strideB,
+                              double *Cval, int64_t strideC, double *ms);
+int mhs_spgemm_values_batched_f32(mhs_ctx *ctx, mhs_values_plan *plan, int nb,
+                                  const float *Aval, int64_t strideA, const float *Bval, int64_t strideB,
+                                  float *Cval, int64_t strideC, double *ms);
+
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).
  * At->M = A->N, At->N = A->M; rows of At list their columns ascending; arrays are

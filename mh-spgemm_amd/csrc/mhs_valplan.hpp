@@ -39,6 +39,19 @@
 // VAL_DENSE_RATIO, VAL_BLOCK_SMALL, VAL_GROUP, the grid caps.  val_slice_entries / val_slice_fits are the
 // guards of a row's LDS slice, for the kernels' row frame (mhs_valwalk.hpp) and for the host alike.
 //
+// The width.  A plan has a third fixed property, its width W (1, 2 or 4: VAL_WIDTH_MAX): the value sets one walk
+// of the pattern accumulates (mhs_values_plan_create_batched).  With it everything above that is bytes depends on
+// the sum bytes sb = W x vb, 4 / 8 / 16 / 32: a direct column costs sb, a searched entry sb + 4 (W sums and the one
+// shared column), and every function below that takes vb serves sb.  W = 1 is the tables above; FP32 W = 2 is the
+// FP64 table (sb = 8); further
+//   sb  plans                wave-direct span  wave-search n  block-direct span  block-search n  team row
+//   16  FP64 W=2, FP32 W=4                512            408              9,984           7,986   1,280 B
+//   32  FP64 W=4                          256            226              4,992           4,436   2,304 B
+// A slice holds its sums set-major: acc[w x pitch + slot], pitch the span (direct) or the slice's entry count
+// (search), the one column array behind all W planes.  Counts still do not move.  At sb = 32 the team launch at its
+// cap is 73,728 B, past the VAL_LDS_PLAIN a launch may take unasked: val_team_registers says which team kernels
+// init_values_attributes registers for val_team_launch_cap.  plan_grad is not computed for W > 1.
+//
 // plan_values(counts) is the whole launch plan of a hot call; issue_values (mhs_values.hip) turns one
 // ValLaunch and the call's arrays into a kernel launch.  No pointer and no HIP type in here:
 // tests/valplan_check.cpp runs it on the host.  plan_grad(counts) is the launch plan of the backward
@@ -80,7 +93,12 @@ constexpr int VAL_DOT_RATIO = 2;
 // Bytes of a value: vb, 8 (FP64) or 4 (FP32)
 constexpr int VAL_VB_F64 = 8, VAL_VB_F32 = 4;
 __host__ __device__ constexpr bool val_vb_ok(int vb) { return vb == VAL_VB_F64 || vb == VAL_VB_F32; }
-__host__ __device__ constexpr int val_search_entry(int vb) { return vb + 4; }  // a searched entry: its sum and its column
+// The width of a plan, W: the value sets one walk accumulates; and the sum bytes sb = W x vb that stand wherever
+// a function below takes vb (W = 1: sb = vb)
+constexpr int VAL_WIDTH_MAX = 4;
+__host__ __device__ constexpr bool val_width_ok(int w) { return w == 1 || w == 2 || w == 4; }
+__host__ __device__ constexpr bool val_sb_ok(int sb) { return sb == 4 || sb == 8 || sb == 16 || sb == 32; }
+__host__ __device__ constexpr int val_search_entry(int vb) { return vb + 4; }  // a searched entry: its sum(s) and its column
 
 // LDS bytes of one row, per method
 __host__ __device__ constexpr long long val_lds_search(long long n, int vb = VAL_VB_F64) {  // sums, then columns
@@ -105,6 +123,24 @@ constexpr bool val_caps_fit(int vb) {
            val_lds_search(val_block_search_n(vb), vb) <= VAL_BLOCK_BYTES;
 }
 static_assert(val_caps_fit(VAL_VB_F64) && val_caps_fit(VAL_VB_F32), "rows fit their team, wave and block slices");
+// The team launch at its cap, and whether it is past what a launch may take without hipFuncSetAttribute: the team
+// kernels of such an sb are registered for val_team_launch_cap (init_values_attributes)
+constexpr int VAL_LDS_PLAIN = 65536;
+constexpr int val_team_launch_cap(int sb) { return (int)val_lds_search(VAL_TEAM_NMAX, sb) * VAL_TEAM_ROWS; }
+constexpr bool val_team_registers(int sb) { return val_team_launch_cap(sb) > VAL_LDS_PLAIN; }
+constexpr bool val_caps_fit_wide(int sb) {
+    return val_team_launch_cap(sb) <= LDS_MAX_C && val_lds_direct(val_wave_direct_span(sb), sb) <= VAL_WAVE_BYTES &&
+           val_lds_search(val_wave_search_n(sb), sb) <= VAL_WAVE_BYTES &&
+           val_lds_direct(val_block_direct_span(sb), sb) <= VAL_BLOCK_BYTES &&
+           val_lds_search(val_block_search_n(sb), sb) <= VAL_BLOCK_BYTES;
+}
+static_assert(val_caps_fit_wide(16) && val_caps_fit_wide(32) && !val_team_registers(4) && !val_team_registers(8) &&
+                  !val_team_registers(16) && val_team_registers(32) && val_team_launch_cap(32) == 73728,
+              "wide rows fit their slices; the sb = 32 team launch is the registered one");
+static_assert(val_wave_direct_span(16) == 512 && val_wave_search_n(16) == 408 && val_block_direct_span(16) == 9984 &&
+                  val_block_search_n(16) == 7986 && val_wave_direct_span(32) == 256 && val_wave_search_n(32) == 226 &&
+                  val_block_direct_span(32) == 4992 && val_block_search_n(32) == 4436,
+              "the width table of the header comment");
 static_assert(VAL_BLOCK_BYTES + VAL_STAGE_BYTES <= 163840, "block rows fit one workgroup");
 static_assert(VAL_WAVE_DIRECT_SPAN == 1024 && VAL_WAVE_SEARCH_N == 682 && VAL_BLOCK_DIRECT_SPAN == 19968 &&
                   VAL_BLOCK_SEARCH_N == 13312 && val_wave_direct_span(4) == 2048 && val_wave_search_n(4) == 1024 &&
@@ -228,6 +264,17 @@ struct ValPlan {
     int n;
     ValLaunch launch[VAL_PLAN_MAX];
 };
+
+// Static LDS of a forward kernel at value size vb and width W, beside its launch's dynamic bytes: the stage of A
+// entries of the wave and block walks (B row start and length; the A value too at W = 1 only: wider walks read
+// it from A.val) and the dot class's stage (column and W values).  The kernels assert their stages against it.
+constexpr int val_static_lds(int kernel, int vb, int width) {
+    const int entry = 8 + (width == 1 ? vb : 0);
+    return kernel == VK_WAVE_DIRECT || kernel == VK_WAVE_SEARCH     ? WPB * 64 * entry
+           : kernel == VK_BLOCK_DIRECT || kernel == VK_BLOCK_SEARCH ? VAL_STAGE * entry
+           : kernel == VK_DOT                                       ? WPB * 64 * (4 + width * vb)
+                                                                    : 0;
+}
 
 constexpr int VAL_TEAM_GRID = 16384;   // block caps (rows past them are walked grid-stride)
 constexpr int VAL_WAVE_GRID = 16384;

@@ -6,7 +6,8 @@
 // Hot call: one value kernel per non-empty class.  Each walks A's row, then B's rows, reads
 // Aval / Bval only for values, and -- told the row's sorted columns -- only finds each product's
 // slot: by subtraction (direct classes) or by binary search (team, search and global classes).
-// Every value kernel is a template on the plan's value type V (double or float: ValArgs<V>); sums are
+// Every value kernel is a template on the plan's value type V (double or float: ValArgs<V>) and on its width
+// W (1, 2 or 4: the value sets one walk sums, mhs_spgemm_values_batched; W = 1 is the unbatched kernel); sums are
 // atomics of that type: ds_add_f64 / ds_add_f32 in LDS, global_atomic_add_f64 / _f32 in the global class.
 // Masked plans (mhs_values_plan_create_masked: C's pattern is a mask, products outside it are dropped)
 // classify by val_class_masked, count the kept products in place of the verify walk, and may send rows
@@ -20,14 +21,32 @@ namespace {
 
 // The products of row `row`: group g of ng groups takes A entries g, g + ng, ...; its G lanes
 // stride over the B row.  add(column, value) per product.
-template <int G, class V, class F>
+// W: the plan's width.  The pattern work of a product -- the B column and, in add, its slot -- is done
+// once, the value work for each of the pass's sets: add(column, sums) with sums.x[w] the product of set
+// w < val_nw (set w's values lie w strides on: ValArgs); the x of a set the pass has not is not set.
+template <int W, class V>
+__device__ __forceinline__ int val_nw(const ValArgs<V>& a) {
+    return W == 1 ? 1 : a.nw;
+}
+template <int G, int W, class V, class F>
 __device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int g, int ng, int t, F add) {
+    const int nw = val_nw<W>(a);
     const int ae = a.A.ptr[row + 1];
     for (int k = a.A.ptr[row] + g; k < ae; k += ng) {
         const int ac = a.A.col[k];
-        const V av = a.A.val[k];
+        V av[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            if (w < nw) av[w] = a.A.val[(long long)w * a.sA + k];
         const int be = a.B.ptr[ac + 1];
-        for (int j = a.B.ptr[ac] + t; j < be; j += G) add(a.B.col[j], av * a.B.val[j]);
+        for (int j = a.B.ptr[ac] + t; j < be; j += G) {
+            const int c = a.B.col[j];
+            ValSums<V, W> p;
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+                if (w < nw) p.x[w] = av[w] * a.B.val[(long long)w * a.sB + j];
+            add(c, p);
+        }
     }
 }
 // The same products for a wave's or a block's row, with memory-level parallelism: the row's `lanes`
@@ -36,9 +55,13 @@ __device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int 
 // lanes takes staged entries g, g + ng, ... and reads its B row VAL_PIECES G-wide pieces at a time,
 // every load issued before the first sum.  pre() runs once, between the first stage's loads and the
 // sync that publishes them (the row's zero fill rides on that sync).
-template <int G, int CH, class V, class Sync, class Pre, class F>
-__device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t, int lanes, ValStage<CH, V>& d, Sync sync,
+// W > 1: the stage holds no A value (ValStage); a group reads each set's at the entry's A position, and
+// val_pieces(W) pieces of W values each are in flight.
+template <int G, int W, int CH, class V, class Sync, class Pre, class F>
+__device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t, int lanes, ValStage<CH, V, W>& d, Sync sync,
                                             Pre pre, F add) {
+    constexpr int P = val_pieces(W);
+    const int nw = val_nw<W>(a);
     const int g = t / G, ng = lanes / G, tl = t % G;
     const int ae = a.A.ptr[row + 1], a0 = a.A.ptr[row];
     if (a0 >= ae) {
@@ -53,26 +76,41 @@ __device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t,
             const int bs = a.B.ptr[ac];
             d.bs[t] = bs;
             d.len[t] = a.B.ptr[ac + 1] - bs;
-            d.av[t] = a.A.val[k0 + t];
+            if constexpr (W == 1) d.av[t] = a.A.val[k0 + t];
         }
         if (k0 == a0) pre();
         sync();
         for (int e = g; e < cnt; e += ng) {
             const int bs = d.bs[e], len = d.len[e];
-            const V av = d.av[e];
-            for (int j = tl; j < len; j += VAL_PIECES * G) {
-                int c[VAL_PIECES];
-                V v[VAL_PIECES];
+            V av[W];
+            if constexpr (W == 1) {
+                av[0] = d.av[e];
+            } else {
 #pragma unroll
-                for (int u = 0; u < VAL_PIECES; ++u) {
+                for (int w = 0; w < W; ++w)
+                    if (w < nw) av[w] = a.A.val[(long long)w * a.sA + (k0 + e)];
+            }
+            for (int j = tl; j < len; j += P * G) {
+                int c[P];
+                V v[P][W];
+#pragma unroll
+                for (int u = 0; u < P; ++u) {
                     const int jj = j + u * G;
                     const bool in = jj < len;
                     c[u] = in ? a.B.col[bs + jj] : -1;
-                    v[u] = in ? a.B.val[bs + jj] : V(0);
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        if (w < nw) v[u][w] = in ? a.B.val[(long long)w * a.sB + (bs + jj)] : V(0);
                 }
 #pragma unroll
-                for (int u = 0; u < VAL_PIECES; ++u)
-                    if (c[u] >= 0) add(c[u], av * v[u]);
+                for (int u = 0; u < P; ++u)
+                    if (c[u] >= 0) {
+                        ValSums<V, W> p;
+#pragma unroll
+                        for (int w = 0; w < W; ++w)
+                            if (w < nw) p.x[w] = av[w] * v[u][w];
+                        add(c[u], p);
+                    }
             }
         }
         sync();
@@ -121,7 +159,7 @@ __global__ __launch_bounds__(256) void k_val_check_cols(const int* __restrict__ 
 // reservation per block and class; cnt is the counter block of mhs_valplan.hpp).  FILL true: write the rows into
 // their class lists, class c's list at the prefix of the counts before it.
 // MASKED: the class by val_class_masked -- the row's A entries and, with B^T's row pointer, its dot cost.
-// vb: the bytes of the plan's value type, which the classes and the LDS needs depend on.
+// vb: the plan's sum bytes (its width x the bytes of its value type), which the classes and the LDS needs depend on.
 template <bool FILL, bool MASKED>
 __global__ __launch_bounds__(256) void k_val_classify(ValPattern p, ValMask m, int vb, int* __restrict__ cnt,
                                                       int* __restrict__ lists) {
@@ -215,61 +253,86 @@ __global__ __launch_bounds__(256) void k_val_count_kept(ValPattern p, unsigned l
 }
 
 // ---------------------------------------------------------- value kernels ---
-// Searched sums of one row by `lanes` lanes (lane t): cols / acc are the row's LDS slice.
-// walk(pre, add) runs pre() and a sync, then add(column, value) per product; sync orders the steps
-// (a wave's or a block's).
-template <class V, class Sync, class Walk>
-__device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V* acc, int* cols, int t, int lanes, Sync sync,
-                                           Walk walk) {
+// Searched sums of one row by `lanes` lanes (lane t): cols / acc are the row's LDS slice, set w's sums the
+// plane acc + w * pitch.  walk(pre, add) runs pre() and a sync, then add(column, sums) per product; sync orders
+// the steps (a wave's or a block's).  Every set's ds_add has the one slot, so the bank pattern of one set's.
+template <int W, class V, class Sync, class Walk>
+__device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V* acc, int* cols, int pitch, int t, int lanes,
+                                           Sync sync, Walk walk) {
+    const int nw = val_nw<W>(a);
     walk(
         [&] {
             for (int p = t; p < n; p += lanes) {
                 cols[p] = a.C.col[s + p];
-                acc[p] = V(0);
+#pragma unroll
+                for (int w = 0; w < W; ++w)
+                    if (w < nw) acc[(size_t)w * pitch + p] = V(0);
             }
         },
-        [&](int c, V v) {
+        [&](int c, const ValSums<V, W>& v) {
             const int slot = find_slot(cols, n, c);
-            if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64 / ds_add_f32
+            if (slot >= 0) {
+#pragma unroll
+                for (int w = 0; w < W; ++w)
+                    if (w < nw) atomicAdd(&acc[(size_t)w * pitch + slot], v.x[w]);  // ds_add_f64 / ds_add_f32
+            }
         });
     sync();
-    for (int p = t; p < n; p += lanes) a.C.val[s + p] = acc[p];
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+        if (w < nw)
+            for (int p = t; p < n; p += lanes) a.C.val[(long long)w * a.sC + (s + p)] = acc[(size_t)w * pitch + p];
     sync();
 }
-// Span-indexed sums of one row: acc[col - first], gathered through C.col afterwards.
-template <class V, class Sync, class Walk>
+// Span-indexed sums of one row: acc[w * span + col - first], gathered through C.col afterwards.
+template <int W, class V, class Sync, class Walk>
 __device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, int first, int span, V* acc, int t, int lanes,
                                            Sync sync, Walk walk) {
+    const int nw = val_nw<W>(a);
     walk(
         [&] {
-            for (int p = t; p < span; p += lanes) acc[p] = V(0);
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+                if (w < nw)
+                    for (int p = t; p < span; p += lanes) acc[(size_t)w * span + p] = V(0);
         },
-        [&](int c, V v) {
+        [&](int c, const ValSums<V, W>& v) {
             const unsigned slot = (unsigned)(c - first);
-            if (slot < (unsigned)span) atomicAdd(&acc[slot], v);  // ds_add_f64 / ds_add_f32
+            if (slot < (unsigned)span) {
+#pragma unroll
+                for (int w = 0; w < W; ++w)
+                    if (w < nw) atomicAdd(&acc[(size_t)w * span + slot], v.x[w]);  // ds_add_f64 / ds_add_f32
+            }
         });
     sync();
-    for (int p = t; p < n; p += lanes) a.C.val[s + p] = acc[a.C.col[s + p] - first];
+    for (int p = t; p < n; p += lanes) {
+        const int slot = a.C.col[s + p] - first;
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            if (w < nw) a.C.val[(long long)w * a.sC + (s + p)] = acc[(size_t)w * span + slot];
+    }
     sync();
 }
 
 // One row of a wave or block class in the row frame: direct or searched sums over the staged walk.
-template <bool DIRECT, int CH, class V, class Sync>
+template <bool DIRECT, int W, int CH, class V, class Sync>
 __device__ __forceinline__ void row_sums(const ValArgs<V>& a, int row, char* base, int region, int t, int lanes,
-                                         ValStage<CH, V>& d, Sync sync) {
-    val_row<DIRECT>(a, row, base, region, [&](int s, int n, int first, int span, V* acc, int* cols) {
-        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP>(a, row, t, lanes, d, sync, pre, add); };
-        if constexpr (DIRECT) row_direct(a, s, n, first, span, acc, t, lanes, sync, walk);
-        else row_search(a, s, n, acc, cols, t, lanes, sync, walk);
+                                         ValStage<CH, V, W>& d, Sync sync) {
+    val_row<DIRECT, W>(a, row, base, region, [&](int s, int n, int first, int span, V* acc, int* cols) {
+        const int pitch = val_slice_entries(region, W * (int)sizeof(V));  // (search: the slice's entries, as search_slice)
+        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP, W>(a, row, t, lanes, d, sync, pre, add); };
+        if constexpr (DIRECT) row_direct<W>(a, s, n, first, span, acc, t, lanes, sync, walk);
+        else row_search<W>(a, s, n, acc, cols, pitch, t, lanes, sync, walk);
     });
 }
 
 // Team class: VAL_TEAM_LANES lanes per row, the teams of a wave in step (wave-level ordering).
-template <class V>
+template <class V, int W>
 __global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     const int team = threadIdx.x / VAL_TEAM_LANES, t = threadIdx.x % VAL_TEAM_LANES;
-    const ValSlice<V> sl = search_slice<V>(lds + (size_t)team * region, region);
+    const int nw = val_nw<W>(a);
+    const ValSlice<V> sl = search_slice<V, W>(lds + (size_t)team * region, region);
     V* acc = sl.val;
     int* cols = sl.cols;
     for (int base = blockIdx.x * VAL_TEAM_ROWS; base < count; base += gridDim.x * VAL_TEAM_ROWS) {
@@ -277,55 +340,72 @@ __global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __res
         const int row = val_team_row(a, list, count, base + team, sl.ne, s, n);
         for (int p = t; p < n; p += VAL_TEAM_LANES) {
             cols[p] = a.C.col[s + p];
-            acc[p] = V(0);
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+                if (w < nw) acc[(size_t)w * sl.ne + p] = V(0);
         }
         vwave_sync();
         if (n > 0)
-            walk_products<VAL_TEAM_LANES>(a, row, 0, 1, t, [&](int c, V v) {
+            walk_products<VAL_TEAM_LANES, W>(a, row, 0, 1, t, [&](int c, const ValSums<V, W>& v) {
                 const int slot = find_slot(cols, n, c);
-                if (slot >= 0) atomicAdd(&acc[slot], v);  // ds_add_f64 / ds_add_f32
+                if (slot >= 0) {
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        if (w < nw) atomicAdd(&acc[(size_t)w * sl.ne + slot], v.x[w]);  // ds_add_f64 / ds_add_f32
+                }
             });
         vwave_sync();
-        for (int p = t; p < n; p += VAL_TEAM_LANES) a.C.val[s + p] = acc[p];
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            if (w < nw)
+                for (int p = t; p < n; p += VAL_TEAM_LANES) a.C.val[(long long)w * a.sC + (s + p)] = acc[(size_t)w * sl.ne + p];
         vwave_sync();
     }
 }
 
 // Wave classes: one wave64 per row, WPB rows per block.
-template <class V, bool DIRECT>
+template <class V, int W, bool DIRECT>
 __global__ __launch_bounds__(256) void k_val_wave(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
-    __shared__ ValStage<64, V> stage[WPB];
+    __shared__ ValStage<64, V, W> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     auto sync = [] { vwave_sync(); };
     for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB)
-        row_sums<DIRECT>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
+        row_sums<DIRECT, W>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
 }
 
 // Block classes: one block of T threads per row, up to the whole 160 KiB (VAL_BLOCK_BYTES dynamic + the stage).
-template <class V, int T, bool DIRECT>
+template <class V, int W, int T, bool DIRECT>
 __global__ __launch_bounds__(T) void k_val_block(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
-    __shared__ ValStage<VAL_STAGE, V> stage;
+    __shared__ ValStage<VAL_STAGE, V, W> stage;
     auto sync = [] { __syncthreads(); };
     const XcdStretch x = xcd_stretch(count);
     for (int idx = x.begin; idx < x.end; idx += x.step)
-        row_sums<DIRECT>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
+        row_sums<DIRECT, W>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
 }
 
-// Global class: the row's Cval segment is the accumulator.
-template <class V>
+// Global class: the row's Cval segment -- of every set of the pass -- is the accumulator.
+template <class V, int W>
 __global__ __launch_bounds__(1024) void k_val_global(ValArgs<V> a, const int* __restrict__ list, int count) {
     const int t = threadIdx.x;
+    const int nw = val_nw<W>(a);
     for (int idx = blockIdx.x; idx < count; idx += gridDim.x) {
         const int row = list[idx];
         const int s = a.C.ptr[row], n = a.C.ptr[row + 1] - s;
-        for (int p = t; p < n; p += 1024) a.C.val[s + p] = V(0);
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            if (w < nw)
+                for (int p = t; p < n; p += 1024) a.C.val[(long long)w * a.sC + (s + p)] = V(0);
         __threadfence();
         __syncthreads();
-        walk_products<VAL_GROUP>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, V v) {
+        walk_products<VAL_GROUP, W>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, const ValSums<V, W>& v) {
             const int slot = find_slot(a.C.col + s, n, c);
-            if (slot >= 0) unsafeAtomicAdd(&a.C.val[s + slot], v);  // global_atomic_add_f64 / _f32
+            if (slot >= 0) {
+#pragma unroll
+                for (int w = 0; w < W; ++w)  // global_atomic_add_f64 / _f32
+                    if (w < nw) unsafeAtomicAdd(&a.C.val[(long long)w * a.sC + (s + slot)], v.x[w]);
+            }
         });
     }
 }
@@ -336,16 +416,19 @@ __global__ __launch_bounds__(1024) void k_val_global(ValArgs<V> a, const int* __
 // the A column's lower bound in trow[lo0, hi0) and adds av * Bval[tperm[q]] over the equal run (B's
 // duplicates, in B's order).  One sum per entry in a register, in A's entry order: no atomics, the
 // same bits on every call; the entry is stored once, reached or not.  The register sum is a V.
-template <class V>
+// W sets: a value per set in the stage, a register sum per set, the one search per (entry, A column);
+// each set's sum in the order of the unbatched call, so with its bits.
+template <class V, int W>
 struct DotStage {
     int col[64];
-    V av[64];
+    V av[W][64];
 };
-template <class V>
+template <class V, int W>
 __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, const int* __restrict__ list, int count) {
-    __shared__ DotStage<V> stage[WPB];
+    __shared__ DotStage<V, W> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    DotStage<V>& d = stage[wave];
+    const int nw = val_nw<W>(a);
+    DotStage<V, W>& d = stage[wave];
     for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB) {
         const int row = list[idx];
         const int s = a.C.ptr[row], n = a.C.ptr[row + 1] - s;
@@ -358,12 +441,16 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, cons
                 lo0 = tr.tptr[j];
                 hi0 = tr.tptr[j + 1];
             }
-            V sum = V(0);
+            V sum[W];
+#pragma unroll
+            for (int w = 0; w < W; ++w) sum[w] = V(0);
             for (int k0 = a0; k0 < ae; k0 += 64) {
                 const int cnt = ae - k0 < 64 ? ae - k0 : 64;
                 if (lane < cnt) {
                     d.col[lane] = a.A.col[k0 + lane];
-                    d.av[lane] = a.A.val[k0 + lane];
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        if (w < nw) d.av[w][lane] = a.A.val[(long long)w * a.sA + (k0 + lane)];
                 }
                 vwave_sync();
                 if (lo0 < hi0)
@@ -375,11 +462,20 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, cons
                             if (tr.trow[mid] < ac) lo = mid + 1;
                             else hi = mid;
                         }
-                        for (; lo < hi0 && tr.trow[lo] == ac; ++lo) sum += d.av[e] * a.B.val[tr.tperm[lo]];
+                        for (; lo < hi0 && tr.trow[lo] == ac; ++lo) {
+                            const int q = tr.tperm[lo];
+#pragma unroll
+                            for (int w = 0; w < W; ++w)
+                                if (w < nw) sum[w] += d.av[w][e] * a.B.val[(long long)w * a.sB + q];
+                        }
                     }
                 vwave_sync();
             }
-            if (p < n) a.C.val[s + p] = sum;
+            if (p < n) {
+#pragma unroll
+                for (int w = 0; w < W; ++w)
+                    if (w < nw) a.C.val[(long long)w * a.sC + (s + p)] = sum[w];
+            }
         }
     }
 }
@@ -390,22 +486,53 @@ int blocks_for(long long items, int per, int cap) {
     return (int)(b < cap ? b : cap);
 }
 
-// The forward's kernels over the LDS classes' lists (val_lds_kernel), for the value type V
-template <class V>
+// The forward's kernels over the LDS classes' lists (val_lds_kernel), for the value type V and the width W
+template <class V, int W>
 struct ValKernels {
     using Fn = void (*)(ValArgs<V>, const int*, int, int);
-    static Fn team() { return k_val_team<V>; }
+    static Fn team() { return k_val_team<V, W>; }
     template <bool DIRECT>
-    static Fn wave() { return k_val_wave<V, DIRECT>; }
+    static Fn wave() { return k_val_wave<V, W, DIRECT>; }
     template <int T, bool DIRECT>
-    static Fn block() { return k_val_block<V, T, DIRECT>; }
+    static Fn block() { return k_val_block<V, W, T, DIRECT>; }
 };
+
+// The kernels' static LDS is what the plan header says (val_static_lds: tests/valplan_batched_check.cpp sums it
+// with every launch's dynamic bytes)
+template <class V, int W>
+constexpr bool val_static_lds_holds() {
+    return sizeof(ValStage<64, V, W>[WPB]) == val_static_lds(VK_WAVE_DIRECT, sizeof(V), W) &&
+           sizeof(ValStage<VAL_STAGE, V, W>) == val_static_lds(VK_BLOCK_SEARCH, sizeof(V), W) &&
+           sizeof(DotStage<V, W>[WPB]) == val_static_lds(VK_DOT, sizeof(V), W);
+}
+static_assert(val_static_lds_holds<double, 1>() && val_static_lds_holds<double, 2>() && val_static_lds_holds<double, 4>() &&
+                  val_static_lds_holds<float, 1>() && val_static_lds_holds<float, 2>() && val_static_lds_holds<float, 4>(),
+              "val_static_lds is the kernels' static LDS");
+
+// The 1024-thread block kernels of (V, W) for the whole 160 KiB, and the team kernel for its launch cap where
+// that is past what a launch may take unasked (val_team_registers: FP64 at width 4)
+template <class V, int W>
+hipError_t val_register() {
+    hipError_t e = val_allow_max_lds<ValKernels<V, W>>();
+    constexpr int sb = W * (int)sizeof(V);
+    if (e == hipSuccess && val_team_registers(sb))
+        e = hipFuncSetAttribute((const void*)ValKernels<V, W>::team(), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                val_team_launch_cap(sb));
+    return e;
+}
+template <class V>
+hipError_t val_register_widths() {
+    hipError_t e = val_register<V, 1>();
+    if (e == hipSuccess) e = val_register<V, 2>();
+    if (e == hipSuccess) e = val_register<V, 4>();
+    return e;
+}
 
 }  // namespace
 
 hipError_t init_values_attributes() {
-    hipError_t e = val_allow_max_lds<ValKernels<double>>();
-    if (e == hipSuccess) e = val_allow_max_lds<ValKernels<float>>();
+    hipError_t e = val_register_widths<double>();
+    if (e == hipSuccess) e = val_register_widths<float>();
     if (e == hipSuccess) e = init_values_grad_attributes();  // their backward (mhs_values_grad.hip)
     return e;
 }
@@ -441,15 +568,26 @@ void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s) {
     hipLaunchKernelGGL(k_val_verify, dim3(blocks_for(p.M, WPB, 16384)), dim3(256), 0, s, p, bad);
 }
 
-template <class V>
-void issue_values(const ValLaunch& l, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s) {
+namespace {
+template <class V, int W>
+void issue_width(const ValLaunch& l, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s) {
     const dim3 g(l.grid), b(l.block);
-    if (const typename ValKernels<V>::Fn k = val_lds_kernel<ValKernels<V>>(l.kernel, l.block))
+    if (const typename ValKernels<V, W>::Fn k = val_lds_kernel<ValKernels<V, W>>(l.kernel, l.block))
         hipLaunchKernelGGL(k, g, b, l.lds, s, a, list, l.count, l.region);
-    else if (l.kernel == VK_GLOBAL) hipLaunchKernelGGL(k_val_global<V>, g, b, 0, s, a, list, l.count);
-    else if (l.kernel == VK_DOT) hipLaunchKernelGGL(k_val_dot<V>, g, b, 0, s, a, t, list, l.count);
+    else if (l.kernel == VK_GLOBAL) hipLaunchKernelGGL((k_val_global<V, W>), g, b, 0, s, a, list, l.count);
+    else if (l.kernel == VK_DOT) hipLaunchKernelGGL((k_val_dot<V, W>), g, b, 0, s, a, t, list, l.count);
 }
-template void issue_values<double>(const ValLaunch&, const ValArgs<double>&, const ValTrans&, const int*, hipStream_t);
-template void issue_values<float>(const ValLaunch&, const ValArgs<float>&, const ValTrans&, const int*, hipStream_t);
+}  // namespace
+
+template <class V>
+void issue_values(const ValLaunch& l, int width, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s) {
+    switch (width) {  // (a width that is none of these made no plan: nothing to launch)
+    case 1: return issue_width<V, 1>(l, a, t, list, s);
+    case 2: return issue_width<V, 2>(l, a, t, list, s);
+    case 4: return issue_width<V, 4>(l, a, t, list, s);
+    }
+}
+template void issue_values<double>(const ValLaunch&, int, const ValArgs<double>&, const ValTrans&, const int*, hipStream_t);
+template void issue_values<float>(const ValLaunch&, int, const ValArgs<float>&, const ValTrans&, const int*, hipStream_t);
 
 }  // namespace mhs

@@ -9,6 +9,9 @@
 // run_values: the plan's launch list issued on the context's stream, timed by the plan's event pair when asked.
 // A plan has one value type (mhs_dtype), fixed at creation: its classes, lists and launch plans are computed
 // for that type's size, and a call of the other type is refused before any HIP call.
+// A plan also has a width (mhs_values_plan_create_batched: 1, 2 or 4 value sets per walk), fixed likewise: it
+// classifies at the sum bytes width x size.  Every forward call is spgemm_values_batched: ceil(nb / width)
+// passes of the launch list inside the one run_values frame; the unbatched entry points are its nb = 1.
 // Kernels and launchers: mhs_values.hip, mhs_values_grad.hip (declared in mhs_valwalk.hpp); classes,
 // launch plans, counter block and status words: mhs_valplan.hpp.
 #include "mhs_ctx.hpp"
@@ -25,6 +28,7 @@ using namespace mhs;
 struct mhs_values_plan {
     int device = 0;
     int dtype = MHS_F64;    // mhs_dtype: the type of every value array of its calls
+    int width = 1;          // value sets a walk of its forward kernels sums (1, 2 or 4)
     ValPattern pat{};
     long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
     long long kept = 0;    // products that land in C's pattern (masked plans count them; else = products)
@@ -45,6 +49,9 @@ struct mhs_values_plan {
 namespace {
 
 constexpr int dtype_bytes(int dtype) { return dtype == MHS_F32 ? VAL_VB_F32 : VAL_VB_F64; }
+// The bytes a plan classifies at: its width x its value's size
+int sum_bytes(const mhs_values_plan* p) { return p->width * dtype_bytes(p->dtype); }
+static_assert(MHS_VAL_WIDTH_MAX == VAL_WIDTH_MAX, "the header's width is the plan's");
 const char* dtype_name(int dtype) { return dtype == MHS_F32 ? "FP32" : "FP64"; }
 template <class V>
 constexpr int dtype_of() {
@@ -133,7 +140,7 @@ struct PlanBuild {
     }
     // 3. classes, lists, and every product's column looked up in its C row
     void classify_and_verify() {
-        launch_val_classify(p->pat, dtype_bytes(p->dtype), d_cnt, p->lists, s);
+        launch_val_classify(p->pat, sum_bytes(p), d_cnt, p->lists, s);
         launch_val_verify(p->pat, d_status + VS_PRODUCTS, s);
     }
     // 3m. a mask: B^T's pattern for the dot class (its sort indexes by B's columns: checked first; its scratch
@@ -164,8 +171,7 @@ struct PlanBuild {
             if (const int rc = hip(e, "mhs_values_plan_create: B^T")) return rc;
             p->trans = ValTrans{tptr, trow, tperm};
         }
-        launch_val_classify_masked(p->pat, ValMask{p->trans.tptr, form, val_dot_ratio()}, dtype_bytes(p->dtype), d_cnt, p->lists,
-                                   s);
+        launch_val_classify_masked(p->pat, ValMask{p->trans.tptr, form, val_dot_ratio()}, sum_bytes(p), d_cnt, p->lists, s);
         launch_val_count_kept(p->pat, d_cnt, s);
         return MHS_OK;
     }
@@ -193,21 +199,24 @@ struct PlanBuild {
             p->tmem_bytes = 0;
             p->trans = ValTrans{};
         }
-        p->plan = plan_values(p->counts, dtype_bytes(p->dtype));
-        p->gplan = plan_grad(p->counts, dtype_bytes(p->dtype));
+        p->plan = plan_values(p->counts, sum_bytes(p));
+        if (p->width == 1) p->gplan = plan_grad(p->counts, sum_bytes(p));  // (no backward on a batched plan)
         return MHS_OK;
     }
 };
 
 // mhs_values_plan_create (masked false: C must contain the product's pattern) and
 // mhs_values_plan_create_masked (C is a mask; form: mhs_mask_form), for values of `dtype` (mhs_dtype).
+// width: the value sets a walk sums (mhs_values_plan_create_batched; 1 for every other entry point).
 int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form, int dtype,
-                       mhs_values_plan** out) {
+                       int width, mhs_values_plan** out) {
     if (!ctx) return MHS_ERR_INVALID;
     if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
     *out = nullptr;
     if (dtype != MHS_F64 && dtype != MHS_F32)
         return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: dtype is not an mhs_dtype (MHS_F64 or MHS_F32)");
+    if (!val_width_ok(width))
+        return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: width " + std::to_string(width) + " is not 1, 2 or 4");
     if (masked && (form < MHS_MASK_AUTO || form > MHS_MASK_DOT))
         return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: form is not an mhs_mask_form");
     if (A->M < 0 || A->N < 0 || A->nnz < 0 || B->M < 0 || B->N < 0 || B->nnz < 0 || C->M < 0 || C->N < 0 || C->nnz < 0)
@@ -222,6 +231,7 @@ int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const m
     mhs_values_plan* p = new mhs_values_plan();
     p->device = ctx->device;
     p->dtype = dtype;
+    p->width = width;
     p->pat = ValPattern{A->M, A->ptr, A->col, B->ptr, B->col, C->ptr, C->col};
     p->nnzA = A->nnz, p->nnzB = B->nnz, p->nnzC = C->nnz;
     Scratch sort_tmp;  // (B^T's sort scratch: it outlives the build's last step, which syncs the stream either way)
@@ -275,19 +285,46 @@ int check_dtype(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
                     " (the value type is fixed at plan creation: mhs_values_plan_create_typed)");
 }
 
-// mhs_spgemm_values and mhs_spgemm_values_f32
+// Every forward call: mhs_spgemm_values_batched / _f32, and mhs_spgemm_values / _f32 as its nb = 1.  Set b reads
+// Aval + b * sA and Bval + b * sB and writes Cval + b * sC.  The plan's launch list runs once per pass of up to
+// `width` sets; pass q starts at set q * width, and the last one has the sets that remain.
 template <class V>
-int spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V* Bval, V* Cval, double* ms, const char* call) {
+int spgemm_values_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V* Aval, long long sA, const V* Bval, long long sB,
+                          V* Cval, long long sC, double* ms, const char* call) {
     if (!ctx) return MHS_ERR_INVALID;
     if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
     if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (nb < 1) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": nb = " + std::to_string(nb) + " (at least one value set)");
+    if (sA < 0 || sB < 0 || sC < 0) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": negative stride");
+    if ((sA > 0 && sA < p->nnzA) || (sB > 0 && sB < p->nnzB))
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string(call) + ": an input stride is 0 (one array shared by all sets) or at least the matrix's nnz");
+    if (nb > 1 && sC < p->nnzC)
+        return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": strideC is below nnz(C): the sets' outputs would overlap");
     if ((p->nnzA > 0 && !Aval) || (p->nnzB > 0 && !Bval) || (p->nnzC > 0 && !Cval))
         return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null value array");
     if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
-    const ValArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, Cval}};
+    const int W = p->width, passes = (nb + W - 1) / W;
     return run_values(
         ctx, p, p->plan, ms, [](hipStream_t) { return MHS_OK; },
-        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values(l, a, p->trans, list, s); });
+        [&](const ValLaunch& l, const int* list, hipStream_t s) {
+            for (int q = 0; q < passes; ++q) {
+                const long long b = (long long)q * W;
+                ValArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval + b * sA}, {p->pat.Bptr, p->pat.Bcol, Bval + b * sB},
+                             {p->pat.Cptr, p->pat.Ccol, Cval + b * sC}};
+                a.sA = sA, a.sB = sB, a.sC = sC;
+                a.nw = nb - b < W ? (int)(nb - b) : W;
+                issue_values(l, W, a, p->trans, list, s);
+            }
+        });
+}
+
+// Whether the backward may run on the plan: it is built for width 1 only
+int check_grad_width(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
+    if (p->width == 1) return MHS_OK;
+    return fail(ctx, MHS_ERR_INVALID,
+                std::string(call) + ": the backward of batched plans is not built (the plan's width is " + std::to_string(p->width) +
+                    "): a width-1 plan has to be used");
 }
 
 // mhs_spgemm_values_grad and mhs_spgemm_values_grad_f32
@@ -297,6 +334,7 @@ int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V*
     if (!ctx) return MHS_ERR_INVALID;
     if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
     if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (const int rc = check_grad_width(ctx, p, call)) return rc;
     if (!dCval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null dCval");
     if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": no output (dAval and dBval are both null)");
     if ((dAval && !Bval) || (dBval && !Aval))
@@ -318,17 +356,28 @@ int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V*
 }  // namespace
 
 int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, out);
+    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1, out);
 }
 
 int mhs_values_plan_create_masked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int form,
                                   mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, out);
+    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, 1, out);
 }
 
 int mhs_values_plan_create_typed(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                  int dtype, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, out);
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, out);
+}
+
+int mhs_values_plan_create_batched(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
+                                   int dtype, int width, mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, width, out);
+}
+
+int mhs_values_plan_width(const mhs_values_plan* p, int* width) {
+    if (!p || !width) return MHS_ERR_INVALID;
+    *width = p->width;
+    return MHS_OK;
 }
 
 int mhs_values_plan_dtype(const mhs_values_plan* p, int* dtype) {
@@ -344,11 +393,22 @@ int mhs_values_plan_kept(const mhs_values_plan* p, int64_t* kept_products) {
 }
 
 int mhs_spgemm_values(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, double* Cval, double* ms) {
-    return spgemm_values<double>(ctx, p, Aval, Bval, Cval, ms, "mhs_spgemm_values");
+    return spgemm_values_batched<double>(ctx, p, 1, Aval, 0, Bval, 0, Cval, 0, ms, "mhs_spgemm_values");
 }
 
 int mhs_spgemm_values_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, float* Cval, double* ms) {
-    return spgemm_values<float>(ctx, p, Aval, Bval, Cval, ms, "mhs_spgemm_values_f32");
+    return spgemm_values_batched<float>(ctx, p, 1, Aval, 0, Bval, 0, Cval, 0, ms, "mhs_spgemm_values_f32");
+}
+
+int mhs_spgemm_values_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const double* Aval, int64_t strideA, const double* Bval,
+                              int64_t strideB, double* Cval, int64_t strideC, double* ms) {
+    return spgemm_values_batched<double>(ctx, p, nb, Aval, strideA, Bval, strideB, Cval, strideC, ms, "mhs_spgemm_values_batched");
+}
+
+int mhs_spgemm_values_batched_f32(mhs_ctx* ctx, mhs_values_plan* p, int nb, const float* Aval, int64_t strideA, const float* Bval,
+                                  int64_t strideB, float* Cval, int64_t strideC, double* ms) {
+    return spgemm_values_batched<float>(ctx, p, nb, Aval, strideA, Bval, strideB, Cval, strideC, ms,
+                                        "mhs_spgemm_values_batched_f32");
 }
 
 int mhs_spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* dCval,

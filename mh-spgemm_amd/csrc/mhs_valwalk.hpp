@@ -26,11 +26,22 @@ struct ValCsr {
     const int *ptr, *col;
     V* val;
 };
+// A batched call (mhs_spgemm_values_batched) runs the launch list once per pass of up to W value sets, W the
+// plan's width: set w of the pass reads A.val + w * sA and B.val + w * sB and writes C.val + w * sC (strides in
+// elements, 64-bit; 0: the one array shared by all sets), and only the sets w < nw exist -- the others' addresses
+// lie outside the caller's arrays.  The unbatched call is nw = 1.
 template <class V>
 struct ValArgs {
     using Value = V;
     ValCsr<const V> A, B;
     ValCsr<V> C;
+    long long sA = 0, sB = 0, sC = 0;
+    int nw = 1;
+};
+// The products of one B entry with a staged A entry, one per set of the pass
+template <class V, int W>
+struct ValSums {
+    V x[W];
 };
 // The backward's (mhs_spgemm_values_grad).  C.val is G, the cotangent on C's pattern; dA / dB: the gradients,
 // zero-filled by the caller, either nullptr (that side is not computed, and B.val / A.val is then not read).
@@ -61,9 +72,10 @@ void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s);
 void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int vb, int* cnt, int* lists, hipStream_t s);
 void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s);
 // One launch of a values plan (plan_values) over its class's row list, on `s` (t: read by VK_DOT only).
-// V (double or float, both instantiated in mhs_values.hip) must be the type the plan was classified for.
+// V (double or float, both instantiated in mhs_values.hip) and `width` (1, 2 or 4) must be the type and the
+// width the plan was classified for: the kernels' slice guards are taken at width x sizeof(V).
 template <class V>
-void issue_values(const ValLaunch& l, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s);
+void issue_values(const ValLaunch& l, int width, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s);
 // One launch of a values plan's backward (plan_grad) over its class's row list, on `s` (mhs_values_grad.hip).
 template <class V>
 void issue_values_grad(const ValLaunch& l, const ValGradArgs<V>& a, const int* list, hipStream_t s);
@@ -111,22 +123,24 @@ static __device__ __forceinline__ XcdStretch xcd_stretch(int count) {
 
 // The row frame of the LDS classes.  A row's LDS slice is `region` bytes: span-indexed sums of V (direct), or
 // val_slice_entries sums and as many columns behind them (search).  The guards -- val_slice_entries and
-// val_slice_fits of mhs_valplan.hpp, at sizeof(V) -- are all that stands between a pattern that is not the
-// plan's and an overrun of the slice: such a row is left alone.
+// val_slice_fits of mhs_valplan.hpp, at W * sizeof(V), W the sets a walk sums (the backward: 1) -- are all that
+// stands between a pattern that is not the plan's and an overrun of the slice: such a row is left alone.
+// W > 1: the sums are set-major, val[w * pitch + slot] with pitch = span (direct) or ne (search), and the one
+// column array lies behind all W planes.
 template <class V>
 struct ValSlice {
     V* val;
     int* cols;  // (search)
-    int ne;     // entries the slice holds (search)
+    int ne;     // entries the slice holds (search): the pitch of its sum planes
 };
-template <class V>
+template <class V, int W = 1>
 static __device__ __forceinline__ ValSlice<V> search_slice(char* base, int region) {
-    const int ne = val_slice_entries(region, (int)sizeof(V));
-    return {(V*)base, (int*)((V*)base + ne), ne};
+    const int ne = val_slice_entries(region, W * (int)sizeof(V));
+    return {(V*)base, (int*)((V*)base + (size_t)W * ne), ne};
 }
 // A wave's or a block's row: body(s, n, first, span, val, cols) for C's segment [s, s + n) of `row`,
 // when it has entries and fits (direct: columns first .. first + span - 1; search: first = span = 0).
-template <bool DIRECT, class Args, class Body>
+template <bool DIRECT, int W = 1, class Args, class Body>
 __device__ __forceinline__ void val_row(const Args& p, int row, char* base, int region, Body body) {
     using V = typename Args::Value;
     const int s = p.C.ptr[row], n = p.C.ptr[row + 1] - s;
@@ -134,10 +148,10 @@ __device__ __forceinline__ void val_row(const Args& p, int row, char* base, int 
     if constexpr (DIRECT) {
         const int first = p.C.col[s];
         const long long span = (long long)p.C.col[s + n - 1] - first + 1;
-        if (!val_slice_fits(span, region, (int)sizeof(V))) return;
+        if (!val_slice_fits(span, region, W * (int)sizeof(V))) return;
         body(s, n, first, (int)span, (V*)base, (int*)nullptr);
     } else {
-        const ValSlice<V> sl = search_slice<V>(base, region);
+        const ValSlice<V> sl = search_slice<V, W>(base, region);
         if (n > sl.ne) return;
         body(s, n, 0, 0, sl.val, sl.cols);
     }
@@ -156,16 +170,25 @@ __device__ __forceinline__ int val_team_row(const Args& p, const int* list, int 
 }
 
 // Up to CH staged A entries of a row as (B row start, length, A value); entry e of the stage that
-// began at A position k0 is A entry k0 + e.  16 B an entry in FP64, 12 B in FP32.
-template <int CH, class V>
+// began at A position k0 is A entry k0 + e.  16 B an entry in FP64, 12 B in FP32.  A walk of W > 1 sets stages
+// no A value: it reads each set's from A.val at the entry's position, beside the B loads (8 B an entry).
+template <int CH, class V, int W = 1>
 struct ValStage {
+    int bs[CH], len[CH];
+};
+template <int CH, class V>
+struct ValStage<CH, V, 1> {
     int bs[CH], len[CH];
     V av[CH];
 };
 static_assert(sizeof(ValStage<VAL_STAGE, double>) <= VAL_STAGE_BYTES && sizeof(ValStage<VAL_STAGE, float>) <= VAL_STAGE_BYTES &&
-                  sizeof(ValStage<64, double>) <= 1024 && sizeof(ValStage<64, float>) <= 1024,
+                  sizeof(ValStage<64, double>) <= 1024 && sizeof(ValStage<64, float>) <= 1024 &&
+                  sizeof(ValStage<VAL_STAGE, double, VAL_WIDTH_MAX>) <= VAL_STAGE_BYTES && sizeof(ValStage<64, double, 2>) <= 1024,
               "the stage: VAL_STAGE_BYTES per block, 1 KiB per wave");
 constexpr int VAL_PIECES = 8;  // G-wide pieces of a B row a lane group loads before its first sum
+// ... of a walk of W sets: W values a piece, so the values in flight (and their registers) stay VAL_PIECES
+constexpr int val_pieces(int W) { return VAL_PIECES / W; }
+static_assert(val_pieces(1) == VAL_PIECES && val_pieces(VAL_WIDTH_MAX) >= 1, "W = 1 keeps its pieces; the widest walk has one");
 
 // ---------------------------------------------------------------- launch ---
 // The kernel of a launch over an LDS class's list, nullptr for the other kernels.  K names a direction's

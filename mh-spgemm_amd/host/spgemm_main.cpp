@@ -1,7 +1,8 @@
 // spgemm_main.cpp -- the `spgemm <file.mtx>` driver (reference src/main.cu:74-217)
 // on top of the C-ABI, printing the reference's stdout lines.
 //
-//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] <file.mtx>
+//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32]
+//          [--batch NB] [--width W] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -34,6 +35,15 @@
 //             entry against the FP64 call's: within 1.01 m 2^-24 S for an entry of m kept products whose
 //             absolute values sum to S (m and S from FP64 calls on all-ones and on absolute values), and
 //             exactly 0 where m = 0.  Without --f32 nothing is added to the output.
+//   --batch NB [--width W]  a modifier of --reuse: after it, NB seeded value sets of A and B on the product's
+//             pattern, a plan of width W (mhs_values_plan_create_batched; 1, 2 or 4, default 4) and N calls of
+//             mhs_spgemm_values_batched on all NB sets beside N x NB unbatched calls on a width-1 plan: one more
+//             line with both median times (with --f32 one more, on float values), and with --check every set of
+//             the batched call against the unbatched call on the same values.  FP64: both are within
+//             1.01 m 2^-53 S of the exact sum, so within twice that of each other; FP32: the reference is the
+//             unbatched FP64 call on the rounded values and the bound 1.01 m 2^-24 S (m from a call on all-ones;
+//             the seeded values are positive, so S is the FP64 call's own result).  --batch without --reuse,
+//             --width without --batch, NB < 1 or a width that is not 1, 2 or 4: the usage message.
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -267,8 +277,72 @@ static void run_f32(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool 
     }
 }
 
+// --batch NB: NB seeded value sets in one batched call on a plan of `width`, beside NB unbatched calls on a
+// width-1 plan of the same type T; with check every set of the batched call against its reference (see the top).
+template <class T>
+static void run_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int calls, int nb, int width, bool check) {
+    const bool f32 = sizeof(T) == sizeof(float);
+    const char* tag = f32 ? "batched f32" : "batched";
+    try {
+        const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)C.nnz, sets = (size_t)nb;
+        unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
+        auto seeded = [&](size_t n) {                       // in [0.1, 1), as T holds them
+            std::vector<T> v(n);
+            for (size_t i = 0; i < n; ++i) {
+                state = state * 6364136223846793005ULL + 1442695040888963407ULL;
+                v[i] = (T)(0.1 + 0.9 * (double)(state >> 11) / 9007199254740992.0);
+            }
+            return v;
+        };
+        const std::vector<T> va = seeded(sets * nA), vb = seeded(sets * nB);
+        const mhs_dtype dt = f32 ? MHS_F32 : MHS_F64;
+        mhs_shim::ValuesPlan wide(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, width), one(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, 1);
+        DevArr<T> a(sets * nA), b(sets * nB), c(sets * nC), c1(sets * nC);
+        a.put(va), b.put(vb);
+        std::vector<double> tb, tl;
+        for (int i = 0; i < calls; ++i) {
+            MH_spgemm_values_batched(nb, a.p, (int64_t)nA, b.p, (int64_t)nB, c.p, (int64_t)nC, wide);
+            tb.push_back(wide.last_ms);
+        }
+        for (int i = 0; i < calls; ++i) {
+            double sum = 0;
+            for (size_t k = 0; k < sets; ++k) {
+                MH_spgemm_values_batched(1, a.p + k * nA, 0, b.p + k * nB, 0, c1.p + k * nC, 0, one);
+                sum += one.last_ms;
+            }
+            tl.push_back(sum);
+        }
+        std::printf("MH-SpGEMM values batched %s (%d sets, width %d) median of %d calls is %.3lf ms, %d unbatched calls %.3lf ms\n",
+                    f32 ? "FP32" : "FP64", nb, width, calls, median(tb), nb, median(tl));
+        if (check) {
+            // FP64 calls on a width-1 plan: m per entry from all-ones, and per set the reference / S on the set's values
+            mhs_shim::ValuesPlan p64(tools, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1);
+            DevArr<double> da(nA), db(nB), dc(nC);
+            da.put(std::vector<double>(nA, 1.0)), db.put(std::vector<double>(nB, 1.0));
+            f32_ok(p64.ctx, mhs_spgemm_values(p64.ctx, p64.plan, da.p, db.p, dc.p, nullptr));
+            const std::vector<double> m = dc.get();
+            const std::vector<T> got = c.get();
+            const double u = f32 ? 5.9604644775390625e-8 : 1.1102230246251565e-16, factor = f32 ? 1.01 : 2 * 1.01;
+            bool ok = true;
+            for (size_t k = 0; k < sets && ok; ++k) {
+                da.put(std::vector<double>(va.begin() + k * nA, va.begin() + (k + 1) * nA));
+                db.put(std::vector<double>(vb.begin() + k * nB, vb.begin() + (k + 1) * nB));
+                f32_ok(p64.ctx, mhs_spgemm_values(p64.ctx, p64.plan, da.p, db.p, dc.p, nullptr));
+                const std::vector<double> ref = dc.get();  // (positive values: also S)
+                for (size_t i = 0; i < nC && ok; ++i) {
+                    const double mm = std::floor(m[i] + 0.5), g = (double)got[k * nC + i];
+                    ok = mm == 0 ? g == 0.0 : std::fabs(g - ref[i]) <= factor * mm * u * ref[i];
+                }
+            }
+            std::printf("%s %s\n", tag, ok ? "pass" : "error");
+        }
+    } catch (const std::exception&) {
+        std::printf("%s error\n", tag);
+    }
+}
+
 int main(int argc, char** argv) {
-    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0;
+    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0;
     bool aat = false, vendor = false, check = false, cache = false, f32 = false;
     std::string csv;
     const char* filename = nullptr;
@@ -285,12 +359,19 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--grad") && i + 1 < argc) grad = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--f32")) f32 = true;
+        else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch = std::atoi(argv[++i]), bad = bad || batch < 1;
+        else if (!std::strcmp(argv[i], "--width") && i + 1 < argc) {
+            width = std::atoi(argv[++i]);
+            bad = bad || !(width == 1 || width == 2 || width == 4);
+        }
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
+    if ((batch > 0 && reuse <= 0) || (width > 0 && batch <= 0)) bad = true;  // (modifiers of --reuse and of --batch)
+    if (width == 0) width = MHS_VAL_WIDTH_MAX;
     if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0 || grad < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--batch NB] [--width W] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -412,6 +493,10 @@ int main(int argc, char** argv) {
                 mask.d_ptr = mask.d_col = nullptr;  // A's
             }
             if (grad > 0) run_f32(tools, A, B, C, false, true, grad, check, "values backward (both gradients)", "grad");
+        }
+        if (batch > 0) {
+            run_batch<double>(tools, A, B, C, reuse, batch, width, check);
+            if (f32) run_batch<float>(tools, A, B, C, reuse, batch, width, check);
         }
         C.d_release_csr();
     } catch (const std::exception&) {

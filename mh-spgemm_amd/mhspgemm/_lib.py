@@ -35,6 +35,7 @@ MHS_MASK_DOT = 2
 # mhs_dtype: the value type of a values plan
 MHS_F64 = 0
 MHS_F32 = 1
+MHS_VAL_WIDTH_MAX = 4  # a values plan's width is 1, 2 or 4
 
 STATUS_NAMES = {0: "MHS_OK", 1: "MHS_ERR_HIP", 2: "MHS_ERR_OOM", 3: "MHS_ERR_INVALID",
                 4: "MHS_ERR_OVERFLOW", 5: "MHS_ERR_IO"}
@@ -176,6 +177,17 @@ def lib() -> ctypes.CDLL:
             L.mhs_spgemm_values_grad_f32.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                      P(ctypes.c_double)]
             L.mhs_spgemm_values_grad_f32.restype = c_int
+        if hasattr(L, "mhs_values_plan_create_batched"):  # (batched values calls: a later addition to ABI 10)
+            c_int64 = ctypes.c_int64
+            L.mhs_values_plan_create_batched.argtypes = [c_void_p, P(mhs_csr), P(mhs_csr), P(mhs_csr), c_int, c_int, c_int,
+                                                         c_int, P(c_void_p)]
+            L.mhs_values_plan_create_batched.restype = c_int
+            L.mhs_values_plan_width.argtypes = [c_void_p, P(c_int)]
+            L.mhs_values_plan_width.restype = c_int
+            for fn in (L.mhs_spgemm_values_batched, L.mhs_spgemm_values_batched_f32):
+                fn.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                               P(ctypes.c_double)]
+                fn.restype = c_int
     if hasattr(L, "mhs_ctx_fence_default_stream"):  # (a later addition to ABI 10)
         L.mhs_ctx_fence_default_stream.argtypes = [c_void_p, c_int]
         L.mhs_ctx_fence_default_stream.restype = c_int

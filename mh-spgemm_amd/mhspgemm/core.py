@@ -370,6 +370,14 @@ def spgemm(tool: Tool, A: CSR, B: CSR, timing: bool = True):
 VALUES_CLASSES = ("none", "team", "wave_direct", "wave_search", "block_direct", "block_search", "global", "dot")
 MASK_FORMS = {"auto": L.MHS_MASK_AUTO, "product": L.MHS_MASK_PRODUCT, "dot": L.MHS_MASK_DOT}
 VALUES_DTYPES = {"float64": L.MHS_F64, "float32": L.MHS_F32}
+VALUES_WIDTHS = (1, 2, 4)
+
+
+def values_width(width) -> int:
+    """A values plan's ``width`` argument as an int: 1, 2 or 4.  ValueError for anything else."""
+    if isinstance(width, bool) or not isinstance(width, int) or width not in VALUES_WIDTHS:
+        raise ValueError(f"width: one of {VALUES_WIDTHS}, not {width!r}")
+    return int(width)
 
 
 def values_dtype_name(dtype) -> str:
@@ -403,15 +411,22 @@ class ValuesPlan:
     ``dtype`` (``torch.float64``, the default, or ``torch.float32``; also by name) is the plan's value type,
     fixed at creation (mhs_values_plan_create_typed): rows are classified for its size, every tensor of
     ``run``, ``grad`` and ``apply`` must have it (``ValueError`` otherwise) and outputs are allocated in it.
-    On a float32 plan ``Aval`` and ``Bval`` must be given: the operands' own ``d_val`` is FP64."""
+    On a float32 plan ``Aval`` and ``Bval`` must be given: the operands' own ``d_val`` is FP64.
 
-    def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto", dtype="float64"):
+    ``width`` (1, the default, 2 or 4; mhs_values_plan_create_batched) is the number of value sets one walk of the
+    patterns sums in ``run_batched``: rows are classified for ``width`` sums per C entry, so ``info()`` differs
+    from the width-1 plan's.  Any plan runs any batch; a width > 1 plan has no ``grad`` and no ``apply``."""
+
+    def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto", dtype="float64", width=1):
+        self.width = values_width(width)
         if not hasattr(L.lib(), "mhs_values_plan_create"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no values-only entry points")
         if masked and not hasattr(L.lib(), "mhs_values_plan_create_masked"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no masked entry points")
         self.dtype_name = values_dtype_name(dtype)
         self.f32 = self.dtype_name == "float32"
+        if self.width > 1 and not hasattr(L.lib(), "mhs_values_plan_create_batched"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no batched values entry points")
         if self.f32 and not hasattr(L.lib(), "mhs_values_plan_create_typed"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no FP32 values entry points")
         if isinstance(form, str):
@@ -429,7 +444,12 @@ class ValuesPlan:
         self.nnzA, self.nnzB, self.nnzC = int(a.nnz), int(b.nnz), int(c.nnz)
         self.plan = ctypes.c_void_p()
         self._pad = None
-        if self.f32:
+        if self.width > 1:
+            rc = L.lib().mhs_values_plan_create_batched(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                        int(self.masked), self.form, VALUES_DTYPES[self.dtype_name],
+                                                        self.width, ctypes.byref(self.plan))
+            _check(tool.ctx, rc, "mhs_values_plan_create_batched")
+        elif self.f32:
             rc = L.lib().mhs_values_plan_create_typed(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
                                                       int(self.masked), self.form, L.MHS_F32, ctypes.byref(self.plan))
             _check(tool.ctx, rc, "mhs_values_plan_create_typed")
@@ -484,6 +504,60 @@ class ValuesPlan:
         _check(self.tool.ctx, rc, "mhs_spgemm_values_f32" if self.f32 else "mhs_spgemm_values")
         return float(ms.value) if timed else None
 
+    def _sets(self, t, nnz, what):
+        """A batched operand: ``[nb, nnz]`` (inner stride 1, row stride >= nnz) or ``[nnz]`` (shared by all sets).
+        Returns (pointer, stride in elements, nb or None)."""
+        torch = _torch()
+        if not (isinstance(t, torch.Tensor) and t.dtype == self.dtype and t.dim() in (1, 2)):
+            got = f" (got {t.dtype})" if isinstance(t, torch.Tensor) and t.dtype != self.dtype else ""
+            raise ValueError(f"{what}: a {self.dtype_name} tensor of shape [nb, {nnz}] or [{nnz}]{got}")
+        if t.shape[-1] != nnz or (nnz > 1 and t.stride(-1) != 1):
+            raise ValueError(f"{what}: {nnz} entries per set with inner stride 1, not shape {tuple(t.shape)} "
+                             f"stride {tuple(t.stride())}")
+        if t.dim() == 1:
+            return (t.data_ptr() if nnz else None), 0, None
+        nb = int(t.shape[0])
+        if nb < 1:
+            raise ValueError(f"{what}: at least one value set")
+        stride = int(t.stride(0)) if nb > 1 else max(int(t.stride(0)), nnz)
+        if stride < nnz:
+            raise ValueError(f"{what}: a row stride of at least {nnz}, not {stride}")
+        return (t.data_ptr() if nnz else None), stride, nb
+
+    def run_batched(self, Aval, Bval, out=None, timed: bool = False):
+        """C's values for ``nb`` value sets in one call (mhs_spgemm_values_batched): ``Aval`` / ``Bval`` are device
+        tensors of the plan's dtype shaped ``[nb, nnz]`` (any row stride >= nnz, inner stride 1) or ``[nnz]`` (one
+        array shared by all sets); ``nb`` comes from whichever is 2-D (both 1-D: 1).  ``out``: ``[nb, nnz(C)]``, row
+        stride >= nnz(C); allocated when not given.  Returns ``out``, or ``(out, ms)`` when ``timed``.  The plan's
+        width sets share each walk of the patterns; a width-1 plan runs the unbatched kernels ``nb`` times."""
+        if not self.plan:
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "ValuesPlan.run_batched: the plan is closed")
+        if not hasattr(L.lib(), "mhs_spgemm_values_batched"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no batched values entry points")
+        torch = _torch()
+        av, sa, na = self._sets(Aval, self.nnzA, "Aval")
+        bv, sb, nb_ = self._sets(Bval, self.nnzB, "Bval")
+        if na is not None and nb_ is not None and na != nb_:
+            raise ValueError(f"Aval has {na} value sets, Bval {nb_}")
+        nb = na if na is not None else nb_ if nb_ is not None else 1
+        if out is None:
+            if not (Aval.is_cuda and Bval.is_cuda):
+                raise ValueError("Aval, Bval: device tensors")
+            out = torch.empty((nb, self.nnzC), dtype=self.dtype, device=Aval.device)
+        if not (isinstance(out, torch.Tensor) and out.dim() == 2):
+            raise ValueError(f"out: a {self.dtype_name} tensor of shape [{nb}, {self.nnzC}]")
+        cv, sc, nc = self._sets(out, self.nnzC, "out")
+        if nc != nb:
+            raise ValueError(f"out has {nc} value sets, the inputs {nb}")
+        for t, what in ((Aval, "Aval"), (Bval, "Bval"), (out, "out")):
+            if not t.is_cuda:
+                raise ValueError(f"{what}: a device tensor")
+        ms = ctypes.c_double(0.0)
+        name = "mhs_spgemm_values_batched_f32" if self.f32 else "mhs_spgemm_values_batched"
+        rc = getattr(L.lib(), name)(self.tool.ctx, self.plan, nb, av, sa, bv, sb, cv, sc, ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, name)
+        return (out, float(ms.value)) if timed else out
+
     def grad(self, dC, Aval=None, Bval=None, need_A: bool = True, need_B: bool = True, out_A=None, out_B=None,
              timed: bool = False):
         """The backward of ``run`` (mhs_spgemm_values_grad): for the cotangent ``dC`` on C's pattern (nnz(C)
@@ -527,6 +601,9 @@ class ValuesPlan:
         (once differentiable).  Both are ordered on torch's current stream, also with MHS_OPT_SYNC 0: a stream
         of torch's making is handed to the tool; torch's default stream (the null stream, handle 0) cannot be,
         so there the calls run on the tool's own stream between two fences (``Tool.fence_default_stream``)."""
+        if self.width > 1:  # no backward on a batched plan: the library's refusal, before the forward runs
+            call = L.lib().mhs_spgemm_values_grad_f32 if self.f32 else L.lib().mhs_spgemm_values_grad
+            _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None, None), "ValuesPlan.apply")
         return _values_function().apply(self, Aval, Bval)
 
     def _ordered_on_current_stream(self, call):
@@ -545,8 +622,8 @@ class ValuesPlan:
 
     def info(self) -> dict:
         """Rows per class (by name and as the ``rows`` list indexed by class id), products, nnzC, plan_bytes,
-        kept_products: the products that land in C's pattern (all of them unless the plan is masked), and dtype:
-        the plan's value type by name (as the library reports it)."""
+        kept_products: the products that land in C's pattern (all of them unless the plan is masked), dtype:
+        the plan's value type by name, and width: its value sets per walk (both as the library reports them)."""
         i = L.mhs_values_info()
         _check(self.tool.ctx, L.lib().mhs_values_plan_info(self.plan, ctypes.byref(i)), "mhs_values_plan_info")
         rows = [int(x) for x in i.rows]
@@ -562,6 +639,11 @@ class ValuesPlan:
             dt = ctypes.c_int(0)
             _check(self.tool.ctx, L.lib().mhs_values_plan_dtype(self.plan, ctypes.byref(dt)), "mhs_values_plan_dtype")
             d["dtype"] = {v: k for k, v in VALUES_DTYPES.items()}[int(dt.value)]
+        d["width"] = 1
+        if hasattr(L.lib(), "mhs_values_plan_width"):
+            w = ctypes.c_int(0)
+            _check(self.tool.ctx, L.lib().mhs_values_plan_width(self.plan, ctypes.byref(w)), "mhs_values_plan_width")
+            d["width"] = int(w.value)
         return d
 
     def close(self):
