@@ -11,6 +11,8 @@
 //   class mhs_shim::ValuesPlan                               owns an mhs_values_plan
 //   void MH_spgemm_values(const CSR&, const CSR&, CSR&, mhs_shim::ValuesPlan&)
 //   void MH_spgemm_values_batched(nb, Aval, strideA, Bval, strideB, Cval, strideC, mhs_shim::ValuesPlan&)
+//   void MH_spgemm_values_grad_batched(nb, Aval, strideA, Bval, strideB, dC, strideG, dA, strideDA, dB, strideDB,
+//                                      mhs_shim::ValuesPlan&)
 //
 // Errors: the C-ABI returns codes; this shim rethrows as std::runtime_error so a
 // caller's try { MH_spgemm(...) } catch (...) { "MH-SpGEMM failed!!!" } behaves as
@@ -362,6 +364,31 @@ inline void MH_spgemm_values_batched(int nb, const float* Aval, int64_t strideA,
                                      int64_t strideC, mhs_shim::ValuesPlan& plan) {
     const int rc =
         mhs_spgemm_values_batched_f32(plan.ctx, plan.plan, nb, Aval, strideA, Bval, strideB, Cval, strideC, &plan.last_ms);
+    if (rc != MHS_OK) {
+        std::printf("%s\n", mhs_last_error(plan.ctx));
+        throw std::runtime_error(mhs_last_error(plan.ctx));
+    }
+}
+
+// The backward of MH_spgemm_values_batched (mhs_spgemm_values_grad_batched / _f32), on a plan of any width: set b
+// reads Aval + b * strideA, Bval + b * strideB and the cotangent dC + b * strideG and writes dA + b * strideDA and
+// dB + b * strideDB (either output nullptr: not computed, and the other operand's values are then not read).
+// Gradients come back per set: strideG, strideDA and strideDB are at least nnz(C), nnz(A) and nnz(B) when nb > 1.
+inline void MH_spgemm_values_grad_batched(int nb, const double* Aval, int64_t strideA, const double* Bval, int64_t strideB,
+                                          const double* dC, int64_t strideG, double* dA, int64_t strideDA, double* dB,
+                                          int64_t strideDB, mhs_shim::ValuesPlan& plan) {
+    const int rc = mhs_spgemm_values_grad_batched(plan.ctx, plan.plan, nb, Aval, strideA, Bval, strideB, dC, strideG, dA, strideDA,
+                                                  dB, strideDB, &plan.last_ms);
+    if (rc != MHS_OK) {
+        std::printf("%s\n", mhs_last_error(plan.ctx));
+        throw std::runtime_error(mhs_last_error(plan.ctx));
+    }
+}
+inline void MH_spgemm_values_grad_batched(int nb, const float* Aval, int64_t strideA, const float* Bval, int64_t strideB,
+                                          const float* dC, int64_t strideG, float* dA, int64_t strideDA, float* dB,
+                                          int64_t strideDB, mhs_shim::ValuesPlan& plan) {
+    const int rc = mhs_spgemm_values_grad_batched_f32(plan.ctx, plan.plan, nb, Aval, strideA, Bval, strideB, dC, strideG, dA,
+                                                      strideDA, dB, strideDB, &plan.last_ms);
     if (rc != MHS_OK) {
         std::printf("%s\n", mhs_last_error(plan.ctx));
         throw std::runtime_error(mhs_last_error(plan.ctx));

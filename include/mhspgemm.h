@@ -327,7 +327,8 @@ int mhs_spgemm_values_grad_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float 
  * synchronise.  Refused with MHS_ERR_INVALID and a message before any HIP call, writing nothing: nb < 1, a
  * negative stride, an input stride between 1 and nnz - 1, strideC < nnz(C) with nb > 1, a needed array NULL,
  * a call of the wrong type, a plan of another device.  mhs_spgemm_values_grad / _f32 on a plan of width > 1 is
- * refused likewise: the backward of batched plans is not built (the next step); use a width-1 plan.
+ * refused likewise (those two entry points serve width-1 plans); the backward of a batched call on a plan of any
+ * width is mhs_spgemm_values_grad_batched, below.
  * Additions to ABI version 10, like the entries above. */
 #define MHS_VAL_WIDTH_MAX 4
 int mhs_values_plan_create_batched(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
@@ -340,6 +341,47 @@ int mhs_spgemm_values_batched(mhs_ctx *ctx, mhs_values_plan *plan, int nb,
 int mhs_spgemm_values_batched_f32(mhs_ctx *ctx, mhs_values_plan *plan, int nb,
                                   const float *Aval, int64_t strideA, const float *Bval, int64_t strideB,
                                   float *Cval, int64_t strideC, double *ms);
+
+/* ---- the backward of a batched values call: W cotangent sets in one walk of the pattern -------
+ * The adjoint of mhs_spgemm_values_batched, for the same callers when they train or compute sensitivities.  It
+ * runs on a plan of any width W: the pattern work of a product -- the B column, the slot in C's row, the staged
+ * B-row bounds -- is done once for W sets, the value loads, the register sums of dAval and the atomics of dBval W
+ * times.  The LDS a class holds W sums per C entry in holds W cotangents per C entry here, so the classes are the
+ * forward's.
+ * Set b (0 <= b < nb) reads Aval + b * strideA, Bval + b * strideB and dCval + b * strideG and writes
+ * dAval + b * strideDA and dBval + b * strideDB.  Strides are in elements.  strideA and strideB follow the
+ * forward's rule (0: one array shared by all sets, otherwise >= that matrix's nnz).  strideG >= nnz(C),
+ * strideDA >= nnz(A) and strideDB >= nnz(B) whenever nb > 1; 0 is not taken for them: gradients always come back
+ * per set, and the gradient of a shared operand is the caller's sum of them.  Per set everything is
+ * mhs_spgemm_values_grad's contract: either output may be NULL, not both; Bval is read only for dAval and Aval
+ * only for dBval, and the unused one may be NULL; every entry of a requested output segment is written, entries
+ * no kept product reaches exactly 0; masked plans of all three forms are served; dBval is summed by atomics in
+ * any order; dAval has no atomics and a fixed order -- two calls give the same bits, a set gives the same bits
+ * inside any batch and alone, and on finite values without underflow they are the bits of mhs_spgemm_values_grad
+ * on a width-1 plan of the same type with that set's values.  Nothing outside the nb segments is written: padding
+ * between strided sets keeps its bytes.  Outputs must not overlap inputs or each other.
+ * Any nb >= 1 runs on any plan: ceil(nb / W) passes of the backward's launch list, the last with the remaining
+ * sets (on a width-1 plan: nb runs of the unbatched kernels).  ms and MHS_OPT_SYNC as in mhs_spgemm_values (a
+ * timed call brackets all passes); with ms == NULL and MHS_OPT_SYNC 0 the call allocates nothing, reads nothing
+ * back and does not synchronise: it queues one zero fill per requested side, over the nb segments only, and the
+ * kernels.  Cost on MI355X against nb unbatched backward calls on a width-1 plan (nb = 8): where
+ * loads and searches carry the call batching divides it (scircuit-like 0.60-0.80x at W = 2, 0.40-0.59x at FP32 W = 4;
+ * masked triangle 0.58-0.61x at W = 2, 0.33-0.35x at FP32 W = 4, on either side and on both).  dBval on cant-like is
+ * its atomics at every width (0.95-1.00x).  Slower than the loop there: dAval alone at FP64 W = 4 (1.59x; W = 2
+ * 1.02x, FP32 W = 2 1.09x) and the two-sided FP64 W = 4 call (1.01x); and on scircuit-like FP64 W = 4 dBval and the
+ * two-sided call (1.08x).  Use W <= 2 for FP64 on such patterns.
+ * Refused with MHS_ERR_INVALID and a message before any HIP call, writing nothing: nb < 1, a negative stride, an
+ * input stride between 1 and nnz - 1, strideG / strideDA / strideDB below its nnz with nb > 1, NULL dCval, both
+ * outputs NULL, a needed input NULL, a call of the wrong type, a plan of another device.
+ * Additions to ABI version 10, like the entries above. */
+int mhs_spgemm_values_grad_batched(mhs_ctx *ctx, mhs_values_plan *plan, int nb,
+                                   const double *Aval, int64_t strideA, const double *Bval, int64_t strideB,
+                                   const double *dCval, int64_t strideG,
+                                   double *dAval, int64_t strideDA, double *dBval, int64_t strideDB, double *ms);
+int mhs_spgemm_values_grad_batched_f32(mhs_ctx *ctx, mhs_values_plan *plan, int nb,
+                                       const float *Aval, int64_t strideA, const float *Bval, int64_t strideB,
+                                       const float *dCval, int64_t strideG,
+                                       float *dAval, int64_t strideDA, float *dBval, int64_t strideDB, double *ms);
 
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).

@@ -50,12 +50,15 @@
 // A slice holds its sums set-major: acc[w x pitch + slot], pitch the span (direct) or the slice's entry count
 // (search), the one column array behind all W planes.  Counts still do not move.  At sb = 32 the team launch at its
 // cap is 73,728 B, past the VAL_LDS_PLAIN a launch may take unasked: val_team_registers says which team kernels
-// init_values_attributes registers for val_team_launch_cap.  plan_grad is not computed for W > 1.
+// init_values_attributes registers for val_team_launch_cap (the forward's and the backward's alike).  plan_grad takes
+// sb too: a wide plan's backward holds W cotangents per C entry where the forward holds W sums
+// (mhs_spgemm_values_grad_batched).
 //
 // plan_values(counts) is the whole launch plan of a hot call; issue_values (mhs_values.hip) turns one
 // ValLaunch and the call's arrays into a kernel launch.  No pointer and no HIP type in here:
 // tests/valplan_check.cpp runs it on the host.  plan_grad(counts) is the launch plan of the backward
-// (mhs_spgemm_values_grad; issue_values_grad, mhs_values_grad.hip): tests/gradplan_check.cpp.
+// (mhs_spgemm_values_grad and _grad_batched; issue_values_grad, mhs_values_grad.hip): tests/gradplan_check.cpp and
+// tests/gradplan_batched_check.cpp.
 #pragma once
 #include "mhs_shape.hpp"
 
@@ -265,9 +268,10 @@ struct ValPlan {
     ValLaunch launch[VAL_PLAN_MAX];
 };
 
-// Static LDS of a forward kernel at value size vb and width W, beside its launch's dynamic bytes: the stage of A
-// entries of the wave and block walks (B row start and length; the A value too at W = 1 only: wider walks read
-// it from A.val) and the dot class's stage (column and W values).  The kernels assert their stages against it.
+// Static LDS of a forward kernel, and of its backward, at value size vb and width W, beside its launch's dynamic
+// bytes: the stage of A entries of the wave and block walks (B row start and length; the A value too at W = 1 only:
+// wider walks read it from A.val) and the dot class's stage (column and W values).  The kernels assert their stages
+// against it.
 constexpr int val_static_lds(int kernel, int vb, int width) {
     const int entry = 8 + (width == 1 ? vb : 0);
     return kernel == VK_WAVE_DIRECT || kernel == VK_WAVE_SEARCH     ? WPB * 64 * entry
@@ -324,7 +328,8 @@ inline ValPlan plan_values(const ValCounts& c, int vb = VAL_VB_F64) {
     return p;
 }
 
-// The launches of a backward call (mhs_spgemm_values_grad): the forward's, each run by its class's backward
+// The launches of a backward call (mhs_spgemm_values_grad, mhs_spgemm_values_grad_batched; vb: the plan's sum
+// bytes): the forward's, each run by its class's backward
 // kernel (mhs_values_grad.hip), but for the dot rows of a masked plan -- there is no dot-form backward: their
 // list goes to the global-form kernel, a wave per row (block 256; the global class runs it 1024 threads a row).
 inline ValPlan plan_grad(const ValCounts& c, int vb = VAL_VB_F64) {

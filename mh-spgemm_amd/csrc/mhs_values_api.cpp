@@ -11,7 +11,8 @@
 // for that type's size, and a call of the other type is refused before any HIP call.
 // A plan also has a width (mhs_values_plan_create_batched: 1, 2 or 4 value sets per walk), fixed likewise: it
 // classifies at the sum bytes width x size.  Every forward call is spgemm_values_batched: ceil(nb / width)
-// passes of the launch list inside the one run_values frame; the unbatched entry points are its nb = 1.
+// passes of the launch list inside the one run_values frame; the unbatched entry points are its nb = 1.  The
+// batched backward (mhs_spgemm_values_grad_batched) makes the same passes over the backward's launch list.
 // Kernels and launchers: mhs_values.hip, mhs_values_grad.hip (declared in mhs_valwalk.hpp); classes,
 // launch plans, counter block and status words: mhs_valplan.hpp.
 #include "mhs_ctx.hpp"
@@ -200,7 +201,7 @@ struct PlanBuild {
             p->trans = ValTrans{};
         }
         p->plan = plan_values(p->counts, sum_bytes(p));
-        if (p->width == 1) p->gplan = plan_grad(p->counts, sum_bytes(p));  // (no backward on a batched plan)
+        p->gplan = plan_grad(p->counts, sum_bytes(p));  // (a wide plan's serves mhs_spgemm_values_grad_batched)
         return MHS_OK;
     }
 };
@@ -319,7 +320,8 @@ int spgemm_values_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V* Ava
         });
 }
 
-// Whether the backward may run on the plan: it is built for width 1 only
+// Whether the unbatched backward entry points may run on the plan: they serve width 1 only (a plan of any width
+// has mhs_spgemm_values_grad_batched)
 int check_grad_width(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
     if (p->width == 1) return MHS_OK;
     return fail(ctx, MHS_ERR_INVALID,
@@ -350,7 +352,68 @@ int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V*
             if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(V) * (size_t)p->nnzB, s));
             return (int)MHS_OK;
         },
-        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_grad(l, a, list, s); });
+        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_grad(l, 1, a, list, s); });
+}
+
+// Zero fill of nb segments of n values, `stride` elements apart, as one call: a plain fill where the segments
+// are contiguous (or there is one), a 2-D fill -- rows of n values at a pitch of `stride` -- where padding lies
+// between them, which keeps its bytes.
+template <class V>
+hipError_t zero_sets(V* dst, long long n, long long stride, int nb, hipStream_t s) {
+    if (!dst || n <= 0) return hipSuccess;
+    if (nb == 1 || stride == n) return hipMemsetAsync(dst, 0, sizeof(V) * (size_t)n * (size_t)nb, s);
+    return hipMemset2DAsync(dst, sizeof(V) * (size_t)stride, 0, sizeof(V) * (size_t)n, (size_t)nb, s);
+}
+
+// mhs_spgemm_values_grad_batched / _f32: the backward of spgemm_values_batched, on a plan of any width.  Set b reads
+// Aval + b * sA, Bval + b * sB and dCval + b * sG and writes dAval + b * sDA and dBval + b * sDB; the backward's
+// launch list runs once per pass of up to `width` sets, as the forward's does.
+template <class V>
+int spgemm_values_grad_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V* Aval, long long sA, const V* Bval, long long sB,
+                               const V* dCval, long long sG, V* dAval, long long sDA, V* dBval, long long sDB, double* ms,
+                               const char* call) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
+    if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (nb < 1) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": nb = " + std::to_string(nb) + " (at least one value set)");
+    if (sA < 0 || sB < 0 || sG < 0 || sDA < 0 || sDB < 0) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": negative stride");
+    if ((sA > 0 && sA < p->nnzA) || (sB > 0 && sB < p->nnzB))
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string(call) + ": an input stride is 0 (one array shared by all sets) or at least the matrix's nnz");
+    if (nb > 1 && sG < p->nnzC)
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string(call) + ": strideG is below nnz(C): every set has its own cotangent (a stride of 0 is not taken)");
+    if (nb > 1 && ((dAval && sDA < p->nnzA) || (dBval && sDB < p->nnzB)))
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string(call) + ": an output stride (strideDA, strideDB) is below its matrix's nnz: gradients come back per "
+                                        "set, and the sets' outputs would overlap");
+    if (!dCval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null dCval");
+    if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": no output (dAval and dBval are both null)");
+    if ((dAval && !Bval) || (dBval && !Aval))
+        return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": dAval needs Bval, dBval needs Aval");
+    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
+    const int W = p->width, passes = (nb + W - 1) / W;
+    return run_values(
+        ctx, p, p->gplan, ms,
+        [&](hipStream_t s) {
+            // as in the unbatched call, over the nb segments only: one fill call per side
+            MHS_HIP(zero_sets(dAval, p->nnzA, sDA, nb, s));
+            MHS_HIP(zero_sets(dBval, p->nnzB, sDB, nb, s));
+            return (int)MHS_OK;
+        },
+        [&](const ValLaunch& l, const int* list, hipStream_t s) {
+            for (int q = 0; q < passes; ++q) {
+                const long long b = (long long)q * W;
+                ValGradArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval ? Aval + b * sA : nullptr},
+                                 {p->pat.Bptr, p->pat.Bcol, Bval ? Bval + b * sB : nullptr},
+                                 {p->pat.Cptr, p->pat.Ccol, dCval + b * sG},
+                                 dAval ? dAval + b * sDA : nullptr,
+                                 dBval ? dBval + b * sDB : nullptr};
+                a.sA = sA, a.sB = sB, a.sG = sG, a.sDA = sDA, a.sDB = sDB;
+                a.nw = nb - b < W ? (int)(nb - b) : W;
+                issue_values_grad(l, W, a, list, s);
+            }
+        });
 }
 
 }  // namespace
@@ -419,6 +482,20 @@ int mhs_spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval,
 int mhs_spgemm_values_grad_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, const float* dCval,
                                float* dAval, float* dBval, double* ms) {
     return spgemm_values_grad<float>(ctx, p, Aval, Bval, dCval, dAval, dBval, ms, "mhs_spgemm_values_grad_f32");
+}
+
+int mhs_spgemm_values_grad_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const double* Aval, int64_t strideA, const double* Bval,
+                                   int64_t strideB, const double* dCval, int64_t strideG, double* dAval, int64_t strideDA,
+                                   double* dBval, int64_t strideDB, double* ms) {
+    return spgemm_values_grad_batched<double>(ctx, p, nb, Aval, strideA, Bval, strideB, dCval, strideG, dAval, strideDA, dBval,
+                                              strideDB, ms, "mhs_spgemm_values_grad_batched");
+}
+
+int mhs_spgemm_values_grad_batched_f32(mhs_ctx* ctx, mhs_values_plan* p, int nb, const float* Aval, int64_t strideA,
+                                       const float* Bval, int64_t strideB, const float* dCval, int64_t strideG, float* dAval,
+                                       int64_t strideDA, float* dBval, int64_t strideDB, double* ms) {
+    return spgemm_values_grad_batched<float>(ctx, p, nb, Aval, strideA, Bval, strideB, dCval, strideG, dAval, strideDA, dBval,
+                                             strideDB, ms, "mhs_spgemm_values_grad_batched_f32");
 }
 
 int mhs_values_plan_info(const mhs_values_plan* p, mhs_values_info* info) {

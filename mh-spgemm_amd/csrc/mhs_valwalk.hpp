@@ -45,11 +45,17 @@ struct ValSums {
 };
 // The backward's (mhs_spgemm_values_grad).  C.val is G, the cotangent on C's pattern; dA / dB: the gradients,
 // zero-filled by the caller, either nullptr (that side is not computed, and B.val / A.val is then not read).
+// A batched backward (mhs_spgemm_values_grad_batched) runs the launch list once per pass of up to W sets, as the
+// forward does: set w of the pass reads A.val + w * sA, B.val + w * sB (0: shared) and the cotangent C.val + w * sG
+// and writes dA + w * sDA and dB + w * sDB (strides in elements, 64-bit); only the sets w < nw exist.  The unbatched
+// call is nw = 1, and a W = 1 kernel reads no stride.
 template <class V>
 struct ValGradArgs {
     using Value = V;
     ValCsr<const V> A, B, C;
     V *dA, *dB;
+    long long sA = 0, sB = 0, sG = 0, sDA = 0, sDB = 0;
+    int nw = 1;
 };
 // A masked plan's B^T pattern (transpose_pattern of B), read by the dot class only; tptr null: none
 struct ValTrans {
@@ -77,8 +83,10 @@ void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s);
 template <class V>
 void issue_values(const ValLaunch& l, int width, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s);
 // One launch of a values plan's backward (plan_grad) over its class's row list, on `s` (mhs_values_grad.hip).
+// V and `width` as for issue_values: the backward's kernels hold `width` cotangents per C entry where the
+// forward's hold as many sums, behind the same slice guards.
 template <class V>
-void issue_values_grad(const ValLaunch& l, const ValGradArgs<V>& a, const int* list, hipStream_t s);
+void issue_values_grad(const ValLaunch& l, int width, const ValGradArgs<V>& a, const int* list, hipStream_t s);
 hipError_t init_values_grad_attributes();  // (called by init_values_attributes)
 
 // -------------------------------------------------------- device helpers ---
@@ -123,10 +131,10 @@ static __device__ __forceinline__ XcdStretch xcd_stretch(int count) {
 
 // The row frame of the LDS classes.  A row's LDS slice is `region` bytes: span-indexed sums of V (direct), or
 // val_slice_entries sums and as many columns behind them (search).  The guards -- val_slice_entries and
-// val_slice_fits of mhs_valplan.hpp, at W * sizeof(V), W the sets a walk sums (the backward: 1) -- are all that
-// stands between a pattern that is not the plan's and an overrun of the slice: such a row is left alone.
-// W > 1: the sums are set-major, val[w * pitch + slot] with pitch = span (direct) or ne (search), and the one
-// column array lies behind all W planes.
+// val_slice_fits of mhs_valplan.hpp, at W * sizeof(V), W the sets a walk sums (the backward: the cotangent sets it
+// holds) -- are all that stands between a pattern that is not the plan's and an overrun of the slice: such a row is
+// left alone.  W > 1: the sums (the backward: the cotangents) are set-major, val[w * pitch + slot] with pitch = span
+// (direct) or ne (search), and the one column array lies behind all W planes.
 template <class V>
 struct ValSlice {
     V* val;

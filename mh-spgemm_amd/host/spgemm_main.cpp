@@ -44,6 +44,13 @@
 //             unbatched FP64 call on the rounded values and the bound 1.01 m 2^-24 S (m from a call on all-ones;
 //             the seeded values are positive, so S is the FP64 call's own result).  --batch without --reuse,
 //             --width without --batch, NB < 1 or a width that is not 1, 2 or 4: the usage message.
+//             With --grad N as well: after those lines, NB seeded cotangent sets beside the value sets, N calls of
+//             mhs_spgemm_values_grad_batched (both gradients) on the plan of width W beside N x NB calls of
+//             mhs_spgemm_values_grad on the width-1 plan: one more line per type with both median times ("values
+//             grad batched"), and with --check "grad batched pass" / "grad batched error" ("grad batched f32 ..."):
+//             every set of both gradients against the unbatched backward of the same type on that set -- each is
+//             within 1.01 m u S of the exact sum (u = 2^-53 or 2^-24), so within twice that of the other, and
+//             exactly 0 where m = 0 (m from the unbatched backward on all-ones; S: the positive values' own result).
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -341,6 +348,75 @@ static void run_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int
     }
 }
 
+// The unbatched backward on device arrays of either type (mhs_spgemm_values_grad / _f32)
+static void grad_unbatched(mhs_shim::ValuesPlan& p, const double* a, const double* b, const double* g, double* da, double* db) {
+    f32_ok(p.ctx, mhs_spgemm_values_grad(p.ctx, p.plan, a, b, g, da, db, &p.last_ms));
+}
+static void grad_unbatched(mhs_shim::ValuesPlan& p, const float* a, const float* b, const float* g, float* da, float* db) {
+    f32_ok(p.ctx, mhs_spgemm_values_grad_f32(p.ctx, p.plan, a, b, g, da, db, &p.last_ms));
+}
+
+// --grad N with --batch NB: the backward of the batched call, NB seeded value and cotangent sets in one call of
+// mhs_spgemm_values_grad_batched on a plan of `width`, beside NB unbatched backward calls on a width-1 plan of the
+// same type T; with check every set of the batched call against the unbatched call on that set (see the top).
+template <class T>
+static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int calls, int nb, int width, bool check) {
+    const bool f32 = sizeof(T) == sizeof(float);
+    const char* tag = f32 ? "grad batched f32" : "grad batched";
+    try {
+        const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)C.nnz, sets = (size_t)nb;
+        unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
+        auto seeded = [&](size_t n) {                       // in [0.1, 1), as T holds them
+            std::vector<T> v(n);
+            for (size_t i = 0; i < n; ++i) {
+                state = state * 6364136223846793005ULL + 1442695040888963407ULL;
+                v[i] = (T)(0.1 + 0.9 * (double)(state >> 11) / 9007199254740992.0);
+            }
+            return v;
+        };
+        const mhs_dtype dt = f32 ? MHS_F32 : MHS_F64;
+        mhs_shim::ValuesPlan wide(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, width), one(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, 1);
+        DevArr<T> a(sets * nA), b(sets * nB), g(sets * nC), da(sets * nA), db(sets * nB), da1(sets * nA), db1(sets * nB);
+        a.put(seeded(sets * nA)), b.put(seeded(sets * nB)), g.put(seeded(sets * nC));
+        std::vector<double> tb, tl;
+        for (int i = 0; i < calls; ++i) {
+            MH_spgemm_values_grad_batched(nb, a.p, (int64_t)nA, b.p, (int64_t)nB, g.p, (int64_t)nC, da.p, (int64_t)nA, db.p, (int64_t)nB,
+                                          wide);
+            tb.push_back(wide.last_ms);
+        }
+        for (int i = 0; i < calls; ++i) {
+            double sum = 0;
+            for (size_t k = 0; k < sets; ++k) {
+                grad_unbatched(one, a.p + k * nA, b.p + k * nB, g.p + k * nC, da1.p + k * nA, db1.p + k * nB);
+                sum += one.last_ms;
+            }
+            tl.push_back(sum);
+        }
+        std::printf("MH-SpGEMM values grad batched %s (%d sets, width %d) median of %d calls is %.3lf ms, %d unbatched calls %.3lf ms\n",
+                    f32 ? "FP32" : "FP64", nb, width, calls, median(tb), nb, median(tl));
+        if (check) {
+            // m per entry from the unbatched call on all-ones; the seeded values are positive, so a set's unbatched
+            // result is also its S, and the two calls -- each within 1.01 m u S of the exact sum -- differ by at most twice that
+            DevArr<T> ones_a(nA), ones_b(nB), ones_g(nC), ma(nA), mb(nB);
+            ones_a.put(std::vector<T>(nA, (T)1)), ones_b.put(std::vector<T>(nB, (T)1)), ones_g.put(std::vector<T>(nC, (T)1));
+            grad_unbatched(one, ones_a.p, ones_b.p, ones_g.p, ma.p, mb.p);
+            const std::vector<T> mA = ma.get(), mB = mb.get(), gotA = da.get(), gotB = db.get(), refA = da1.get(), refB = db1.get();
+            const double u = f32 ? 5.9604644775390625e-8 : 1.1102230246251565e-16;
+            auto within = [&](const std::vector<T>& got, const std::vector<T>& ref, const std::vector<T>& m, size_t n) {
+                for (size_t k = 0; k < sets; ++k)
+                    for (size_t i = 0; i < n; ++i) {
+                        const double mm = std::floor((double)m[i] + 0.5), x = (double)got[k * n + i], r = (double)ref[k * n + i];
+                        if (mm == 0 ? x != 0.0 : !(std::fabs(x - r) <= 2 * 1.01 * mm * u * r)) return false;
+                    }
+                return true;
+            };
+            std::printf("%s %s\n", tag, within(gotA, refA, mA, nA) && within(gotB, refB, mB, nB) ? "pass" : "error");
+        }
+    } catch (const std::exception&) {
+        std::printf("%s error\n", tag);
+    }
+}
+
 int main(int argc, char** argv) {
     int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0;
     bool aat = false, vendor = false, check = false, cache = false, f32 = false;
@@ -497,6 +573,10 @@ int main(int argc, char** argv) {
         if (batch > 0) {
             run_batch<double>(tools, A, B, C, reuse, batch, width, check);
             if (f32) run_batch<float>(tools, A, B, C, reuse, batch, width, check);
+            if (grad > 0) {
+                run_grad_batch<double>(tools, A, B, C, grad, batch, width, check);
+                if (f32) run_grad_batch<float>(tools, A, B, C, grad, batch, width, check);
+            }
         }
         C.d_release_csr();
     } catch (const std::exception&) {

@@ -188,6 +188,12 @@ def lib() -> ctypes.CDLL:
                 fn.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                P(ctypes.c_double)]
                 fn.restype = c_int
+        if hasattr(L, "mhs_spgemm_values_grad_batched"):  # (the batched backward: a later addition to ABI 10)
+            c_int64 = ctypes.c_int64
+            for fn in (L.mhs_spgemm_values_grad_batched, L.mhs_spgemm_values_grad_batched_f32):
+                fn.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                               c_void_p, c_int64, c_void_p, c_int64, P(ctypes.c_double)]
+                fn.restype = c_int
     if hasattr(L, "mhs_ctx_fence_default_stream"):  # (a later addition to ABI 10)
         L.mhs_ctx_fence_default_stream.argtypes = [c_void_p, c_int]
         L.mhs_ctx_fence_default_stream.restype = c_int

@@ -415,7 +415,9 @@ class ValuesPlan:
 
     ``width`` (1, the default, 2 or 4; mhs_values_plan_create_batched) is the number of value sets one walk of the
     patterns sums in ``run_batched``: rows are classified for ``width`` sums per C entry, so ``info()`` differs
-    from the width-1 plan's.  Any plan runs any batch; a width > 1 plan has no ``grad`` and no ``apply``."""
+    from the width-1 plan's.  Any plan runs any batch.  ``grad_batched`` is the backward of ``run_batched``
+    (mhs_spgemm_values_grad_batched) and ``apply_batched`` the pair as a ``torch.autograd.Function``, both on a plan
+    of any width; the unbatched ``grad`` and ``apply`` serve width-1 plans only."""
 
     def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto", dtype="float64", width=1):
         self.width = values_width(width)
@@ -606,6 +608,81 @@ class ValuesPlan:
             _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None, None), "ValuesPlan.apply")
         return _values_function().apply(self, Aval, Bval)
 
+    def grad_batched(self, dC, Aval, Bval, need_A: bool = True, need_B: bool = True, out_A=None, out_B=None,
+                     timed: bool = False):
+        """The backward of ``run_batched`` (mhs_spgemm_values_grad_batched), on a plan of any width: ``dC`` is the
+        cotangent ``[nb, nnz(C)]``, ``Aval`` / ``Bval`` are ``[nb, nnz]`` or ``[nnz]`` (shared by all sets) as in
+        ``run_batched``; a side's operand that is not needed (``Bval`` with ``need_A=False``, ``Aval`` with
+        ``need_B=False``) may be None.  Returns ``(dA, dB)``, each ``[nb, nnz]`` -- one gradient per set also for a
+        shared operand, whose gradient is their sum over the sets -- into ``out_A`` / ``out_B`` (row stride >= nnz;
+        allocated when not given), with None for a side not asked for, whose buffer is not touched; and
+        ``(dA, dB, ms)`` when ``timed``.  The plan's width sets share each walk of the patterns; a width-1 plan runs
+        the unbatched backward kernels ``nb`` times."""
+        if not self.plan:
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "ValuesPlan.grad_batched: the plan is closed")
+        if not hasattr(L.lib(), "mhs_spgemm_values_grad_batched"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no batched backward entry points")
+        if not (need_A or need_B):
+            raise ValueError("ValuesPlan.grad_batched: need_A or need_B")
+        torch = _torch()
+        if not (isinstance(dC, torch.Tensor) and dC.dim() == 2):
+            raise ValueError(f"dC: a {self.dtype_name} tensor of shape [nb, {self.nnzC}]")
+        gp, sg, nb = self._sets(dC, self.nnzC, "dC")
+        used = [(dC, "dC")]
+        av = bv = pa = pb = None
+        sa = sb = sda = sdb = 0
+        dA = dB = None
+
+        def operand(t, nnz, what):
+            ptr, stride, n = self._sets(t, nnz, what)
+            if n is not None and n != nb:
+                raise ValueError(f"{what} has {n} value sets, dC {nb}")
+            used.append((t, what))
+            return ptr, stride
+
+        def output(t, nnz, what):
+            if t is None:  # (beside dC, which the device check below looks at first)
+                t = torch.empty((nb, nnz), dtype=self.dtype, device=dC.device)
+            if not (isinstance(t, torch.Tensor) and t.dim() == 2):
+                raise ValueError(f"{what}: a {self.dtype_name} tensor of shape [{nb}, {nnz}]")
+            ptr, stride, n = self._sets(t, nnz, what)
+            if n != nb:
+                raise ValueError(f"{what} has {n} value sets, dC {nb}")
+            used.append((t, what))
+            return t, ptr, stride
+
+        if need_B:
+            av, sa = operand(Aval, self.nnzA, "Aval")
+        if need_A:
+            bv, sb = operand(Bval, self.nnzB, "Bval")
+            dA, pa, sda = output(out_A, self.nnzA, "out_A")
+        if need_B:
+            dB, pb, sdb = output(out_B, self.nnzB, "out_B")
+        for t, what in used:
+            if not t.is_cuda:
+                raise ValueError(f"{what}: a device tensor")
+        # (an empty array has no address; the library wants one for every array it is given: nothing reads it)
+        if self._pad is None:
+            self._pad = torch.zeros(1, dtype=self.dtype, device=dC.device)
+        pad = self._pad.data_ptr()
+        if need_A:
+            bv, pa = bv or pad, pa or pad
+        if need_B:
+            av, pb = av or pad, pb or pad
+        ms = ctypes.c_double(0.0)
+        name = "mhs_spgemm_values_grad_batched_f32" if self.f32 else "mhs_spgemm_values_grad_batched"
+        rc = getattr(L.lib(), name)(self.tool.ctx, self.plan, nb, av, sa, bv, sb, gp or pad, sg, pa, sda, pb, sdb,
+                                    ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, name)
+        return (dA, dB, float(ms.value)) if timed else (dA, dB)
+
+    def apply_batched(self, Aval, Bval):
+        """``run_batched`` as a differentiable function of ``Aval`` and ``Bval`` (a ``torch.autograd.Function``), on
+        a plan of any width: the forward is ``run_batched`` into a fresh ``[nb, nnz(C)]`` tensor, the backward
+        ``grad_batched`` for the inputs that need it (once differentiable), both ordered on torch's current stream
+        as in ``apply``.  The gradient of a 1-D (shared) operand is the per-set gradients summed over the sets."""
+        return _values_batched_function().apply(self, Aval, Bval)
+
     def _ordered_on_current_stream(self, call):
         """Run ``call()`` with its library work ordered after what torch's current stream holds, and before
         what it is given next."""
@@ -692,6 +769,46 @@ def _values_function():
 
     _VALUES_FUNCTION = ValuesProduct
     return ValuesProduct
+
+
+_VALUES_BATCHED_FUNCTION = None
+
+
+def _values_batched_function():
+    """The autograd function behind ``ValuesPlan.apply_batched`` (made on first use, as ``_values_function``)."""
+    global _VALUES_BATCHED_FUNCTION
+    if _VALUES_BATCHED_FUNCTION is not None:
+        return _VALUES_BATCHED_FUNCTION
+    torch = _torch()
+    from torch.autograd.function import once_differentiable
+
+    class ValuesBatchedProduct(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, Aval, Bval):
+            out = plan._ordered_on_current_stream(lambda: plan.run_batched(Aval, Bval))
+            ctx.plan = plan
+            ctx.save_for_backward(Aval, Bval)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dC):
+            Aval, Bval = ctx.saved_tensors
+            _, need_A, need_B = ctx.needs_input_grad
+            if not (need_A or need_B):
+                return None, None, None
+            plan, dC = ctx.plan, dC.contiguous()
+            dA, dB = plan._ordered_on_current_stream(
+                lambda: plan.grad_batched(dC, Aval, Bval, need_A=need_A, need_B=need_B))
+            # a shared (1-D) operand took part in every set: its gradient is the sets' summed
+            if dA is not None and Aval.dim() == 1:
+                dA = dA.sum(0)
+            if dB is not None and Bval.dim() == 1:
+                dB = dB.sum(0)
+            return None, dA, dB
+
+    _VALUES_BATCHED_FUNCTION = ValuesBatchedProduct
+    return ValuesBatchedProduct
 
 
 def transpose(tool: Tool, A: CSR) -> CSR:
