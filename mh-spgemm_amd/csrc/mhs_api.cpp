@@ -158,7 +158,7 @@ Layout plan(int M, int MB, long long nnzA, long long nnzB, int mc_list, int M_to
     L.grp = take((size_t)M);
     static_assert((int)NUM_NB >= (int)SYM_NB, "bin_list holds either phase's bins");
     L.bin_list = take((size_t)(NUM_NB - 1) * M * 4);
-    L.blkflop = take(((size_t)analyze_blocks(nnzA, M) + 1) * 8);
+    L.blkflop = take(((size_t)analyze_launch(nnzA, M).words + 1) * 8);
     L.scan_part = take(nscan * 8 + (size_t)ZERO_INTS * 4);  // look-back words, then the row cursors and bin counters
     L.mcache = take((size_t)M * mc_stride(mc_list) * 8);
     L.spill_cap = spill_cap(nnzB);
@@ -238,7 +238,7 @@ Work make_work(mhs_ctx* ctx, const Layout& L, int M, long long nnzA, long long n
     w.tiny_num = ctx->tiny_num ? 1 : 0;  // per row: packed sort keys hold its column offsets in 23 bits
     w.bin_list = (int*)(ctx->ws + L.bin_list);
     w.blkflop = (unsigned long long*)(ctx->ws + L.blkflop);
-    w.nflop = M > 0 ? analyze_blocks(nnzA, M) : 0;
+    w.nflop = analyze_launch(nnzA, M).words;
     w.scan_part = (int*)(ctx->ws + L.scan_part);
     w.cursors = w.scan_part + 2 * ((M + 1 + SCAN_ITEMS - 1) / SCAN_ITEMS + 1);
     w.mcache = ctx->use_mcache ? (unsigned long long*)(ctx->ws + L.mcache) : nullptr;
@@ -296,17 +296,17 @@ void fill_bins(mhs_timing& tm, int M, const int* sym, const int* num) {
 
 // Everything before the numeric launches for the rows of `a` (M > 0): (mask of B), row
 // analysis, symbolic bins, row_ptr scan into Cptr[0..M] + numeric bins, the Stats hand-off.
+// The plans of a pass without the probe, near groups, a fork or a speculated plan, on one stream.
 int front_pass(mhs_ctx* ctx, const Csr& a, const Csr& b, Work& w, int* Cptr, bool mask, Stats& h) {
     hipStream_t s = ctx->stream;
     if (!ctx->stats_zero) MHS_HIP(hipMemsetAsync(w.stats, 0, sizeof(Stats), s));
     ctx->stats_zero = false;
-    if (mask) launch_mask_b(b, w, s);
-    launch_analyze(a, w, b.M, s, Cptr);
-    launch_symbolic_common(a, b, w, a.M, b.N, Cptr, s);
-    launch_symbolic_rare(a, w, a.M, b.N, Cptr, s, false);
-    launch_symbolic_b256(a, w, a.M, b.N, Cptr, s);
+    const FrontShape sh{a.M, b.M, a.nnz, b.nnz, mask};
+    const FrontPointers fp{a, b, w, Cptr, ctx->dense_span_max, ctx->d_pub};
+    for (const FrontPlan& p : {plan_front_rows(sh), plan_front_symbolic(sh, nullptr)})
+        for (int i = 0; i < p.n; ++i) issue_front(p.launch[i], fp, s);
     const int seq = ++ctx->seq;
-    launch_scan_classify(a.M, w, Cptr, a.ptr, s, ctx->dense_span_max, ctx->d_pub, seq, SpecArgs{});
+    issue_front(front_scan(a.M), fp, s, seq);
     MHS_HIP(hipGetLastError());
     const int rc = wait_published(ctx, s, ctx->pub, seq);
     if (rc) return rc;
@@ -595,6 +595,7 @@ struct Call {
     mhs_ctx::PlanKey key{};
     Stats ph{};  // the plan (a copy: this call replaces the context's)
     Stats h{};   // this call's own Stats, after the hand-off
+    FrontPlan fplan{};  // the launches up to the bin lists, then (launch_symbolic) the symbolic ones
     NumPlan nplan{};  // the numeric launches (a speculated call: built by phase A, finished by phase B)
     int seq = 0;            // k_scan's publication
     bool launched = false;  // the plan's phase A went out
@@ -631,6 +632,15 @@ struct Call {
     int prepare_numeric(const Stats& of, bool* no_room);
     int run_or_stamp(const Stats& of, int phase);
     int fill_timing(mhs_timing& tm);
+    FrontShape front_shape() const { return {M, b.M, a.nnz, b.nnz, 1, probe, w.nft, w.sym_big, L.near, fork_sym}; }
+    // one pre-numeric launch on the stream it names; fplan's from *i on, up to and including family `last`
+    void issue(const FrontLaunch& l, int seq_ = 0, const SpecArgs* sa = nullptr) {
+        issue_front(l, {a, b, w, own.out.ptr, ctx->dense_span_max, ctx->d_pub}, l.stream == FRONT_AUX ? ctx->aux[0] : s,
+                    seq_, sa);
+    }
+    void issue_upto(int* i, int last, int seq_ = 0) {
+        for (; *i < fplan.n && fplan.launch[*i].kernel <= last; ++*i) issue(fplan.launch[*i], seq_);
+    }
 };
 
 int check_args(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C) {
@@ -701,7 +711,9 @@ int Call::plan_workspace() {
 // rows (big M): k_analyze also bins the rows that way and counts them (the probe); the host
 // picks the bin lists and sizes the candidates' value slots
 int Call::analyze_rows() {
-    launch_mask_b(b, w, s);
+    fplan = plan_front_rows(front_shape());
+    int i = 0;
+    issue_upto(&i, FK_MASK);
     if (t) MHS_HIP(hipEventRecord(ctx->ev[1], s));
     auto slots = [&](size_t n) {  // the value slots of n entries, if they fit
         if (ensure(ctx, &ctx->slots, &ctx->slots_bytes, n * 12) != MHS_OK) return false;
@@ -716,7 +728,7 @@ int Call::analyze_rows() {
         else (void)hipGetLastError();
     }
     const int seq_probe = probe ? ++ctx->seq : 0;
-    launch_analyze(a, w, b.M, s, own.out.ptr, probe ? ctx->d_pub : nullptr, seq_probe);
+    issue_upto(&i, FK_PROBE_PUBLISH, seq_probe);
     if (probe) {
         MHS_HIP(hipGetLastError());
         const int rc = wait_published(ctx, s, ctx->pub, seq_probe);
@@ -729,8 +741,8 @@ int Call::analyze_rows() {
         // with slots, 19% of its rows past the tiny classes; GAP-road- / delaunay-like -12% / -17%)
         if (!(n > 0 && ctx->nft_slots && other * 100 <= (unsigned long long)M * ctx->nft_other_pct && slots((size_t)n)))
             (void)hipGetLastError();
-        launch_bin_list(a, w, s);
     }
+    issue_upto(&i, FK_BIN_LIST);
     if (t) MHS_HIP(hipEventRecord(ctx->ev[2], s));
     return MHS_OK;
 }
@@ -757,39 +769,35 @@ void Call::choose_plan() {
     ctx->plan_valid = false;  // (set again by this call's success)
 }
 
-// ---- Calculate_C_nnz: persistent grids that read their bins' sizes on the device: no host
-// round trip.  Forked: rows of the rare bins (long, few) run on an aux stream beside the
-// common bins -- their tail no longer idles the chip
+// ---- Calculate_C_nnz: the symbolic plan (plan_front_symbolic decides the launches, what a speculated
+// plan leaves out and the order around the fork); here the fork event, the aux stream's wait ahead
+// of its first launch -- behind the call stream's first: no host call ahead of that one -- and the join
 int Call::launch_symbolic() {
-    int* Cptr = own.out.ptr;
-    const int N = b.N;
-    const Stats* plan_h = spec ? &ph : nullptr;
-    if (fork_sym) {
+    fplan = plan_front_symbolic(front_shape(), spec ? &ph : nullptr);
+    // (a rerun does not speculate -- it leaves nothing out and adds nothing here)
+    ctx->stat[MHS_STAT_SPEC_SKIPPED] += fplan.left_out;
+    int fork = fplan.fork;  // 0: none; 1: forked; 2: the aux stream waits for the fork event; 3: joined
+    if (fork) {
         ctx->stat[MHS_STAT_SYM_FORK] += !rerun;  // (once per user call: a miss has counted its first attempt)
         MHS_HIP(hipEventRecord(ctx->fork_ev, s));
-        if (ctx->fork_common_first) {  // (the call stream's launch first: no host launch ahead of it)
-            launch_symbolic_common(a, b, w, M, N, Cptr, s, plan_h);
+    }
+    auto advance = [&](int to) -> int {  // the fork's steps up to `to`, each once
+        if (fork == 1 && to >= 2) {
             MHS_HIP(hipStreamWaitEvent(ctx->aux[0], ctx->fork_ev, 0));
-            launch_symbolic_rare(a, w, M, N, Cptr, ctx->aux[0], false);
-        } else {
-            MHS_HIP(hipStreamWaitEvent(ctx->aux[0], ctx->fork_ev, 0));
-            launch_symbolic_rare(a, w, M, N, Cptr, ctx->aux[0], false);
-            launch_symbolic_common(a, b, w, M, N, Cptr, s, plan_h);
+            fork = 2;
         }
-        launch_symbolic_b256(a, w, M, N, Cptr, s);
-        MHS_HIP(hipEventRecord(ctx->join_ev[0], ctx->aux[0]));
-        MHS_HIP(hipStreamWaitEvent(s, ctx->join_ev[0], 0));
-        launch_near(a, w, Cptr, s);
-    } else {
-        launch_symbolic_common(a, b, w, M, N, Cptr, s, plan_h);
-        // a speculated plan leaves out the rare bins' launches where the plan's bins are empty
-        // (a row in one of them changes the Stats: k_scan rejects the plan, the call reruns)
-        const bool rare = !spec || ph.sym_count[SYM_WM] > 0 || ph.sym_count[SYM_B1024] > 0 ||
-                          ph.sym_count[SYM_GLOBAL] > 0 || (L.near && ph.near_heads > 0);
-        if (rare) launch_symbolic_rare(a, w, M, N, Cptr, s, true);  // (+ near row groups)
-        if (!spec || ph.sym_count[SYM_B256] > 0) launch_symbolic_b256(a, w, M, N, Cptr, s);
-        // (a rerun does not speculate -- it leaves nothing out and adds nothing here)
-        ctx->stat[MHS_STAT_SPEC_SKIPPED] += (!rare) + (spec && ph.sym_count[SYM_B256] == 0);
+        if (fork == 2 && to >= 3) {
+            MHS_HIP(hipEventRecord(ctx->join_ev[0], ctx->aux[0]));
+            MHS_HIP(hipStreamWaitEvent(s, ctx->join_ev[0], 0));
+            fork = 3;
+        }
+        return MHS_OK;
+    };
+    for (int i = 0; i <= fplan.n; ++i) {  // (past the last launch: what is left of the fork's steps)
+        const FrontLaunch* l = i < fplan.n ? &fplan.launch[i] : nullptr;
+        const int rc = advance(!l || l->after_join ? 3 : l->stream == FRONT_AUX ? 2 : 0);
+        if (rc) return rc;
+        if (l) issue(*l);
     }
     MHS_HIP(hipGetLastError());
     if (t) MHS_HIP(hipEventRecord(ctx->ev[3], s));
@@ -801,8 +809,8 @@ int Call::launch_symbolic() {
 int Call::launch_scan() {
     if (M > 0) {
         seq = ++ctx->seq;
-        launch_scan_classify(M, w, own.out.ptr, a.ptr, s, ctx->dense_span_max, ctx->d_pub, seq,
-                             spec ? SpecArgs{ctx->d_go, ph} : SpecArgs{});
+        const SpecArgs sa{ctx->d_go, ph};
+        issue(front_scan(M), seq, spec ? &sa : nullptr);
         MHS_HIP(hipGetLastError());
     } else {
         MHS_HIP(hipGetLastError());
@@ -1039,7 +1047,6 @@ int mhs_ctx_create(mhs_ctx** out, int device) {
     if (const char* e = getenv("MHS_NFT_OTHER_PCT")) ctx->nft_other_pct = atoi(e);
     if (const char* e = getenv("MHS_NFT_AUTO_AVG")) ctx->nft_auto_avg = atoi(e);
     if (const char* e = getenv("MHS_NO_SPEC")) ctx->spec = atoi(e) == 0;
-    if (const char* e = getenv("MHS_FORK_ORDER")) ctx->fork_common_first = atoi(e) != 0;
     if (const char* e = getenv("MHS_SPEC_FORK")) {
         ctx->spec_fork = atoi(e) == 1;
         ctx->spec_fork_rare = atoi(e) == 2;

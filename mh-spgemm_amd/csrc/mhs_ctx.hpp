@@ -84,10 +84,6 @@ struct mhs_ctx {
     // speculated calls run their plan's rare symbolic rows on an aux stream beside k_sym_common
     // (scircuit-like -3.9 %, the other configs within 0.5 %: r06sf2); MHS_SPEC_FORK=0 turns it off
     bool spec_fork_rare = true;
-    // a forked symbolic pass launches k_sym_common before the aux stream's rare rows (no host launch
-    // ahead of the call stream's: scircuit-like -0.6 %, webbase-like -0.3 %, cage15-like -0.1 %: r06fo);
-    // MHS_FORK_ORDER=0: the rare rows first
-    bool fork_common_first = true;
     int spec_nss = mhs_ctx::NAUX + 1;  // streams of a speculated numeric phase (MHS_SPEC_NSS: a cap, A/B)
     // MHS_SPEC_NO_ROOM=1 (tests): a speculated call behaves as if the plan's C had not fitted -- its phase A
     // stays in (a budget cannot force that: the first call's C fitted under it); other calls are not touched

@@ -16,11 +16,13 @@
 //     ctiles[M] distinct C tiles of row i (symbolic)
 //     C.ptr     nnz of row i (symbolic), then scanned in place to the row_ptr
 //   binning: bin id per row (uint8), per-block bin counts, row lists grouped by bin.
-// The constants, bins, Stats and LDS needs are in mhs_shape.hpp, the numeric launch plan in
-// mhs_numplan.hpp (both HIP-free); this header adds what takes HIP types.
+// The constants, bins, Stats and LDS needs are in mhs_shape.hpp, the pre-numeric launch plans in
+// mhs_frontplan.hpp, the numeric launch plan in mhs_numplan.hpp (all HIP-free); this header adds what
+// takes HIP types: the call's arrays, and issue_front / issue_numeric, which launch one plan entry.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mhs_frontplan.hpp"
 #include "mhs_numplan.hpp"
 
 namespace mhs {
@@ -106,25 +108,18 @@ struct Work {
     int sym_big;       // the numeric-first probe counted >= 2^21 rows past the tiny classes: big symbolic wave grid
 };
 
-void launch_mask_b(const Csr& B, const Work& w, hipStream_t s);
-// Row analysis, then the symbolic bin lists -- or, with w.nft_bin (the numeric-first
-// probe), the candidate counts published as `seq` (the host then calls launch_bin_list)
-void launch_analyze(const Csr& A, const Work& w, int MB, hipStream_t s, int* Cptr, Published* pub = nullptr,
-                    int seq = 0);
-void launch_bin_list(const Csr& A, const Work& w, hipStream_t s);
-
-int analyze_blocks(long long nnzA, int M);
-
-void launch_symbolic_common(const Csr& A, const Csr& B, const Work& w, int M, int N, int* Cptr, hipStream_t s,
-                            const Stats* plan = nullptr);
-// with_near: its phase 0 checks the near row-group candidates (after k_sym_common on the
-// same stream); else launch_near does, once both symbolic launches are done
-void launch_symbolic_rare(const Csr& A, const Work& w, int M, int N, int* Cptr, hipStream_t s, bool with_near);
-void launch_symbolic_b256(const Csr& A, const Work& w, int M, int N, int* Cptr, hipStream_t s);
-// near row groups: verify k_bin_list's candidates after the symbolic pass, build union rows
-void launch_near(const Csr& A, const Work& w, const int* Cptr, hipStream_t s);
-void launch_scan_classify(int M, const Work& w, int* Cptr, const int* Aptr, hipStream_t s, int dense_span_max,
-                          Published* pub, int seq, const SpecArgs& spec);
+// The arrays the pre-numeric launches read and write: the pointer half of a launch, where FrontLaunch
+// is the shape half.  References: the call fills in its Work as the stages go (nft, the value slots).
+struct FrontPointers {
+    const Csr &A, &B;
+    const Work& w;
+    int* Cptr;
+    int dense_span_max;
+    Published* pub;  // where k_probe_publish and k_scan publish
+};
+// One launch of a call's pre-numeric plans (plan_front_rows, plan_front_symbolic, front_scan) on `s`.
+// seq: what FK_PROBE_PUBLISH / FK_SCAN publish; spec: k_scan's check of a speculated plan (null: none).
+void issue_front(const FrontLaunch& l, const FrontPointers& p, hipStream_t s, int seq = 0, const SpecArgs* spec = nullptr);
 // The arrays a call's numeric launches read and write (and the two scalars the kernels take beside
 // them): the pointer half of a launch, where NumLaunch is the shape half.  Built once per call.
 struct NumPointers {

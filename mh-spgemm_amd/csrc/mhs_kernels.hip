@@ -25,8 +25,9 @@
 // wave, no block barriers), block-per-row kernels (256 / 1024 threads, up to 160 KiB
 // of LDS) and a global-memory fallback; rows are walked in XCD-grouped order so that
 // neighbouring rows (which share B rows) run on one XCD's L2.
-// Which numeric kernels a call launches, with which grids and LDS, is plan_numeric
-// (mhs_numplan.hpp); issue_numeric, at the end of this file, launches one entry of that plan.
+// Which kernels a call launches, with which grids and LDS, is decided in two HIP-free headers:
+// mhs_frontplan.hpp (everything up to k_scan) and mhs_numplan.hpp (plan_numeric); issue_front and
+// issue_numeric, at the end of this file, each launch one entry of such a plan.
 #include "mhs_internal.hpp"
 
 #include <hip/hip_ext.h>
@@ -44,23 +45,14 @@ constexpr int MHS_RUN_UNROLL = 2;  // B entries per lane issued together in a ru
 constexpr int MHS_TILE_UNROLL = 2;  // tiles per lane issued together in a tile walk
 constexpr int MHS_UNROLL = 4;  // B entries per lane issued together in the product walk
 constexpr int MHS_UNROLL_BLOCK = 8;  // ... in the block kernels (measured: S1-like rows -9%; the wave kernels keep 4)
-// block cap of each numeric-first symbolic tiny class: 4096, 16384 from 4 M rows (r05ab17/18:
-// delaunay-like 10.26 -> 9.70 ms, GAP-road-like 4.53 -> 4.43 at 16384, but mac_econ-, scircuit-like
-// +5-6 %; 512-2048 slower on every huge matrix, delaunay-like up to 19 ms)
-constexpr int MHS_NFT_GRID = 4096, MHS_NFT_GRID_BIG = 16384;  // (from MHS_NFT_BIG_M rows)
 constexpr int MHS_TINY_PF = 1;  // tiny teams load their next row a round ahead (GAP-road-like -3 %, mac_econ-, scircuit-like -1 %)
-constexpr int MHS_SYM_WAVE_GRID = 2048;  // block cap of k_sym_common's wave rows (65536: cage15-like -3 %, cop20k-, webbase-, mac_econ-like +5 %)
-constexpr int MHS_SYM_WAVE_GRID_BIG = 65536;  // ... when the probe counted >= 2^21 table rows (Work::sym_big)
 constexpr int MHS_VAL_GMIN = 4;  // narrowest lane group of a value walk
 constexpr int MHS_TILE_GMIN = 4;  // narrowest lane group of a tile walk
 constexpr int MHS_RUN_GMIN = 8;  // narrowest lane group of a chunk with merged runs (32 before: see DESIGN §8)
-constexpr int MHS_MASK_GMAX = 64;
-constexpr int MHS_AN_GMAX = 8;  // k_analyze: 8 lanes per row (several rows per wave overlap their load chains)
 constexpr int MHS_GRP_UNROLL = 3;  // entries per lane issued together in a row-group walk
 // Occupancy targets (waves per SIMD; 0 = the compiler's choice).  The wave kernels are
 // bound by per-row latency chains, so waves in flight matter more than a few spills.
 constexpr int MHS_WPE_HASH = 8;  // measured: cop20k-like numeric -18%, cage15-like -16% (vs the compiler's 6)
-constexpr int MHS_SYM_B256_GRID = 1024;  // block cap of the persistent 256-thread symbolic bin launch
 constexpr int MHS_WPE_HASH16 = 4;  // the 10 KiB hash bin: LDS allows 4 waves per SIMD (an 8-wave register target spilled 34 VGPRs for nothing)
 // (the generic / grouped wave numeric kernel: no occupancy floor -- the compiler's choice; a
 // 5-wave floor at 96 VGPRs measured slower)
@@ -201,7 +193,6 @@ namespace mhs {
 
 constexpr int MHS_TINY_DUP = 2;  // ... and at most this many products a C column
 constexpr int MHS_TINY_SPARSE_PCT = 50;  // class-4 rows with tiles >= this % of their C columns go to the sort class (0: off)
-constexpr int MHS_LANE_AVG = 9;  // k_mask_b / k_analyze: a lane per row below this many entries a row on average (0: off)
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
 
 // Ordering point for LDS traffic between lanes of ONE wave: a wave's LDS
@@ -2597,7 +2588,6 @@ struct NearArgs {
     long long vcheck_n;
     int* nonfinite;  // Stats::nonfinite
 };
-constexpr int MHS_NEAR_GRID = 2048;  // k_near's block cap
 constexpr int NEAR_PER = 4;  // A entries a lane holds: a group's R rows of at most 256 entries
 constexpr int NEAR_LDS = NEAR_WORDS * 12 + RG_MAX * NEAR_UMAX * 8;  // a wave's bitmap, word prefixes, values
 static_assert(16 * NEAR_LDS <= LDS_MAX_C - 1024, "k_sym_rare's 16 waves hold their near-group regions");
@@ -4300,7 +4290,6 @@ __global__ __launch_bounds__(256) MHS_WPE_ATTR(8) void k_tiny_num_small(TinyArgs
 
 // Every symbolic tiny class in one launch (the bins' sizes are on the device): blocks
 // [TINY_SYM_GRID*c, TINY_SYM_GRID*(c+1)) walk class c's list.
-constexpr int TINY_SYM_GRID = 1024;
 __device__ __forceinline__ void tiny_sym_rows(TinyArgs a, int blk) {
     int c = blk / TINY_SYM_GRID, bid = blk % TINY_SYM_GRID, nb = TINY_SYM_GRID;
     if (a.nft) {  // numeric-first slots: the grid follows the bins' sizes, as numeric's does
@@ -4414,128 +4403,6 @@ __global__ __launch_bounds__(256) MHS_WPE_ATTR(MHS_WPE_SYM) void k_sym_common(Sy
 
 // -------------------------------------------------------------- launchers ---
 
-// Rows per block of the row_ptr scan and the bin lists: 4096 (four per thread) for big
-// matrices -- a quarter of the blocks, so a quarter of the per-(block, bin) cursor atomics
-// (tiny-row matrices of millions of rows were bound by them) -- 1024 below, where fewer
-// blocks would leave the chip idle (measured: cant-like -6% at 4096).
-constexpr int MHS_SCAN_BIG_M = (1 << 19);
-static int scan_per(int M) { return M >= MHS_SCAN_BIG_M ? 4 : 1; }
-
-constexpr int MHS_ROW_GMIN = 4;  // narrowest lane group per row in k_mask_b / k_analyze (tiny rows: 16 per wave)
-static int pick_group(long long nnz, int rows, int gmax = 64) {
-    const long long avg = rows > 0 ? (nnz + rows - 1) / rows : 1;
-    int g = MHS_ROW_GMIN;
-    while (g < avg && g < gmax) g <<= 1;
-    return g;
-}
-
-// Must run on every call, even when B is unchanged: it rewrites all of bmeta, and k_scan
-// marks near heads in bmeta.w (over the lo tile) for the numeric pass -- a skipped mask pass
-// would let stale NEAR_HEAD bits reach k_analyze.
-void launch_mask_b(const Csr& B, const Work& w, hipStream_t s) {
-    if (B.M <= 0) return;
-    // about four chunk iterations per row: a wave then holds several rows, whose
-    // dependent load chains overlap (measured on gfx950: 64-lane rows were latency-bound)
-    const long long avg = B.M > 0 ? B.nnz / B.M : 0;
-    if (avg < MHS_LANE_AVG) {  // short rows: a lane per row
-        const dim3 grid((B.M + 255) / 256), blk(256);
-        if (avg < 4)
-            hipLaunchKernelGGL(k_mask_lane<4>, grid, blk, 0, s, B.M, B.N, B.ptr, B.col, w.btcol, w.btmask, w.bmeta, w.bhi, w.stats);
-        else
-            hipLaunchKernelGGL(k_mask_lane<8>, grid, blk, 0, s, B.M, B.N, B.ptr, B.col, w.btcol, w.btmask, w.bmeta, w.bhi, w.stats);
-        return;
-    }
-    // rows of < 3 entries (road networks): 2-lane groups, 32 rows per wave (GAP-road-like -3.6 %)
-    // (round 6: groups widen from rows of 16 G entries on, not 8 G -- eight rows a wave for
-    // cant-like's 69-entry rows, three chunk rounds instead of two: the waves overlap their
-    // ptr -> col chains, cant-like pipelined steps -1.5 %, cant-perturbed-like -0.6 %)
-    int G = avg < 3 ? 2 : avg < 4 ? MHS_ROW_GMIN : 8;
-    while (2 * G <= avg / 8 && G < MHS_MASK_GMAX) G <<= 1;
-    const int rpb = 256 / G;
-    const dim3 grid((B.M + rpb - 1) / rpb), blk(256);
-#define MHS_MASK(GG, MM) hipLaunchKernelGGL((k_mask_b<GG, MM>), grid, blk, 0, s, B.M, B.N, B.ptr, B.col, w.btcol, w.btmask, w.bmeta, w.bhi, w.stats)
-    const bool multi = avg > G;  // rows of several chunks: four chunks a round trip
-    switch (G) {
-    case 2: MHS_MASK(2, 1); break;
-    case 4: MHS_MASK(4, 1); break;
-    case 8: if (multi) MHS_MASK(8, 4); else MHS_MASK(8, 1); break;
-    case 16: if (multi) MHS_MASK(16, 4); else MHS_MASK(16, 1); break;
-    case 32: if (multi) MHS_MASK(32, 4); else MHS_MASK(32, 1); break;
-    default: MHS_MASK(64, 4); break;
-#undef MHS_MASK
-    }
-}
-
-// k_analyze: G lanes per row, 256-thread blocks.
-// 2-lane groups for rows of < 3 entries on average (GAP-road-like 5.29 -> 4.97 ms)
-// G = 1: k_analyze_lane (rows averaging fewer than MHS_LANE_AVG entries; two per-block words)
-static void analyze_geometry(long long nnzA, int M, int* G, int* blocks) {
-    const long long avg = M > 0 ? nnzA / M : 0;
-    *G = avg < MHS_LANE_AVG ? 1 : avg < 3 ? 2 : pick_group(nnzA, M, MHS_AN_GMAX);
-    const int rpb = 256 / *G;
-    *blocks = (M + rpb - 1) / rpb;
-}
-
-int analyze_blocks(long long nnzA, int M) {  // k_analyze's per-block words
-    int G, blocks;
-    analyze_geometry(nnzA, M, &G, &blocks);
-    return G == 1 ? 2 * blocks : blocks;
-}
-
-void launch_analyze(const Csr& A, const Work& w, int MB, hipStream_t s, int* Cptr, Published* pub, int seq) {
-    if (A.M <= 0) return;
-    int G, blocks;
-    analyze_geometry(A.nnz, A.M, &G, &blocks);
-    const dim3 grid(blocks), blk(256);
-#define MHS_ANALYZE(GG, UU) hipLaunchKernelGGL((k_analyze<GG, UU>), grid, blk, 0, s, A.M, MB, A.ptr, A.col, w.bmeta, w.bhi, w.rflop, w.rtflop, w.rlo, w.rhi, w.ctiles, w.sym_bin, Cptr, w.blkflop, w.asame, w.stats, (unsigned long long*)w.scan_part, (A.M + 1 + SCAN_ITEMS - 1) / SCAN_ITEMS + 1 + ZERO_INTS / 2, w.nft_bin, (w.near_list && !w.nft_bin) ? w.nsig : nullptr, w.tiny_num && MHS_SYM_SORT64)
-#define MHS_ANALYZE_LANE(UU) hipLaunchKernelGGL((k_analyze_lane<UU>), grid, blk, 0, s, A.M, MB, A.ptr, A.col, w.bmeta, w.bhi, w.rflop, w.rtflop, w.rlo, w.rhi, w.ctiles, w.sym_bin, Cptr, w.blkflop, w.asame, w.stats, (unsigned long long*)w.scan_part, (A.M + 1 + SCAN_ITEMS - 1) / SCAN_ITEMS + 1 + ZERO_INTS / 2, w.nft_bin, (w.near_list && !w.nft_bin) ? w.nsig : nullptr, w.tiny_num && MHS_SYM_SORT64)
-    switch (G) {
-    case 1:
-        if (A.nnz < 4LL * A.M) MHS_ANALYZE_LANE(4);
-        else MHS_ANALYZE_LANE(8);
-        break;
-    case 2: MHS_ANALYZE(2, 1); break;
-    case 4: MHS_ANALYZE(4, 1); break;
-    case 8:
-        if (A.nnz > 8LL * A.M) MHS_ANALYZE(8, 4);  // rows of more than a group's 8 entries on average
-        else MHS_ANALYZE(8, 1);
-        break;
-    case 16: MHS_ANALYZE(16, 1); break;
-    case 32: MHS_ANALYZE(32, 1); break;
-    default: MHS_ANALYZE(64, 4); break;
-    }
-#undef MHS_ANALYZE
-#undef MHS_ANALYZE_LANE
-    if (w.nft_bin && pub) {  // numeric-first probe: the counts go to the host, which picks the bin lists
-        hipLaunchKernelGGL(k_probe_publish, dim3(64), dim3(1024), 0, s, (const unsigned long long*)w.blkflop,
-                           G == 1 ? 2 * blocks : blocks,
-                           w.stats, pub, seq);
-        return;
-    }
-    launch_bin_list(A, w, s);
-}
-
-void launch_bin_list(const Csr& A, const Work& w, hipStream_t s) {
-    const unsigned char* nb = w.nft ? w.nft_bin : nullptr;
-    const NearCand nc{w.nsig, (w.groups && !nb) ? w.near_list : nullptr};
-    if (scan_per(A.M) == 4)
-        hipLaunchKernelGGL(k_bin_list<4>, dim3((A.M + 4095) / 4096), dim3(1024), 0, s, A.M, w.sym_bin, w.asame, w.grp,
-                           w.groups, w.bin_list, nb, w.stats, nc, w.cursors + CURSOR_INTS);
-    else
-        hipLaunchKernelGGL(k_bin_list<1>, dim3((A.M + 1023) / 1024), dim3(1024), 0, s, A.M, w.sym_bin, w.asame, w.grp,
-                           w.groups, w.bin_list, nb, w.stats, nc, w.cursors + CURSOR_INTS);
-}
-
-static NearArgs near_args(const Csr& A, const Work& w, const int* Cptr);  // (with the symbolic launchers)
-
-void launch_near(const Csr& A, const Work& w, const int* Cptr, hipStream_t s) {
-    const NearArgs p = near_args(A, w, Cptr);
-    if (!p.list) return;
-    // a persistent grid over the device-side candidate count (none: the waves return at once)
-    const int cap = (A.M / 3 + WPB - 1) / WPB;
-    hipLaunchKernelGGL(k_near, dim3(round8(cap, MHS_NEAR_GRID)), dim3(256), 0, s, p);
-}
-
 hipError_t probe_counter(unsigned long long** dev) {
 #if MHS_PROBE_STATS
     return hipGetSymbolAddress((void**)dev, HIP_SYMBOL(g_probe_conflicts));
@@ -4610,69 +4477,7 @@ static SymArgs sym_args(const Csr& A, const Work& w, int M, int N, int* Cptr) {
     return a;
 }
 
-// The common symbolic bins, launched right after the row analysis with persistent
-// grids that read their bin's size on the device: the small-table wave bin and
-// every tiny class (one launch).
-void launch_symbolic_common(const Csr& A, const Csr& B, const Work& w, int M, int N, int* Cptr, hipStream_t s,
-                            const Stats* plan) {
-    if (M <= 0) return;
-    SymArgs a = sym_args(A, w, M, N, Cptr);
-    a.bin = SYM_WAVE;
-    // A speculated plan (SpecArgs) gives the bins' sizes ahead of the device: the roles are sized to
-    // them (an empty role launches no blocks; a bin of other counts changes the Stats, k_scan rejects
-    // the plan and the call reruns with the grids below).  Without a plan every role's grid is sized
-    // for M rows and its surplus blocks exit after one load.  (r06pg: mac_econ-like -2 %,
-    // scircuit-like -3 %, webbase-like -0.6 %: thousands of empty blocks no longer dispatched)
-    const int wave_rows = plan ? plan->sym_count[SYM_WAVE] : M;
-    // (the probe counted >= 2^21 rows past the tiny classes -- table rows, nearly all in this bin: the
-    // numeric hash bin's big-grid rule; r06i: cage15-like -3.2 %; wb-edu-like, 1.9 M such rows, keeps 2048)
-    const int wave_blocks =
-        wave_rows == 0 ? 0 : round8((wave_rows + WPB - 1) / WPB, w.sym_big ? MHS_SYM_WAVE_GRID_BIG : MHS_SYM_WAVE_GRID);
-    TinyArgs t{};
-    t.M = M;
-    t.Aptr = A.ptr;
-    t.Acol = A.col;
-    t.bmeta = w.bmeta;
-    t.Bcol = B.col;
-    t.stats = w.stats;
-    t.grp = w.grp;
-    t.Cptr = Cptr;
-    t.ctiles = w.ctiles;
-    t.list = w.bin_list + (long long)(SYM_TINY - 1) * M;
-    t.count = -1;
-    t.nft = w.nft;
-    if (w.nft) {
-        t.Aval = A.val;
-        t.Bval = B.val;
-        t.rlo = w.rlo;
-        t.sc_col = w.sc_col;
-        t.sc_val = w.sc_val;
-        t.tslot = w.tslot;
-    }
-    constexpr int NCL = MHS_SYM_SORT64 ? TINY_SYMX_NC : TINY_SYM_NC;
-    int tiny_blocks = TINY_SYM_GRID * NCL;
-    if (plan && !t.nft) {  // (class c's blocks are [1024 c, 1024 (c+1)): all of them, or none)
-        int rows = 0;
-        for (int c = 0; c < NCL; ++c) rows += plan->sym_count[SYM_TINY + c];
-        if (rows == 0) tiny_blocks = 0;
-    }
-    if (t.nft) {  // (the classes' sizes are on the device: grids for M rows each, as numeric's)
-        for (int c = 0; c < TINY_SYM_NC; ++c) {
-            const int per = 256 / tiny_w(c);
-            const int rows = plan ? plan->sym_count[SYM_TINY + c] : M;
-            t.blk0[c + 1] = t.blk0[c] + (rows == 0 ? 0 : round8((rows + per - 1) / per, M >= MHS_NFT_BIG_M ? MHS_NFT_GRID_BIG : MHS_NFT_GRID));
-        }
-        const bool c4 = MHS_SYM_SORT64 && (!plan || plan->sym_count[SYM_TINY + 4] > 0);
-        t.blk0[TINY_SYMX_NC] = t.blk0[TINY_SYM_NC] + (c4 ? TINY_SYM_GRID : 0);  // class 4: a walk
-        tiny_blocks = t.blk0[TINY_SYMX_NC];
-    }
-    if (wave_blocks + tiny_blocks > 0)
-        hipLaunchKernelGGL(k_sym_common<SYM_WAVE_BYTES>, dim3(wave_blocks + tiny_blocks), dim3(256),
-                           WPB * SYM_WAVE_BYTES, s, a, t, wave_blocks);
-}
-
-// The rare bins (10 KiB waves, 32 KiB and 157 KiB block tables, global memory): one
-// persistent launch that reads the bins' sizes on the device.
+// The near check's arguments (k_sym_rare's phase 0, or k_near)
 static NearArgs near_args(const Csr& A, const Work& w, const int* Cptr) {
     NearArgs p{};
     if (A.M <= 1 || !w.near_list || !w.groups || w.nft) return p;  // p.list == nullptr: none
@@ -4702,35 +4507,101 @@ static NearArgs near_args(const Csr& A, const Work& w, const int* Cptr) {
     return p;
 }
 
-void launch_symbolic_rare(const Csr& A, const Work& w, int M, int N, int* Cptr, hipStream_t s, bool with_near) {
-    if (M <= 0) return;
-    SymArgs a = sym_args(A, w, M, N, Cptr);
-    const NearArgs np = with_near ? near_args(A, w, Cptr) : NearArgs{};
-    hipLaunchKernelGGL(k_sym_rare, dim3(256), dim3(1024), LDS_MAX - 1024, s, a, np);
-}
-
-// The 32 KiB block bin (its own launch: at one block per CU in k_sym_rare it would hold a fifth
-// of the rows in flight).  With the rare bins on an aux stream it follows the common bins on the
-// call's stream, beside k_sym_rare (webbase-like: 60 us off the symbolic phase).
-void launch_symbolic_b256(const Csr& A, const Work& w, int M, int N, int* Cptr, hipStream_t s) {
-    if (M <= 0) return;
-    SymArgs a = sym_args(A, w, M, N, Cptr);
-    a.bin = SYM_B256;
-    hipLaunchKernelGGL((k_sym_block<256, false>), dim3(round8(M, MHS_SYM_B256_GRID)), dim3(256), SYM_B256_BYTES, s, a);
-}
-
-void launch_scan_classify(int M, const Work& w, int* Cptr, const int* Aptr, hipStream_t s, int dense_span_max,
-                          Published* pub, int seq, const SpecArgs& spec) {
-    // the state words were zeroed by k_analyze (SCAN_ITEMS-row blocks: enough for either width)
-    const int per = scan_per(M), nb = (M + 1 + 1024 * per - 1) / (1024 * per);
-#define MHS_SCAN(P)                                                                                                \
-    hipLaunchKernelGGL(k_scan<P>, dim3(nb), dim3(1024), 0, s, M, Cptr, (unsigned long long*)w.scan_part, w.rflop,  \
-                       w.rlo, w.rhi, w.ctiles, w.grp, Aptr, w.bin_list, w.stats, dense_span_max, pub, seq, w.tiny_num, \
-                       w.blkflop, w.nflop, w.sc_col != nullptr, w.tslot, w.gna, w.near_b ? w.bmeta : nullptr, w.sym_bin, spec, \
-                       w.cursors + CURSOR_INTS + NBINS * BINCNT_STRIDE)
-    if (per == 4) MHS_SCAN(4);
-    else MHS_SCAN(1);
-#undef MHS_SCAN
+// One pre-numeric launch (mhs_frontplan.hpp): the plan chose the kernel, its variant, grid, LDS and the
+// roles of k_sym_common's blocks; here they meet the call's arrays.  The variants are all the rules reach.
+void issue_front(const FrontLaunch& l, const FrontPointers& p, hipStream_t s, int seq, const SpecArgs* spec) {
+    const Csr &A = p.A, &B = p.B;
+    const Work& w = p.w;
+    const dim3 grid(l.grid), blk(l.block);
+    auto mask = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, blk, 0, s, B.M, B.N, B.ptr, B.col, w.btcol, w.btmask, w.bmeta, w.bhi, w.stats);
+    };
+    auto analyze = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, blk, 0, s, A.M, B.M, A.ptr, A.col, w.bmeta, w.bhi, w.rflop, w.rtflop, w.rlo,
+                           w.rhi, w.ctiles, w.sym_bin, p.Cptr, w.blkflop, w.asame, w.stats,
+                           (unsigned long long*)w.scan_part, (A.M + 1 + SCAN_ITEMS - 1) / SCAN_ITEMS + 1 + ZERO_INTS / 2,
+                           w.nft_bin, (w.near_list && !w.nft_bin) ? w.nsig : nullptr, w.tiny_num && MHS_SYM_SORT64);
+    };
+    auto bin_list = [&](auto kernel) {
+        const unsigned char* nb = w.nft ? w.nft_bin : nullptr;
+        const NearCand nc{w.nsig, (w.groups && !nb) ? w.near_list : nullptr};
+        hipLaunchKernelGGL(kernel, grid, blk, 0, s, A.M, w.sym_bin, w.asame, w.grp, w.groups, w.bin_list, nb, w.stats, nc,
+                           w.cursors + CURSOR_INTS);
+    };
+    auto scan = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, blk, 0, s, A.M, p.Cptr, (unsigned long long*)w.scan_part, w.rflop, w.rlo, w.rhi,
+                           w.ctiles, w.grp, A.ptr, w.bin_list, w.stats, p.dense_span_max, p.pub, seq, w.tiny_num,
+                           w.blkflop, w.nflop, w.sc_col != nullptr, w.tslot, w.gna, w.near_b ? w.bmeta : nullptr,
+                           w.sym_bin, spec ? *spec : SpecArgs{}, w.cursors + CURSOR_INTS + NBINS * BINCNT_STRIDE);
+    };
+    switch (l.kernel) {
+    case FK_MASK_LANE:
+        if (l.variant == 4) mask(k_mask_lane<4>);
+        else mask(k_mask_lane<8>);
+        break;
+    case FK_MASK:
+        if (l.variant == 8) mask(k_mask_b<8, 4>);
+        else if (l.variant == 16) mask(k_mask_b<16, 4>);
+        else if (l.variant == 32) mask(k_mask_b<32, 4>);
+        else mask(k_mask_b<64, 4>);
+        break;
+    case FK_ANALYZE_LANE:
+        if (l.variant == 4) analyze(k_analyze_lane<4>);
+        else analyze(k_analyze_lane<8>);
+        break;
+    case FK_ANALYZE: analyze(k_analyze<8, 4>); break;
+    case FK_PROBE_PUBLISH:
+        hipLaunchKernelGGL(k_probe_publish, grid, blk, 0, s, (const unsigned long long*)w.blkflop, l.words, w.stats, p.pub,
+                           seq);
+        break;
+    case FK_BIN_LIST:
+        if (l.variant == 4) bin_list(k_bin_list<4>);
+        else bin_list(k_bin_list<1>);
+        break;
+    case FK_SYM_COMMON: {
+        SymArgs a = sym_args(A, w, A.M, B.N, p.Cptr);
+        a.bin = SYM_WAVE;
+        TinyArgs t{};
+        t.M = A.M;
+        t.Aptr = A.ptr;
+        t.Acol = A.col;
+        t.bmeta = w.bmeta;
+        t.Bcol = B.col;
+        t.stats = w.stats;
+        t.grp = w.grp;
+        t.Cptr = p.Cptr;
+        t.ctiles = w.ctiles;
+        t.list = w.bin_list + (long long)(SYM_TINY - 1) * A.M;
+        t.count = -1;
+        t.nft = w.nft;
+        if (w.nft) {
+            t.Aval = A.val;
+            t.Bval = B.val;
+            t.rlo = w.rlo;
+            t.sc_col = w.sc_col;
+            t.sc_val = w.sc_val;
+            t.tslot = w.tslot;
+        }
+        for (int c = 0; c <= TINY_SYMX_NC; ++c) t.blk0[c] = l.blk0[c];
+        hipLaunchKernelGGL(k_sym_common<SYM_WAVE_BYTES>, grid, blk, l.lds, s, a, t, l.wave_blocks);
+        break;
+    }
+    case FK_SYM_RARE:
+        hipLaunchKernelGGL(k_sym_rare, grid, blk, l.lds, s, sym_args(A, w, A.M, B.N, p.Cptr),
+                           l.with_near ? near_args(A, w, p.Cptr) : NearArgs{});
+        break;
+    case FK_SYM_B256: {
+        SymArgs a = sym_args(A, w, A.M, B.N, p.Cptr);
+        a.bin = SYM_B256;
+        hipLaunchKernelGGL((k_sym_block<256, false>), grid, blk, l.lds, s, a);
+        break;
+    }
+    case FK_NEAR: hipLaunchKernelGGL(k_near, grid, blk, 0, s, near_args(A, w, p.Cptr)); break;
+    case FK_SCAN:
+        if (l.variant == 4) scan(k_scan<4>);
+        else scan(k_scan<1>);
+        break;
+    }
 }
 
 // Partition of the split block bins' lists (one 1024-thread block per bin): rows at or below

@@ -17,18 +17,12 @@ constexpr int MHS_NUM_WS_GRID = 4096;  // block cap of the small-row grouped num
 constexpr int MHS_TINY64_GRID = 4096;  // block cap of the 64-lane tiny numeric launches (8192: wb-edu-like +6 %)
 constexpr int MHS_NUM_W16H_GRID = 2048;  // block cap of the 10 KiB hash launch (4096: neutral at 16 KiB, profiles/r02za2_grid)
 constexpr int MHS_COPY_CAP_BIG = 65536;  // the slot copy's block cap from 4 M rows (16384 below; delaunay-like -1 %, r05ab19)
-constexpr int MHS_NFT_BIG_M = 1 << 22;   // "4 M rows": the numeric-first grids' big-matrix threshold
 constexpr int MHS_NUM_WSH_BIG = (1 << 21);  // small hash bins of at least this many rows: block cap MHS_NUM_WSH_BIG_GRID
 constexpr int MHS_NUM_WSH_BIG_GRID = 65536;  // (cage15-like -2.5 % over 16384; 65536 for every bin: offshore-, webbase-like +1.5 %)
 constexpr int MHS_NUM_WSX_GRID = 16384;  // ... of the small-row hash / direct launches (8192: cage15-like numeric +4.5 %, 4096: +13 %,
                                          // cant-perturbed +5 %; the grouped launch: 8192 measured +1.4 % on cant-like)
 constexpr int MHS_DYN16_MAX = 32768;  // hash 10 KiB bins of at most this many rows: all rows from the cursor
 
-inline int round8(long long x, int cap) {
-    long long g = x < cap ? x : cap;
-    if (g < 8) g = 8;
-    return (int)((g + 7) / 8 * 8);
-}
 // Dynamic LDS of a block-kernel launch: the header plus its largest row's tables, in
 // 2 KiB steps, at most the bin's budget.
 inline int block_lds(int need, int budget, int T) {

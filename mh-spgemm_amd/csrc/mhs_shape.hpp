@@ -260,6 +260,13 @@ __host__ __device__ inline int hash_slots_pow2(int bound) {
     return h < 16 ? 16 : h;
 }
 __host__ __device__ inline long long align16(long long x) { return (x + 15) & ~15LL; }
+// a grid of x blocks at most `cap`, a multiple of 8 (both launch plans)
+inline int round8(long long x, int cap) {
+    long long g = x < cap ? x : cap;
+    if (g < 8) g = 8;
+    return (int)((g + 7) / 8 * 8);
+}
+constexpr int MHS_NFT_BIG_M = 1 << 22;   // "4 M rows": the numeric-first grids' big-matrix threshold
 
 // Symbolic tile table: direct-mapped over the row's tile span (no keys, no CAS) when
 // the span is not much wider than the table a hash would need and the direct table

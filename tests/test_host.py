@@ -56,6 +56,20 @@ def test_numeric_plan_under_sanitizers(tmp_path):
     assert run.returncode == 0 and run.stdout.strip() == "numplan ok", run.stdout + run.stderr
 
 
+def test_front_plan_under_sanitizers(tmp_path):
+    # the pre-numeric launch plans (csrc/mhs_frontplan.hpp) are HIP-free functions of the call's shape and a
+    # speculated call's Stats: tests/frontplan_check.cpp checks the mask / analyze / scan geometry on both
+    # sides of every edge, k_sym_common's roles, the skip rules, the forked order and the set of kernel
+    # variants the rules reach against hand-computed literals on the host
+    exe = tmp_path / "frontplan_check"
+    cc = subprocess.run(["c++", "-std=c++17", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                         "-fno-sanitize-recover=all", str(ROOT / "tests" / "frontplan_check.cpp"), "-o", str(exe)],
+                        capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout.strip() == "frontplan ok", run.stdout + run.stderr
+
+
 def test_vendor_library_exports_every_declared_symbol():
     # rocSPARSE comparison row (include/mhs_vendor.h): loads without a GPU, exports its two entries
     V = _lib.vendor_lib()
