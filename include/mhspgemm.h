@@ -25,6 +25,13 @@
  *     on every FP64 path (the full call, the values plans and their backward):
  *     an entry of m kept products is within m * 2^-53 * (the sum of the
  *     products' absolute values) of the exact sum, in any order.
+ *   - Inf, NaN and stored zeros propagate as IEEE arithmetic on the products does, whatever the order: every kept
+ *     product is formed and nothing else is.  With each product classified in double (FP32 plans: in float; 0 * Inf
+ *     and anything times NaN are NaN), an entry of C is NaN if one of its products is NaN or products of both
+ *     infinities occur, +Inf or -Inf if only that infinity occurs, and otherwise finite within the bound above.  A
+ *     stored zero in A or B is an ordinary entry: 0 * Inf is a NaN here as in the reference.  (Near row groups add
+ *     explicit 0 * b products, so a call whose B holds a non-finite value runs without them.)  The one exemption is
+ *     stated at mhs_spgemm_values_grad: a zero cotangent times a non-finite value.
  */
 #ifndef MHSPGEMM_H
 #define MHSPGEMM_H
@@ -206,7 +213,10 @@ int mhs_values_plan_create(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, con
  * synchronises and writes the hipEvent time of the call.
  * Hot calls do not re-validate: the pattern arrays must not have changed since plan creation.
  * A call with ms == NULL and MHS_OPT_SYNC 0 allocates nothing, reads nothing back and does not
- * synchronise; it only launches on the context stream (mhs_ctx_set_stream's, when set). */
+ * synchronise; it only launches on the context stream (mhs_ctx_set_stream's, when set).
+ * Non-finite values and stored zeros follow the data contract at the top of this header -- on every plan: plain or
+ * masked in any form (a product outside the mask reaches no entry, finite or not), either value type, any width
+ * and every set of a batched call (a set's Inf or NaN stays in that set), forward and backward. */
 int mhs_spgemm_values(mhs_ctx *ctx, mhs_values_plan *plan, const double *Aval, const double *Bval,
                       double *Cval, double *ms);
 typedef struct mhs_values_info {
@@ -259,7 +269,8 @@ int mhs_values_plan_kept(const mhs_values_plan *plan, int64_t *kept_products);
  * be NULL.  Outputs must not alias inputs.  Every entry of a requested output is written: an entry that
  * no kept product reaches (an empty B row, an empty C row, a B row no A column points at) gets exactly 0.0.
  * dAval is summed without atomics in a fixed order: two calls give the same bits.  dBval is summed by
- * FP64 atomics: its order is not fixed.  A zero cotangent times a non-finite value may give 0 or NaN.
+ * FP64 atomics: its order is not fixed.  Inf, NaN and stored zeros in Aval, Bval and dCval propagate as the data
+ * contract at the top says, with one exemption: a zero cotangent times a non-finite value may give 0 or NaN.
  * ms and MHS_OPT_SYNC as in mhs_spgemm_values: a call with ms == NULL and MHS_OPT_SYNC 0 allocates nothing,
  * reads nothing back and does not synchronise; it queues a zero fill of the outputs and the kernels on
  * the context stream.  Hot calls do not re-validate.  NULL ctx, plan or dCval, both outputs NULL, or a
@@ -318,7 +329,8 @@ int mhs_spgemm_values_grad_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float 
  * writes Cval + b * strideC.  Strides are in elements.  An input stride of 0 means one array shared by all
  * sets; otherwise it is >= that matrix's nnz.  strideC >= nnz(C) whenever nb > 1.  Outputs must not overlap
  * inputs or each other.  Every set has the contract of the unbatched call: every entry written, entries no
- * kept product reaches exactly 0, the any-order bound of the plan's type.  Nothing outside the nb segments of
+ * kept product reaches exactly 0, the any-order bound of the plan's type, the data contract's propagation of Inf,
+ * NaN and stored zeros within the set (a set's non-finite values reach no other set).  Nothing outside the nb segments of
  * nnz(C) values is written.  On the dot rows of a masked plan a set has the bits of the unbatched call on its
  * values.  Any nb >= 1 runs on any plan: ceil(nb / W) passes of the plan's launch list, the last with the
  * remaining sets (on a width-1 plan: nb runs of the unbatched kernels).  mhs_spgemm_values / _f32 on a plan of

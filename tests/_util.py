@@ -461,6 +461,116 @@ def wide_values(n, seed):
     return np.ldexp(rng.uniform(0.5, 1.0, n), rng.integers(-20, 21, n)) * rng.choice([-1.0, 1.0], n)
 
 
+# ------------------------------------------- IEEE propagation of Inf, NaN and stored zeros ---
+# The contract of every value path for non-finite inputs (include/mhspgemm.h), free of any summation order: an
+# output entry forms every kept product x * y and nothing else.  With each product classified in IEEE double
+# (0 * Inf and anything times NaN are NaN), the entry is NaN if a product is NaN or both +Inf and -Inf products
+# occur, +Inf or -Inf if only that sign of infinity occurs, and otherwise finite within the rounding bound of
+# its products, 1.01 m u S (exactly 0.0 where m = 0).  A stored zero is an ordinary entry.  Finite magnitudes
+# stay in the suite's ranges (wide_values; [0.1, 1) for FP32), so no finite partial sum overflows and the class
+# of an entry does not depend on the order.
+FINITE, POS_INF, NEG_INF, IS_NAN = 0, 1, 2, 3
+CLASS_NAMES = ("finite", "+Inf", "-Inf", "NaN")
+U32 = 2.0 ** -24
+
+
+def inject_nonfinite(v, seed, rate=0.004, least=6, zeros=True):
+    """A copy of v with k = max(least, int(rate * n)) entries, drawn without replacement, set to +Inf, -Inf, NaN
+    and 0.0 in turn (zeros=False: the first three)."""
+    out = np.array(v, copy=True)
+    n = len(out)
+    k = max(least, int(rate * n))
+    pos = np.random.default_rng(seed).choice(n, k, replace=False)
+    marks = np.array([np.inf, -np.inf, np.nan, 0.0] if zeros else [np.inf, -np.inf, np.nan], out.dtype)
+    out[pos] = marks[np.arange(k) % len(marks)]
+    return out
+
+
+def classes_of(v):
+    """The class of every value: FINITE, POS_INF, NEG_INF or IS_NAN."""
+    v = np.asarray(v, np.float64)
+    return np.where(np.isnan(v), IS_NAN, np.where(v == np.inf, POS_INF, np.where(v == -np.inf, NEG_INF, FINITE))).astype(np.int8)
+
+
+def product_classes(idx, x, y, n):
+    """The class of each slot k of [0, n) from the products x[i] * y[i] with idx[i] == k, formed in IEEE double."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = np.asarray(x, np.float64) * np.asarray(y, np.float64)
+    idx = np.asarray(idx, np.int64)
+    nan = np.bincount(idx[np.isnan(w)], minlength=n) > 0
+    pos = np.bincount(idx[w == np.inf], minlength=n) > 0
+    neg = np.bincount(idx[w == -np.inf], minlength=n) > 0
+    return np.where(nan | (pos & neg), IS_NAN, np.where(pos, POS_INF, np.where(neg, NEG_INF, FINITE))).astype(np.int8)
+
+
+def class_counts(cls):
+    return {CLASS_NAMES[c]: int(np.count_nonzero(cls == c)) for c in range(4)}
+
+
+def nonfinite_reference(idx, x, y, n, u):
+    """What the contract above asks of an output of n entries for the kept products x[i] * y[i] of slot idx[i]:
+    (classes, ref, m, S, u) -- the class per entry, and for the finite entries, in their order, the sum of their
+    products (all of them finite), their count and their absolute sum.  u = 2^-53: long-double sums; u = 2^-24:
+    double sums on the inputs as given, which the caller has rounded to float32.  Computed once and read only."""
+    assert u in (U64, U32), u
+    idx = np.asarray(idx, np.int64)
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    want = product_classes(idx, x, y, n)
+    fin = want == FINITE
+    keep = fin[idx]  # the products of the finite entries: every one of them finite
+    slot = (np.cumsum(fin) - 1)[idx[keep]]
+    nf = int(fin.sum())
+    m = np.bincount(slot, minlength=nf).astype(np.int64)
+    assert m.max(initial=0) < (2 ** 20 if u == U64 else 2 ** 16)
+    if u == U64:
+        ref, _, S = _exact_sums(slot, x[keep], y[keep], nf)
+    else:
+        w = x[keep] * y[keep]
+        ref, S = np.bincount(slot, w, nf), np.bincount(slot, np.abs(w), nf)
+    assert np.isfinite(S.astype(np.float64)).all()
+    return want, ref, m, S, u
+
+
+def assert_nonfinite_reference(got, reference, what, only=None):
+    """got against a nonfinite_reference: the classes equal entry for entry, the finite entries within 1.01 m u S of
+    their sums, and exactly 0.0 where m = 0.  only (a boolean mask): the entries judged.  Returns the classes."""
+    want, ref, m, S, u = reference
+    got = np.asarray(got).astype(np.float64)
+    n = len(want)
+    assert got.shape == (n,), f"{what}: shape"
+    only = np.ones(n, bool) if only is None else np.asarray(only, bool)
+    have = classes_of(got)
+    wrong = (want != have) & only
+    if wrong.any():
+        pairs = {f"{CLASS_NAMES[a]} -> {CLASS_NAMES[b]}": int(np.count_nonzero(wrong & (want == a) & (have == b)))
+                 for a in range(4) for b in range(4) if a != b}
+        pairs = {k: c for k, c in pairs.items() if c}
+        raise AssertionError(f"{what}: {wrong.sum()} of {only.sum()} entries in another class than their products' "
+                             f"(contract -> got: {pairs}; first at entry {int(np.nonzero(wrong)[0][0])})")
+    fin = want == FINITE
+    g, judged = got[fin], only[fin]
+    assert np.all(g[(m == 0) & judged] == 0.0), f"{what}: entries no kept product reaches are exactly 0.0"
+    if u == U64:
+        err = np.abs(g.astype(np.longdouble) - ref)
+        bound = np.longdouble(1.01 * U64) * m.astype(np.longdouble) * S
+    else:
+        err, bound = np.abs(g - ref), 1.01 * U32 * m * S
+    ratio = np.zeros(len(g), err.dtype)
+    np.divide(err, bound, out=ratio, where=(bound > 0) & judged)
+    worst = float(ratio.max(initial=0.0))
+    print(f"non-finite contract, {what}: {class_counts(want[only])}, worst err / bound {worst:.3f} on the finite "
+          f"entries, max m {m.max(initial=0)}")
+    bad = (err > bound) & judged
+    assert not bad.any(), (f"{what}: {bad.sum()} of {judged.sum()} finite entries outside 1.01 m u S, "
+                           f"u = 2^{int(np.log2(u))} (worst err / bound {worst:.3e})")
+    return want
+
+
+def assert_nonfinite_contract(got, idx, x, y, n, u, what):
+    """The whole check of an output against the contract above: nonfinite_reference, then assert_nonfinite_reference."""
+    return assert_nonfinite_reference(got, nonfinite_reference(idx, x, y, n, u), what)
+
+
 # ------------------------------------------------------------ the edge ladder ---
 # Rows that sit exactly on a bin or class edge of csrc/mhs_shape.hpp / mhs_valplan.hpp.  The edges themselves
 # come from tests/golden/shape_edges.json (printed by tests/shape_edges.cpp from the headers); the families

@@ -194,9 +194,10 @@ def test_near_union_runs_square(tool, drop):
 def test_near_groups_nonfinite_values(tool):
     """Near groups and union runs add explicit 0*b / a*0 products, which turn into NaN when
     b or a is Inf / NaN, where the reference (src/CSR.cu:48-96 compares every entry) never
-    forms the product.  k_mask_b checks B's values (A's, when B is A) and a non-finite
-    value turns near groups off for the call: Inf and NaN land exactly where the oracle has
-    them, A*A and A*B with B an unaliased copy."""
+    forms the product.  near_groups (mhs_kernels.hip) checks B's values (A's, when B is A) in
+    wave-strided slices and a non-finite value makes k_scan dissolve the near groups of the
+    call: Inf and NaN land exactly where the oracle has them, A*A and A*B with B an unaliased
+    copy.  (tests/test_gpu_nonfinite.py holds every value path to the whole contract.)"""
     A0 = _perturbed_fem(7, 6, 24, 0.03, seed=31)
     v = A0.val.copy()
     v[[5, 1000, 2500, 7001]] = np.inf
