@@ -158,11 +158,15 @@ long long mhs_ctx_chunked_calls(const mhs_ctx *ctx);
  *   MHS_STAT_MULTI_STREAM numeric launches dealt over several streams,
  *   MHS_STAT_SPEC         (ABI v10) the previous call's numeric plan launched ahead of the scan,
  *   MHS_STAT_SPEC_MISS    ... and rejected by the scan (the call reran without speculation),
- *   MHS_STAT_SPEC_SKIPPED symbolic launches left out by speculated calls (the plan's empty bins).
+ *   MHS_STAT_SPEC_SKIPPED symbolic launches left out by speculated calls (the plan's empty bins),
+ *   MHS_STAT_WIDE_OFFSETS (an addition to ABI v10) their numeric kernels with 64-bit byte offsets into
+ *                         B's arrays: nnz(B) + 3 nnz(A) >= 2^29, or every call of a context created
+ *                         with the environment variable MHS_NO_O32=1 (a test switch: small operands
+ *                         run the kernels of huge ones).  Once per call, also after a speculation miss.
  * Returns -1 for a null context or an unknown counter. */
 typedef enum mhs_stat { MHS_STAT_CHUNKED = 0, MHS_STAT_SPLIT = 1, MHS_STAT_SYM_FORK = 2, MHS_STAT_NFT = 3,
                         MHS_STAT_NEAR = 4, MHS_STAT_MULTI_STREAM = 5, MHS_STAT_SPEC = 6, MHS_STAT_SPEC_MISS = 7,
-                        MHS_STAT_SPEC_SKIPPED = 8 } mhs_stat;
+                        MHS_STAT_SPEC_SKIPPED = 8, MHS_STAT_WIDE_OFFSETS = 9 } mhs_stat;
 long long mhs_ctx_stat(const mhs_ctx *ctx, int which);
 /* Numeric-phase durations (ms) of the last min(n, recorded) calls, oldest
  * first; waits for them.  Returns the count written, or -status on error. */

@@ -342,7 +342,8 @@ int numeric_streams(const mhs_ctx* ctx, const Stats& h) {
 enum NumPhase { NUM_ALL = 0, NUM_SPEC_A = 1, NUM_SPEC_B = 2 };
 
 NumShape num_shape(const mhs_ctx* ctx, const Csr& a, const Csr& b, const Work& w, bool split) {
-    return NumShape{a.M, a.nnz, b.nnz, w.bx_on, w.sc_col != nullptr, split, NUM_GLOBAL_GRID, ctx->cus, ctx->group_cap};
+    return NumShape{a.M, a.nnz, b.nnz, w.bx_on, w.sc_col != nullptr, split, NUM_GLOBAL_GRID, ctx->cus, ctx->group_cap,
+                    ctx->no_o32};
 }
 
 // `plan`: built by the phase that runs first (ALL, SPEC_A) and kept by the caller for SPEC_B.
@@ -506,7 +507,7 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
         if (rc) return rc;
         tmp.give_back();  // (every pass has been waited for)
     }
-    if (total > INT_MAX) return fail(ctx, MHS_ERR_OVERFLOW, "nnz(C) exceeds INT32_MAX");
+    if (total > INT_MAX) return fail(ctx, MHS_ERR_OVERFLOW, "nnz(C) exceeds INT32_MAX (the total over the row chunks)");
     // C before the second pass's workspace: it does not depend on the chunking
     const int Mc1 = Mc;
     free_cached(ctx);
@@ -533,6 +534,7 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
     // pass 2: every chunk's rows at their offset
     long long off = 0;
     int sym[NBINS] = {}, num[NBINS] = {};
+    bool wide = false;  // a chunk's plan took the 64-bit offsets
     own.queued = true;
     for (int c = 0; c < nch; ++c) {
         const Csr a = view(c);
@@ -545,6 +547,7 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
             const NumPlan p = plan_numeric(h, num_shape(ctx, a, b, w, false));
             const NumPointers np{a, b, w, out.ptr + r0, out.col + off, out.val + off, ctx->dense_span_max};
             for (int i = 0; i < p.n; ++i) issue_numeric(p.launch[i], p.o32, np, s, nullptr, nullptr);
+            wide |= !p.o32;
         }
         launch_add_offset(out.ptr + r0, a.M + (c == nch - 1 ? 1 : 0), (int)off, s);
         MHS_HIP(hipGetLastError());
@@ -557,6 +560,7 @@ int spgemm_chunked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, mhs_csr* C,
     MHS_HIP(hipStreamSynchronize(s));
     own.commit(C);
     ++ctx->chunked_calls;
+    ctx->stat[MHS_STAT_WIDE_OFFSETS] += wide;
     if (t) {
         mhs_timing tm{};
         tm.total_e2e = tm.total_ref = ms_since(T0);
@@ -901,6 +905,7 @@ int Call::finish_speculated() {
     case SPEC_PROCEED:
         return MHS_OK;
     case SPEC_HIT:
+        ctx->stat[MHS_STAT_WIDE_OFFSETS] += ph.nnzC > 0 && !nplan.o32;  // (a miss: counted by the rerun)
         return ph.nnzC > 0 ? run_numeric(ctx, a, b, w, ph, own.out, nplan, nev0, nev1, NUM_SPEC_B) : MHS_OK;
     case SPEC_RERUN:
         break;
@@ -935,6 +940,7 @@ int Call::numeric_after_handoff() {
     w.go = nullptr;
     rc = run_or_stamp(h, NUM_ALL);
     if (rc) return rc;
+    ctx->stat[MHS_STAT_WIDE_OFFSETS] += h.nnzC > 0 && !nplan.o32;
     MHS_HIP(hipGetLastError());
     if (t) MHS_HIP(hipEventRecord(ctx->ev[6], s));
     return MHS_OK;
@@ -1056,6 +1062,7 @@ int mhs_ctx_create(mhs_ctx** out, int device) {
     if (const char* e = getenv("MHS_GROUP_GRID")) ctx->group_cap = std::max(0, atoi(e));  // (MHS_OPT_GROUP_GRID, A/B)
     if (const char* e = getenv("MHS_SPEC_NSS")) ctx->spec_nss = std::max(1, std::min(atoi(e), mhs_ctx::NAUX + 1));
     if (const char* e = getenv("MHS_SPEC_NO_ROOM")) ctx->spec_no_room = atoi(e) != 0;
+    if (const char* e = getenv("MHS_NO_O32")) ctx->no_o32 = atoi(e) != 0;  // tests: the 64-bit-offset numeric kernels
     *out = ctx;
     return MHS_OK;
 }
@@ -1225,7 +1232,7 @@ int mhs_ctx_set_option(mhs_ctx* ctx, int option, int value) {
 long long mhs_ctx_chunked_calls(const mhs_ctx* ctx) { return ctx ? ctx->chunked_calls : -1; }
 
 long long mhs_ctx_stat(const mhs_ctx* ctx, int which) {
-    if (!ctx || which < 0 || which > MHS_STAT_SPEC_SKIPPED) return -1;
+    if (!ctx || which < 0 || which > MHS_STAT_WIDE_OFFSETS) return -1;
     return which == MHS_STAT_CHUNKED ? ctx->chunked_calls : ctx->stat[which];
 }
 

@@ -54,7 +54,7 @@ struct mhs_ctx {
     size_t c_held = 0;       // C bytes a row-chunked call holds while it lays out its second pass
     long long front_passes = 0;  // front_pass calls (row-chunked passes; mhs_ctx_chunked_calls diagnostics)
     long long chunked_calls = 0;  // calls that ran row-chunked (mhs_ctx_chunked_calls)
-    long long stat[9] = {};       // path counters (mhs_ctx_stat; [0] unused: chunked_calls)
+    long long stat[10] = {};       // path counters (mhs_ctx_stat; [0] unused: chunked_calls)
     int dense_span_max = 0;  // NM_DENSE for rows spanning <= this many 64-column tiles (MHS_DENSE_SPAN; off: occupancy)
     // output pool (caching allocator for C arrays): (buffer, allocation size)
     std::vector<std::pair<void*, size_t>> pool;
@@ -88,6 +88,9 @@ struct mhs_ctx {
     // MHS_SPEC_NO_ROOM=1 (tests): a speculated call behaves as if the plan's C had not fitted -- its phase A
     // stays in (a budget cannot force that: the first call's C fitted under it); other calls are not touched
     bool spec_no_room = false;
+    // MHS_NO_O32=1 (tests): every numeric plan takes the 64-bit-offset kernels, which the size rule of
+    // plan_numeric selects only from 2^29 entries of B on (MHS_STAT_WIDE_OFFSETS counts the calls)
+    bool no_o32 = false;
     // the grouped numeric bin's cursor walk (plan_numeric): the device's compute units size its
     // resident set (MHS_GROUP_WALK=0: cus stays 0, the static walk); MHS_OPT_GROUP_GRID caps its blocks
     int cus = 0;

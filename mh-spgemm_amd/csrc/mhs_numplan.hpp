@@ -103,6 +103,7 @@ struct NumShape {
     int global_grid;  // block cap of the global bin
     int cus = 0;        // compute units (0: not known -- the grouped bins keep their static walk)
     int group_cap = 0;  // MHS_OPT_GROUP_GRID: block cap of the grouped cursor walk (0: the resident set)
+    int no_o32 = 0;     // MHS_NO_O32=1 (tests): 64-bit byte offsets whatever the sizes
 };
 
 // Numeric launches of the non-empty bins, largest rows first: dealt round-robin over the streams
@@ -118,7 +119,7 @@ inline NumPlan plan_numeric(const Stats& h, const NumShape& sh) {
     NumPlan p{};
     // 32-bit byte offsets for the B gathers when B's value array (extended by the union rows)
     // stays below 4 GiB: nnz(B) + 3 nnz(A) < 2^29 (the reference's int32 CSR allows up to 2^31)
-    p.o32 = (long long)sh.nnzB + (sh.bx_on ? 3LL * sh.nnzA : 0) < (1LL << 29);
+    p.o32 = !sh.no_o32 && (long long)sh.nnzB + (sh.bx_on ? 3LL * sh.nnzA : 0) < (1LL << 29);
     // a launch over `bin`'s list (cursor slot = bin) of `blocks` blocks at most `cap`
     auto add = [&](int kernel, int bin, int count, long long blocks, int cap, int threads, int lds) -> NumLaunch& {
         NumLaunch& l = p.launch[p.n < NUM_PLAN_MAX ? p.n++ : NUM_PLAN_MAX - 1];

@@ -29,6 +29,18 @@ MHS_OPT_TINY_FIRST_ROWS = 4
 MHS_OPT_SPECULATE = 5
 MHS_OPT_GROUP_GRID = 6
 
+# mhs_stat: the path counters of mhs_ctx_stat
+MHS_STAT_CHUNKED = 0
+MHS_STAT_SPLIT = 1
+MHS_STAT_SYM_FORK = 2
+MHS_STAT_NFT = 3
+MHS_STAT_NEAR = 4
+MHS_STAT_MULTI_STREAM = 5
+MHS_STAT_SPEC = 6
+MHS_STAT_SPEC_MISS = 7
+MHS_STAT_SPEC_SKIPPED = 8
+MHS_STAT_WIDE_OFFSETS = 9  # numeric kernels with 64-bit offsets (huge B, or MHS_NO_O32=1)
+
 MHS_MASK_AUTO = 0
 MHS_MASK_PRODUCT = 1
 MHS_MASK_DOT = 2

@@ -309,6 +309,16 @@ def with_hub_row(ptr, col, N, n_hub, feed=0):
     return p2.astype(np.int32), c2
 
 
+def compress_columns(col):
+    """B's columns mapped to their ranks among the distinct columns used: (ranks, true), ranks an int32 array of
+    col's shape, true the sorted distinct columns, true[ranks] == col.  The map is monotone, so sortedness,
+    duplicates and the product's structure are kept: the C of A * (B with the ranks, N = len(true)) is the C of
+    A * B with every column index c replaced by true[c].  For column spaces the oracle's dense per-thread arrays
+    of N entries cannot take (N up to INT32_MAX)."""
+    true, ranks = np.unique(np.asarray(col), return_inverse=True)
+    return ranks.reshape(np.shape(col)).astype(np.int32), true
+
+
 # ---------------------- helpers of the values-plan GPU tests (values, masked, backward) ---
 RTOL, ATOL = 1e-6, 1e-12  # the project's value tolerance (tests/test_gpu_parity.py)
 

@@ -288,7 +288,60 @@ static void test_dealing() {
     CHECK(a == 0x1111 && b == 0x2eee && (a & b) == 0 && (a | b) == 0x3fff);
 }
 
+// every field of a launch, one by one
+static bool same_launch(const NumLaunch& a, const NumLaunch& b) {
+    bool ok = a.kernel == b.kernel && a.variant == b.variant && a.grid == b.grid && a.block == b.block &&
+              a.lds == b.lds && a.list_bin == b.list_bin && a.list_off == b.list_off && a.count == b.count &&
+              a.slot == b.slot && a.wave_bytes == b.wave_bytes && a.gbytes == b.gbytes && a.qall == b.qall &&
+              a.hash_blocks == b.hash_blocks && a.after_split == b.after_split && a.cursor_walk == b.cursor_walk &&
+              a.fused.nclass == b.fused.nclass;
+    for (int k = 0; k < 4; ++k) ok = ok && a.fused.c[k] == b.fused.c[k] && a.fused.count[k] == b.fused.count[k];
+    for (int k = 0; k < 5; ++k) ok = ok && a.fused.blk0[k] == b.fused.blk0[k];
+    return ok;
+}
+
+// NumShape::no_o32 (MHS_NO_O32=1): o32 == 0 below the size rule, and nothing else of the plan moves.
+static void test_no_o32() {
+    static_assert(sizeof(NumLaunch) == (15 + 14) * sizeof(int), "same_launch names every field of NumLaunch");
+    struct Case {
+        Stats h;
+        NumShape sh;
+    };
+    Stats copy{};  // the fused copy (test_fused_copy)
+    copy.num_count[8] = 5000;
+    copy.num_count[9] = 3000;
+    copy.num_count[14] = 2000;
+    Stats cls3{};  // the plain copy, 16 lanes
+    cls3.num_count[8] = 1;
+    cls3.num_count[11] = 9;
+    NumShape walk = shape(100000, false, false);  // the grouped cursor walk
+    walk.cus = 256;
+    walk.group_cap = 8;
+    const Case cases[] = {{every_bin(), shape(100000, false, true)}, {every_bin(), shape(100000, false, false)},
+                          {every_bin(), walk}, {copy, shape(100000, true, false)}, {cls3, shape(100000, true, false)},
+                          {Stats{}, shape(0, false, false)}};
+    for (const Case& c : cases) {
+        NumShape on = c.sh;
+        CHECK(on.no_o32 == 0);  // (the default: the size rule)
+        const NumPlan p = plan_numeric(c.h, on);
+        on.no_o32 = 1;
+        const NumPlan q = plan_numeric(c.h, on);
+        CHECK(p.o32 == 1 && q.o32 == 0 && p.n == q.n);
+        for (int i = 0; i < NUM_PLAN_MAX; ++i) CHECK(same_launch(p.launch[i], q.launch[i]));
+        NumPlan r = q;  // ... and bytewise, o32 apart
+        r.o32 = 1;
+        CHECK(same(p, r));
+    }
+    // above the size rule the switch changes nothing: o32 is 0 either way
+    NumShape big = shape(100, false, false);
+    big.nnzB = 1 << 29;
+    const NumPlan p = plan_numeric(every_bin(), big);
+    big.no_o32 = 1;
+    CHECK(p.o32 == 0 && same(p, plan_numeric(every_bin(), big)));
+}
+
 int main() {
+    test_no_o32();
     test_every_bin();
     test_fused_copy();
     test_sparse_and_edges();
