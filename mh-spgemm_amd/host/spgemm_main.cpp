@@ -21,7 +21,8 @@
 //             calls on the same A and B (mhs_spgemm_values); their mean time on a line of its own, and
 //             with --check the recomputed values against the product's own by CSR::operator==
 //   --masked N after the product (and --reuse), a masked values plan (mhs_values_plan_create_masked, AUTO) of
-//             the same A and B on A's own pattern -- A*A kept where A has entries; needs rowA = colA -- and
+//             the same A and B on A's own pattern -- A*A kept where A has entries (an entry the file repeats is
+//             one mask entry: a mask's columns ascend strictly); needs rowA = colA -- and
 //             N calls; their mean time, the kept products and the dot rows on a line of its own, and with
 //             --check the values against the product's own C filtered to A's pattern (the 1e-9 rule)
 //   --grad N  after the product (and --reuse, --masked), a values plan on C's pattern and, with a seeded
@@ -95,15 +96,41 @@ static void recycle(Tool& tools, CSR& C) {
 
 // --masked N: A * B kept on A's pattern by a masked plan, N calls; with check against C (the full
 // product, on the device) filtered to A's pattern on the host.
+// A's pattern as a mask.  A mask's columns ascend strictly within a row (mhspgemm.h), and the reader keeps the
+// repeated entries of a file (sorted within the row): the mask holds such a column once.  Its pattern is on the
+// host (mask.ptr, mask.col); on the device it borrows A's arrays where A repeats nothing and has arrays of its
+// own otherwise.  Returns whether it owns them; unborrow_mask before the mask goes out of scope.
+static bool mask_of(const CSR& A, int N, CSR& mask) {
+    mask.alloc(A.M, N, A.nnz);
+    int n = 0;
+    for (int i = 0; i < A.M; ++i) {
+        mask.ptr[i] = n;
+        for (int k = A.ptr[i]; k < A.ptr[i + 1]; ++k)
+            if (k == A.ptr[i] || A.col[k] != A.col[k - 1]) mask.col[n++] = A.col[k];
+    }
+    mask.ptr[A.M] = n;
+    mask.nnz = n;
+    if (n == A.nnz) {
+        mask.d_ptr = A.d_ptr;
+        mask.d_col = A.d_col;
+        return false;
+    }
+    mhs_shim::hip_check(hipMalloc((void**)&mask.d_ptr, sizeof(int) * (size_t)(A.M + 1)), "hipMalloc mask ptr");
+    mhs_shim::hip_check(hipMalloc((void**)&mask.d_col, sizeof(int) * (size_t)(n > 0 ? n : 1)), "hipMalloc mask col");
+    mhs_shim::hip_check(hipMemcpy(mask.d_ptr, mask.ptr, sizeof(int) * (size_t)(A.M + 1), hipMemcpyHostToDevice), "H2D mask ptr");
+    mhs_shim::hip_check(hipMemcpy(mask.d_col, mask.col, sizeof(int) * (size_t)n, hipMemcpyHostToDevice), "H2D mask col");
+    return true;
+}
+static void unborrow_mask(CSR& mask, bool owns) {
+    if (!owns) mask.d_ptr = mask.d_col = nullptr;  // A's
+}
+
 static void run_masked(Tool& tools, const CSR& A, const CSR& B, CSR& C, int calls, bool check) {
-    CSR mask;  // A's pattern (borrowed device arrays) with values of its own
-    mask.M = A.M;
-    mask.N = B.N;
-    mask.nnz = A.nnz;
-    mhs_shim::hip_check(hipMalloc((void**)&mask.d_val, sizeof(double) * (size_t)(A.nnz > 0 ? A.nnz : 1)), "hipMalloc mask");
-    mask.d_ptr = A.d_ptr;
-    mask.d_col = A.d_col;
+    CSR mask;  // A's pattern with values of its own
+    bool owns = false;
     try {
+        owns = mask_of(A, B.N, mask);
+        mhs_shim::hip_check(hipMalloc((void**)&mask.d_val, sizeof(double) * (size_t)(mask.nnz > 0 ? mask.nnz : 1)), "hipMalloc mask");
         mhs_shim::ValuesPlan plan(tools, A, B, mask, true, MHS_MASK_AUTO);
         double sum = 0;
         for (int i = 0; i < calls; ++i) {
@@ -115,14 +142,14 @@ static void run_masked(Tool& tools, const CSR& A, const CSR& B, CSR& C, int call
                     sum / calls, plan.kept(), (long long)info.products, (int)info.rows[7]);
         if (check) {
             C.D2H();
-            std::vector<double> got((size_t)(A.nnz > 0 ? A.nnz : 1));
-            mhs_shim::hip_check(hipMemcpy(got.data(), mask.d_val, sizeof(double) * (size_t)A.nnz, hipMemcpyDeviceToHost), "D2H mask");
+            std::vector<double> got((size_t)(mask.nnz > 0 ? mask.nnz : 1));
+            mhs_shim::hip_check(hipMemcpy(got.data(), mask.d_val, sizeof(double) * (size_t)mask.nnz, hipMemcpyDeviceToHost), "D2H mask");
             int err = 0;
-            for (int i = 0; i < A.M; ++i)
-                for (int k = A.ptr[i]; k < A.ptr[i + 1]; ++k) {
+            for (int i = 0; i < mask.M; ++i)
+                for (int k = mask.ptr[i]; k < mask.ptr[i + 1]; ++k) {
                     const int *row = C.col + C.ptr[i], *end = C.col + C.ptr[i + 1];
-                    const int* hit = std::lower_bound(row, end, A.col[k]);
-                    const double want = hit != end && *hit == A.col[k] ? C.val[hit - C.col] : 0.0;
+                    const int* hit = std::lower_bound(row, end, mask.col[k]);
+                    const double want = hit != end && *hit == mask.col[k] ? C.val[hit - C.col] : 0.0;
                     const double d = std::fabs(want - got[(size_t)k]);
                     if (!(d < 1e-9 || d < 1e-9 * std::fabs(want))) ++err;
                 }
@@ -131,9 +158,7 @@ static void run_masked(Tool& tools, const CSR& A, const CSR& B, CSR& C, int call
     } catch (const std::exception&) {
         std::puts("masked fail");
     }
-    (void)hipFree(mask.d_val);
-    mask.d_ptr = mask.d_col = nullptr;  // A's
-    mask.d_val = nullptr;
+    unborrow_mask(mask, owns);  // (the mask's own arrays go with it)
 }
 
 static double median(std::vector<double> v) {
@@ -562,11 +587,10 @@ int main(int argc, char** argv) {
         if (f32) {
             if (reuse > 0) run_f32(tools, A, B, C, false, false, reuse, check, "values-only (pattern reused)", "values");
             if (masked > 0 && A.M == A.N) {
-                CSR mask;  // A's pattern, borrowed (a plan reads no values)
-                mask.M = A.M, mask.N = B.N, mask.nnz = A.nnz;
-                mask.d_ptr = A.d_ptr, mask.d_col = A.d_col;
+                CSR mask;  // A's pattern (a plan reads no values)
+                const bool owns = mask_of(A, B.N, mask);
                 run_f32(tools, A, B, mask, true, false, masked, check, "masked (A's pattern)", "masked");
-                mask.d_ptr = mask.d_col = nullptr;  // A's
+                unborrow_mask(mask, owns);
             }
             if (grad > 0) run_f32(tools, A, B, C, false, true, grad, check, "values backward (both gradients)", "grad");
         }
