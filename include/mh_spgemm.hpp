@@ -268,12 +268,19 @@ public:
     }
     // The batched constructor (mhs_values_plan_create_batched): a plan of `width` (1, 2 or 4) value sets per walk,
     // for MH_spgemm_values_batched.  Width 1 is the typed constructor's plan.
-    ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C, bool masked, int form, mhs_dtype dtype, int width)
+    // semiring: an mhs_semiring (mhs_values_plan_create_semiring).  A plan of another one than MHS_SR_PLUS_TIMES has
+    // width 1; MH_spgemm_values and MH_spgemm_values_batched run it, the backward calls throw the library's refusal.
+    ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C, bool masked, int form, mhs_dtype dtype, int width,
+               int semiring = MHS_SR_PLUS_TIMES)
         : ctx(tools.ctx) {
         mhs_csr a{A.M, A.N, A.nnz, A.d_ptr, A.d_col, A.d_val};
         mhs_csr b{B.M, B.N, B.nnz, B.d_ptr, B.d_col, B.d_val};
         mhs_csr c{C.M, C.N, C.nnz, C.d_ptr, C.d_col, C.d_val};
-        if (mhs_values_plan_create_batched(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, width, &plan) != MHS_OK) {
+        if (semiring != MHS_SR_PLUS_TIMES && width != 1) throw std::runtime_error("ValuesPlan: a semiring plan has width 1");
+        const int rc = semiring != MHS_SR_PLUS_TIMES
+                           ? mhs_values_plan_create_semiring(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, semiring, &plan)
+                           : mhs_values_plan_create_batched(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, width, &plan);
+        if (rc != MHS_OK) {
             std::printf("%s\n", mhs_last_error(ctx));
             throw std::runtime_error(mhs_last_error(ctx));
         }

@@ -399,6 +399,46 @@ int mhs_spgemm_values_grad_batched_f32(mhs_ctx *ctx, mhs_values_plan *plan, int 
                                        const float *dCval, int64_t strideG,
                                        float *dAval, int64_t strideDA, float *dBval, int64_t strideDB, double *ms);
 
+/* ---- semiring values plans: min-plus, max-plus and max-min on a kept pattern ------------------
+ * For graph callers: one relaxation step of shortest paths (min-plus: A (x) A on a kept pattern, or masked on A's
+ * own pattern to tighten existing edges only), longest or critical paths and Viterbi-style scoring (max-plus),
+ * widest (bottleneck) paths (max-min; on {0, 1} values the boolean or-and product, i.e. reachability).  A plan has a
+ * fourth fixed property beside its value type, its width and its mask form: its semiring (add, mul, the identity
+ * of add):
+ *   MHS_SR_PLUS_TIMES   +    x    0       every plan of the creation calls above
+ *   MHS_SR_MIN_PLUS     min  +    +Inf
+ *   MHS_SR_MAX_PLUS     max  +    -Inf
+ *   MHS_SR_MAX_MIN      max  min  -Inf
+ * mhs_values_plan_create_semiring with MHS_SR_PLUS_TIMES is exactly mhs_values_plan_create_typed; any other semiring
+ * value returns MHS_ERR_INVALID before any HIP call.  Semiring plans have width 1.  Validation, borrowing, plan
+ * memory, mhs_values_plan_info and mhs_values_plan_kept are those of any plan; a row's class is LDS arithmetic on
+ * the value's size and does not depend on the semiring, nor do the masked forms and AUTO's rule.
+ * Hot calls are the entry points above -- mhs_spgemm_values, _f32, mhs_spgemm_values_batched, _batched_f32 (nb runs
+ * of the kernels, as on any width-1 plan) -- with their stream, ms, MHS_OPT_SYNC and no-allocation contract; the plan
+ * knows its semiring.  On a plan of one of the three new semirings:
+ *   Cval(i,j) = add over the kept products of mul(A(i,k), B(k,j)).
+ *   Every duplicate entry of A or B is a product of its own: duplicates are reduced by add, not summed.
+ *   On a masked plan a product outside the mask reaches nothing.
+ *   Every entry of the C segment is written; an entry that no kept product reaches gets the identity of add:
+ *   +Inf, -Inf or -Inf.
+ *   Results are bit-identical to any sequential evaluation in the plan's value type, in any order, on every class
+ *   (min and max are exact and the one rounding of a + b does not depend on order), and so from call to call; the one
+ *   exemption is that the sign of a zero result is unspecified.
+ *   +-Inf values are ordinary: +Inf is "no edge" under min-plus.
+ *   A product that is NaN leaves that entry unspecified: either NaN or the add of its other products (the hardware
+ *   min and max are minNum and maxNum).  A NaN product comes from a NaN operand, or from +Inf + -Inf under the two
+ *   _PLUS semirings.  No other entry is affected.
+ *   FP32: a subnormal product or result may be flushed to zero, as on FP32 plus-times plans.
+ * The four backward entry points (mhs_spgemm_values_grad, _f32, _grad_batched, _grad_batched_f32) on a plan whose
+ * semiring is not MHS_SR_PLUS_TIMES return MHS_ERR_INVALID before any HIP call, with a message naming the semiring,
+ * and write nothing: min and max have subgradients only, which are not built.
+ * Cost on MI355X: DESIGN section 16.  Additions to ABI version 10, like the entries above. */
+typedef enum mhs_semiring { MHS_SR_PLUS_TIMES = 0, MHS_SR_MIN_PLUS = 1, MHS_SR_MAX_PLUS = 2, MHS_SR_MAX_MIN = 3 } mhs_semiring;
+int mhs_values_plan_create_semiring(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
+                                    int masked, int form, int dtype, int semiring, mhs_values_plan **plan);
+/* The plan's semiring (mhs_semiring). */
+int mhs_values_plan_semiring(const mhs_values_plan *plan, int *semiring);
+
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).
  * At->M = A->N, At->N = A->M; rows of At list their columns ascending; arrays are

@@ -12,6 +12,12 @@
 // Masked plans (mhs_values_plan_create_masked: C's pattern is a mask, products outside it are dropped)
 // classify by val_class_masked, count the kept products in place of the verify walk, and may send rows
 // to the dot class: k_val_dot, the inner-product form over B^T's pattern (no sums shared, no atomics).
+// The algebra is a policy S (SrPolicy of mhs_valwalk.hpp over mhs_semiring.hpp), the last template parameter of the
+// walks and the value kernels: S::identity() in the fills, S::mul for a product, S::lds / S::glob for the reduce of a
+// product into an LDS or a Cval sum, S::reg for the dot class's register.  The default, PlusTimes, is the code that
+// was there (V(0), av * bv, atomicAdd, unsafeAtomicAdd, +=); plans of mhs_values_plan_create_semiring run the min-plus,
+// max-plus and max-min instantiations, at width 1: ds_min_* / ds_max_* in LDS, global_atomic_min_f64 / _max_f64 in
+// the global class (FP32 there: a compare-and-swap loop).
 #include "mhs_valwalk.hpp"
 
 #include <climits>
@@ -28,7 +34,7 @@ template <int W, class V>
 __device__ __forceinline__ int val_nw(const ValArgs<V>& a) {
     return W == 1 ? 1 : a.nw;
 }
-template <int G, int W, class V, class F>
+template <int G, int W, class S = PlusTimes, class V, class F>
 __device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int g, int ng, int t, F add) {
     const int nw = val_nw<W>(a);
     const int ae = a.A.ptr[row + 1];
@@ -44,7 +50,7 @@ __device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int 
             ValSums<V, W> p;
 #pragma unroll
             for (int w = 0; w < W; ++w)
-                if (w < nw) p.x[w] = av[w] * a.B.val[(long long)w * a.sB + j];
+                if (w < nw) p.x[w] = S::mul(av[w], a.B.val[(long long)w * a.sB + j]);
             add(c, p);
         }
     }
@@ -57,7 +63,7 @@ __device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int 
 // sync that publishes them (the row's zero fill rides on that sync).
 // W > 1: the stage holds no A value (ValStage); a group reads each set's at the entry's A position, and
 // val_pieces(W) pieces of W values each are in flight.
-template <int G, int W, int CH, class V, class Sync, class Pre, class F>
+template <int G, int W, class S = PlusTimes, int CH, class V, class Sync, class Pre, class F>
 __device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t, int lanes, ValStage<CH, V, W>& d, Sync sync,
                                             Pre pre, F add) {
     constexpr int P = val_pieces(W);
@@ -108,7 +114,7 @@ __device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t,
                         ValSums<V, W> p;
 #pragma unroll
                         for (int w = 0; w < W; ++w)
-                            if (w < nw) p.x[w] = av[w] * v[u][w];
+                            if (w < nw) p.x[w] = S::mul(av[w], v[u][w]);
                         add(c[u], p);
                     }
             }
@@ -256,7 +262,7 @@ __global__ __launch_bounds__(256) void k_val_count_kept(ValPattern p, unsigned l
 // Searched sums of one row by `lanes` lanes (lane t): cols / acc are the row's LDS slice, set w's sums the
 // plane acc + w * pitch.  walk(pre, add) runs pre() and a sync, then add(column, sums) per product; sync orders
 // the steps (a wave's or a block's).  Every set's ds_add has the one slot, so the bank pattern of one set's.
-template <int W, class V, class Sync, class Walk>
+template <int W, class S = PlusTimes, class V, class Sync, class Walk>
 __device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V* acc, int* cols, int pitch, int t, int lanes,
                                            Sync sync, Walk walk) {
     const int nw = val_nw<W>(a);
@@ -266,7 +272,7 @@ __device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V*
                 cols[p] = a.C.col[s + p];
 #pragma unroll
                 for (int w = 0; w < W; ++w)
-                    if (w < nw) acc[(size_t)w * pitch + p] = V(0);
+                    if (w < nw) acc[(size_t)w * pitch + p] = S::template identity<V>();
             }
         },
         [&](int c, const ValSums<V, W>& v) {
@@ -274,7 +280,7 @@ __device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V*
             if (slot >= 0) {
 #pragma unroll
                 for (int w = 0; w < W; ++w)
-                    if (w < nw) atomicAdd(&acc[(size_t)w * pitch + slot], v.x[w]);  // ds_add_f64 / ds_add_f32
+                    if (w < nw) S::lds(&acc[(size_t)w * pitch + slot], v.x[w]);  // ds_add_f64 / ds_add_f32, ds_min_* / ds_max_*
             }
         });
     sync();
@@ -285,7 +291,7 @@ __device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V*
     sync();
 }
 // Span-indexed sums of one row: acc[w * span + col - first], gathered through C.col afterwards.
-template <int W, class V, class Sync, class Walk>
+template <int W, class S = PlusTimes, class V, class Sync, class Walk>
 __device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, int first, int span, V* acc, int t, int lanes,
                                            Sync sync, Walk walk) {
     const int nw = val_nw<W>(a);
@@ -294,14 +300,14 @@ __device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, in
 #pragma unroll
             for (int w = 0; w < W; ++w)
                 if (w < nw)
-                    for (int p = t; p < span; p += lanes) acc[(size_t)w * span + p] = V(0);
+                    for (int p = t; p < span; p += lanes) acc[(size_t)w * span + p] = S::template identity<V>();
         },
         [&](int c, const ValSums<V, W>& v) {
             const unsigned slot = (unsigned)(c - first);
             if (slot < (unsigned)span) {
 #pragma unroll
                 for (int w = 0; w < W; ++w)
-                    if (w < nw) atomicAdd(&acc[(size_t)w * span + slot], v.x[w]);  // ds_add_f64 / ds_add_f32
+                    if (w < nw) S::lds(&acc[(size_t)w * span + slot], v.x[w]);  // ds_add_f64 / ds_add_f32, ds_min_* / ds_max_*
             }
         });
     sync();
@@ -315,19 +321,19 @@ __device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, in
 }
 
 // One row of a wave or block class in the row frame: direct or searched sums over the staged walk.
-template <bool DIRECT, int W, int CH, class V, class Sync>
+template <bool DIRECT, int W, class S, int CH, class V, class Sync>
 __device__ __forceinline__ void row_sums(const ValArgs<V>& a, int row, char* base, int region, int t, int lanes,
                                          ValStage<CH, V, W>& d, Sync sync) {
     val_row<DIRECT, W>(a, row, base, region, [&](int s, int n, int first, int span, V* acc, int* cols) {
         const int pitch = val_slice_entries(region, W * (int)sizeof(V));  // (search: the slice's entries, as search_slice)
-        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP, W>(a, row, t, lanes, d, sync, pre, add); };
-        if constexpr (DIRECT) row_direct<W>(a, s, n, first, span, acc, t, lanes, sync, walk);
-        else row_search<W>(a, s, n, acc, cols, pitch, t, lanes, sync, walk);
+        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP, W, S>(a, row, t, lanes, d, sync, pre, add); };
+        if constexpr (DIRECT) row_direct<W, S>(a, s, n, first, span, acc, t, lanes, sync, walk);
+        else row_search<W, S>(a, s, n, acc, cols, pitch, t, lanes, sync, walk);
     });
 }
 
 // Team class: VAL_TEAM_LANES lanes per row, the teams of a wave in step (wave-level ordering).
-template <class V, int W>
+template <class V, int W, class S = PlusTimes>
 __global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     const int team = threadIdx.x / VAL_TEAM_LANES, t = threadIdx.x % VAL_TEAM_LANES;
@@ -342,16 +348,16 @@ __global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __res
             cols[p] = a.C.col[s + p];
 #pragma unroll
             for (int w = 0; w < W; ++w)
-                if (w < nw) acc[(size_t)w * sl.ne + p] = V(0);
+                if (w < nw) acc[(size_t)w * sl.ne + p] = S::template identity<V>();
         }
         vwave_sync();
         if (n > 0)
-            walk_products<VAL_TEAM_LANES, W>(a, row, 0, 1, t, [&](int c, const ValSums<V, W>& v) {
+            walk_products<VAL_TEAM_LANES, W, S>(a, row, 0, 1, t, [&](int c, const ValSums<V, W>& v) {
                 const int slot = find_slot(cols, n, c);
                 if (slot >= 0) {
 #pragma unroll
                     for (int w = 0; w < W; ++w)
-                        if (w < nw) atomicAdd(&acc[(size_t)w * sl.ne + slot], v.x[w]);  // ds_add_f64 / ds_add_f32
+                        if (w < nw) S::lds(&acc[(size_t)w * sl.ne + slot], v.x[w]);  // ds_add_f64 / ds_add_f32, ds_min_* / ds_max_*
                 }
             });
         vwave_sync();
@@ -364,29 +370,29 @@ __global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __res
 }
 
 // Wave classes: one wave64 per row, WPB rows per block.
-template <class V, int W, bool DIRECT>
+template <class V, int W, bool DIRECT, class S = PlusTimes>
 __global__ __launch_bounds__(256) void k_val_wave(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     __shared__ ValStage<64, V, W> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     auto sync = [] { vwave_sync(); };
     for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB)
-        row_sums<DIRECT, W>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
+        row_sums<DIRECT, W, S>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
 }
 
 // Block classes: one block of T threads per row, up to the whole 160 KiB (VAL_BLOCK_BYTES dynamic + the stage).
-template <class V, int W, int T, bool DIRECT>
+template <class V, int W, int T, bool DIRECT, class S = PlusTimes>
 __global__ __launch_bounds__(T) void k_val_block(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     __shared__ ValStage<VAL_STAGE, V, W> stage;
     auto sync = [] { __syncthreads(); };
     const XcdStretch x = xcd_stretch(count);
     for (int idx = x.begin; idx < x.end; idx += x.step)
-        row_sums<DIRECT, W>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
+        row_sums<DIRECT, W, S>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
 }
 
 // Global class: the row's Cval segment -- of every set of the pass -- is the accumulator.
-template <class V, int W>
+template <class V, int W, class S = PlusTimes>
 __global__ __launch_bounds__(1024) void k_val_global(ValArgs<V> a, const int* __restrict__ list, int count) {
     const int t = threadIdx.x;
     const int nw = val_nw<W>(a);
@@ -396,15 +402,15 @@ __global__ __launch_bounds__(1024) void k_val_global(ValArgs<V> a, const int* __
 #pragma unroll
         for (int w = 0; w < W; ++w)
             if (w < nw)
-                for (int p = t; p < n; p += 1024) a.C.val[(long long)w * a.sC + (s + p)] = V(0);
+                for (int p = t; p < n; p += 1024) a.C.val[(long long)w * a.sC + (s + p)] = S::template identity<V>();
         __threadfence();
         __syncthreads();
-        walk_products<VAL_GROUP, W>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, const ValSums<V, W>& v) {
+        walk_products<VAL_GROUP, W, S>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, const ValSums<V, W>& v) {
             const int slot = find_slot(a.C.col + s, n, c);
             if (slot >= 0) {
 #pragma unroll
-                for (int w = 0; w < W; ++w)  // global_atomic_add_f64 / _f32
-                    if (w < nw) unsafeAtomicAdd(&a.C.val[(long long)w * a.sC + (s + slot)], v.x[w]);
+                for (int w = 0; w < W; ++w)  // global_atomic_add_f64 / _f32, global_atomic_min_f64 / _max_f64 (FP32: a loop)
+                    if (w < nw) S::glob(&a.C.val[(long long)w * a.sC + (s + slot)], v.x[w]);
             }
         });
     }
@@ -423,7 +429,7 @@ struct DotStage {
     int col[64];
     V av[W][64];
 };
-template <class V, int W>
+template <class V, int W, class S = PlusTimes>
 __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, const int* __restrict__ list, int count) {
     __shared__ DotStage<V, W> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -443,7 +449,7 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, cons
             }
             V sum[W];
 #pragma unroll
-            for (int w = 0; w < W; ++w) sum[w] = V(0);
+            for (int w = 0; w < W; ++w) sum[w] = S::template identity<V>();
             for (int k0 = a0; k0 < ae; k0 += 64) {
                 const int cnt = ae - k0 < 64 ? ae - k0 : 64;
                 if (lane < cnt) {
@@ -466,7 +472,7 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, cons
                             const int q = tr.tperm[lo];
 #pragma unroll
                             for (int w = 0; w < W; ++w)
-                                if (w < nw) sum[w] += d.av[w][e] * a.B.val[(long long)w * a.sB + q];
+                                if (w < nw) sum[w] = S::reg(sum[w], S::mul(d.av[w][e], a.B.val[(long long)w * a.sB + q]));
                         }
                     }
                 vwave_sync();
@@ -487,14 +493,15 @@ int blocks_for(long long items, int per, int cap) {
 }
 
 // The forward's kernels over the LDS classes' lists (val_lds_kernel), for the value type V and the width W
-template <class V, int W>
+// and the semiring policy S
+template <class V, int W, class S = PlusTimes>
 struct ValKernels {
     using Fn = void (*)(ValArgs<V>, const int*, int, int);
-    static Fn team() { return k_val_team<V, W>; }
+    static Fn team() { return k_val_team<V, W, S>; }
     template <bool DIRECT>
-    static Fn wave() { return k_val_wave<V, W, DIRECT>; }
+    static Fn wave() { return k_val_wave<V, W, DIRECT, S>; }
     template <int T, bool DIRECT>
-    static Fn block() { return k_val_block<V, W, T, DIRECT>; }
+    static Fn block() { return k_val_block<V, W, T, DIRECT, S>; }
 };
 
 // The kernels' static LDS is what the plan header says (val_static_lds: tests/valplan_batched_check.cpp sums it
@@ -511,20 +518,24 @@ static_assert(val_static_lds_holds<double, 1>() && val_static_lds_holds<double, 
 
 // The 1024-thread block kernels of (V, W) for the whole 160 KiB, and the team kernel for its launch cap where
 // that is past what a launch may take unasked (val_team_registers: FP64 at width 4)
-template <class V, int W>
+template <class V, int W, class S = PlusTimes>
 hipError_t val_register() {
-    hipError_t e = val_allow_max_lds<ValKernels<V, W>>();
+    hipError_t e = val_allow_max_lds<ValKernels<V, W, S>>();
     constexpr int sb = W * (int)sizeof(V);
     if (e == hipSuccess && val_team_registers(sb))
-        e = hipFuncSetAttribute((const void*)ValKernels<V, W>::team(), hipFuncAttributeMaxDynamicSharedMemorySize,
+        e = hipFuncSetAttribute((const void*)ValKernels<V, W, S>::team(), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 val_team_launch_cap(sb));
     return e;
 }
+// ... of every width on plus-times, and of the three other semirings at their one width
 template <class V>
 hipError_t val_register_widths() {
     hipError_t e = val_register<V, 1>();
     if (e == hipSuccess) e = val_register<V, 2>();
     if (e == hipSuccess) e = val_register<V, 4>();
+    if (e == hipSuccess) e = val_register<V, 1, SrPolicy<SR_MIN_PLUS>>();
+    if (e == hipSuccess) e = val_register<V, 1, SrPolicy<SR_MAX_PLUS>>();
+    if (e == hipSuccess) e = val_register<V, 1, SrPolicy<SR_MAX_MIN>>();
     return e;
 }
 
@@ -569,25 +580,35 @@ void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s) {
 }
 
 namespace {
-template <class V, int W>
+template <class V, int W, class S = PlusTimes>
 void issue_width(const ValLaunch& l, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s) {
     const dim3 g(l.grid), b(l.block);
-    if (const typename ValKernels<V, W>::Fn k = val_lds_kernel<ValKernels<V, W>>(l.kernel, l.block))
+    if (const typename ValKernels<V, W, S>::Fn k = val_lds_kernel<ValKernels<V, W, S>>(l.kernel, l.block))
         hipLaunchKernelGGL(k, g, b, l.lds, s, a, list, l.count, l.region);
-    else if (l.kernel == VK_GLOBAL) hipLaunchKernelGGL((k_val_global<V, W>), g, b, 0, s, a, list, l.count);
-    else if (l.kernel == VK_DOT) hipLaunchKernelGGL((k_val_dot<V, W>), g, b, 0, s, a, t, list, l.count);
+    else if (l.kernel == VK_GLOBAL) hipLaunchKernelGGL((k_val_global<V, W, S>), g, b, 0, s, a, list, l.count);
+    else if (l.kernel == VK_DOT) hipLaunchKernelGGL((k_val_dot<V, W, S>), g, b, 0, s, a, t, list, l.count);
 }
 }  // namespace
 
 template <class V>
-void issue_values(const ValLaunch& l, int width, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s) {
+void issue_values(const ValLaunch& l, int width, int semiring, const ValArgs<V>& a, const ValTrans& t, const int* list,
+                  hipStream_t s) {
+    if (semiring != SR_PLUS_TIMES) {  // (width 1: no other plan of such a semiring is made)
+        if (width != 1) return;
+        switch (semiring) {
+        case SR_MIN_PLUS: return issue_width<V, 1, SrPolicy<SR_MIN_PLUS>>(l, a, t, list, s);
+        case SR_MAX_PLUS: return issue_width<V, 1, SrPolicy<SR_MAX_PLUS>>(l, a, t, list, s);
+        case SR_MAX_MIN: return issue_width<V, 1, SrPolicy<SR_MAX_MIN>>(l, a, t, list, s);
+        }
+        return;
+    }
     switch (width) {  // (a width that is none of these made no plan: nothing to launch)
     case 1: return issue_width<V, 1>(l, a, t, list, s);
     case 2: return issue_width<V, 2>(l, a, t, list, s);
     case 4: return issue_width<V, 4>(l, a, t, list, s);
     }
 }
-template void issue_values<double>(const ValLaunch&, int, const ValArgs<double>&, const ValTrans&, const int*, hipStream_t);
-template void issue_values<float>(const ValLaunch&, int, const ValArgs<float>&, const ValTrans&, const int*, hipStream_t);
+template void issue_values<double>(const ValLaunch&, int, int, const ValArgs<double>&, const ValTrans&, const int*, hipStream_t);
+template void issue_values<float>(const ValLaunch&, int, int, const ValArgs<float>&, const ValTrans&, const int*, hipStream_t);
 
 }  // namespace mhs

@@ -13,6 +13,9 @@
 // classifies at the sum bytes width x size.  Every forward call is spgemm_values_batched: ceil(nb / width)
 // passes of the launch list inside the one run_values frame; the unbatched entry points are its nb = 1.  The
 // batched backward (mhs_spgemm_values_grad_batched) makes the same passes over the backward's launch list.
+// A plan has a semiring too (mhs_values_plan_create_semiring; mhs_semiring.hpp), fixed likewise: classes and launch
+// plans do not depend on it, the forward's issue passes it on to the kernels' policy, and the backward entry points
+// refuse a plan of another semiring than plus-times (check_grad_semiring).
 // Kernels and launchers: mhs_values.hip, mhs_values_grad.hip (declared in mhs_valwalk.hpp); classes,
 // launch plans, counter block and status words: mhs_valplan.hpp.
 #include "mhs_ctx.hpp"
@@ -30,6 +33,7 @@ struct mhs_values_plan {
     int device = 0;
     int dtype = MHS_F64;    // mhs_dtype: the type of every value array of its calls
     int width = 1;          // value sets a walk of its forward kernels sums (1, 2 or 4)
+    int semiring = SR_PLUS_TIMES;  // mhs_semiring: what its forward kernels reduce the kept products with
     ValPattern pat{};
     long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
     long long kept = 0;    // products that land in C's pattern (masked plans count them; else = products)
@@ -60,6 +64,9 @@ constexpr int dtype_of() {
     return sizeof(V) == VAL_VB_F32 ? MHS_F32 : MHS_F64;
 }
 
+static_assert((int)MHS_SR_PLUS_TIMES == (int)SR_PLUS_TIMES && (int)MHS_SR_MIN_PLUS == (int)SR_MIN_PLUS &&
+                  (int)MHS_SR_MAX_PLUS == (int)SR_MAX_PLUS && (int)MHS_SR_MAX_MIN == (int)SR_MAX_MIN,
+              "mhs_semiring is ValSemiring");
 static_assert((int)MHS_MASK_AUTO == (int)VM_AUTO && (int)MHS_MASK_PRODUCT == (int)VM_PRODUCT && (int)MHS_MASK_DOT == (int)VM_DOT,
               "mhs_mask_form is ValMaskForm");
 
@@ -209,11 +216,19 @@ struct PlanBuild {
 // mhs_values_plan_create (masked false: C must contain the product's pattern) and
 // mhs_values_plan_create_masked (C is a mask; form: mhs_mask_form), for values of `dtype` (mhs_dtype).
 // width: the value sets a walk sums (mhs_values_plan_create_batched; 1 for every other entry point).
+// semiring: mhs_semiring (mhs_values_plan_create_semiring; MHS_SR_PLUS_TIMES for every other entry point); another
+// one than plus-times has width 1.
 int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form, int dtype,
-                       int width, mhs_values_plan** out) {
+                       int width, int semiring, mhs_values_plan** out) {
     if (!ctx) return MHS_ERR_INVALID;
     if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
     *out = nullptr;
+    if (!val_semiring_ok(semiring))
+        return fail(ctx, MHS_ERR_INVALID,
+                    "mhs_values_plan_create: semiring " + std::to_string(semiring) + " is not an mhs_semiring (0 to 3)");
+    if (semiring != SR_PLUS_TIMES && width != 1)
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string("mhs_values_plan_create: a ") + val_semiring_name(semiring) + " plan has width 1");
     if (dtype != MHS_F64 && dtype != MHS_F32)
         return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: dtype is not an mhs_dtype (MHS_F64 or MHS_F32)");
     if (!val_width_ok(width))
@@ -233,6 +248,7 @@ int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const m
     p->device = ctx->device;
     p->dtype = dtype;
     p->width = width;
+    p->semiring = semiring;
     p->pat = ValPattern{A->M, A->ptr, A->col, B->ptr, B->col, C->ptr, C->col};
     p->nnzA = A->nnz, p->nnzB = B->nnz, p->nnzC = C->nnz;
     Scratch sort_tmp;  // (B^T's sort scratch: it outlives the build's last step, which syncs the stream either way)
@@ -315,7 +331,7 @@ int spgemm_values_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V* Ava
                              {p->pat.Cptr, p->pat.Ccol, Cval + b * sC}};
                 a.sA = sA, a.sB = sB, a.sC = sC;
                 a.nw = nb - b < W ? (int)(nb - b) : W;
-                issue_values(l, W, a, p->trans, list, s);
+                issue_values(l, W, p->semiring, a, p->trans, list, s);
             }
         });
 }
@@ -329,6 +345,14 @@ int check_grad_width(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
                     "): a width-1 plan has to be used");
 }
 
+// Whether a backward entry point may run on the plan: min and max have subgradients only, which are not built
+int check_grad_semiring(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
+    if (p->semiring == SR_PLUS_TIMES) return MHS_OK;
+    return fail(ctx, MHS_ERR_INVALID,
+                std::string(call) + ": the plan's semiring is " + val_semiring_name(p->semiring) +
+                    ": the backward is built for plus_times plans only");
+}
+
 // mhs_spgemm_values_grad and mhs_spgemm_values_grad_f32
 template <class V>
 int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V* Bval, const V* dCval, V* dAval, V* dBval,
@@ -336,6 +360,7 @@ int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V*
     if (!ctx) return MHS_ERR_INVALID;
     if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
     if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (const int rc = check_grad_semiring(ctx, p, call)) return rc;
     if (const int rc = check_grad_width(ctx, p, call)) return rc;
     if (!dCval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null dCval");
     if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": no output (dAval and dBval are both null)");
@@ -375,6 +400,7 @@ int spgemm_values_grad_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V
     if (!ctx) return MHS_ERR_INVALID;
     if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
     if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (const int rc = check_grad_semiring(ctx, p, call)) return rc;
     if (nb < 1) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": nb = " + std::to_string(nb) + " (at least one value set)");
     if (sA < 0 || sB < 0 || sG < 0 || sDA < 0 || sDB < 0) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": negative stride");
     if ((sA > 0 && sA < p->nnzA) || (sB > 0 && sB < p->nnzB))
@@ -419,22 +445,35 @@ int spgemm_values_grad_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V
 }  // namespace
 
 int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1, out);
+    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1, MHS_SR_PLUS_TIMES, out);
 }
 
 int mhs_values_plan_create_masked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int form,
                                   mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, 1, out);
+    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, 1, MHS_SR_PLUS_TIMES, out);
 }
 
 int mhs_values_plan_create_typed(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                  int dtype, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, out);
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, MHS_SR_PLUS_TIMES,
+                              out);
 }
 
 int mhs_values_plan_create_batched(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                    int dtype, int width, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, width, out);
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, width, MHS_SR_PLUS_TIMES,
+                              out);
+}
+
+int mhs_values_plan_create_semiring(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
+                                    int dtype, int semiring, mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, semiring, out);
+}
+
+int mhs_values_plan_semiring(const mhs_values_plan* p, int* semiring) {
+    if (!p || !semiring) return MHS_ERR_INVALID;
+    *semiring = p->semiring;
+    return MHS_OK;
 }
 
 int mhs_values_plan_width(const mhs_values_plan* p, int* width) {

@@ -6,6 +6,7 @@
 // walks read their B rows from, and the kernel of a launch.
 #pragma once
 #include "mhs_internal.hpp"
+#include "mhs_semiring.hpp"
 #include "mhs_valplan.hpp"
 
 #include <initializer_list>
@@ -79,9 +80,11 @@ void launch_val_classify_masked(const ValPattern& p, const ValMask& m, int vb, i
 void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s);
 // One launch of a values plan (plan_values) over its class's row list, on `s` (t: read by VK_DOT only).
 // V (double or float, both instantiated in mhs_values.hip) and `width` (1, 2 or 4) must be the type and the
-// width the plan was classified for: the kernels' slice guards are taken at width x sizeof(V).
+// width the plan was classified for: the kernels' slice guards are taken at width x sizeof(V).  `semiring`
+// (ValSemiring) is the plan's: SR_PLUS_TIMES at any width, the others at width 1 only.
 template <class V>
-void issue_values(const ValLaunch& l, int width, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s);
+void issue_values(const ValLaunch& l, int width, int semiring, const ValArgs<V>& a, const ValTrans& t, const int* list,
+                  hipStream_t s);
 // One launch of a values plan's backward (plan_grad) over its class's row list, on `s` (mhs_values_grad.hip).
 // V and `width` as for issue_values: the backward's kernels hold `width` cotangents per C entry where the
 // forward's hold as many sums, behind the same slice guards.
@@ -97,6 +100,29 @@ static __device__ __forceinline__ void vwave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// The policy of a value kernel: the plan's semiring (mhs_semiring.hpp: identity, mul, reg) with the reduce of one
+// product into an LDS sum (lds: workgroup scope) and into the row's Cval segment (glob: the global class, agent
+// scope), both relaxed and without a return value.  Plus-times: ds_add_f64 / ds_add_f32 and global_atomic_add_f64 /
+// _f32, as before there was a policy.  min and max: ds_min_f64 / ds_max_f64 / ds_min_f32 / ds_max_f32 in LDS and
+// global_atomic_min_f64 / _max_f64 in memory; gfx950 has no float min / max in global memory, so the FP32 global
+// class reduces by a compare-and-swap loop.
+template <int SR>
+struct SrPolicy : SrValue<SR> {
+    template <class V>
+    static __device__ __forceinline__ void lds(V* p, V v) {
+        if constexpr (SR == SR_PLUS_TIMES) atomicAdd(p, v);
+        else if constexpr (SR == SR_MIN_PLUS) (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        else (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    template <class V>
+    static __device__ __forceinline__ void glob(V* p, V v) {
+        if constexpr (SR == SR_PLUS_TIMES) unsafeAtomicAdd(p, v);
+        else if constexpr (SR == SR_MIN_PLUS) (void)__hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+using PlusTimes = SrPolicy<SR_PLUS_TIMES>;  // the default of every kernel template: existing call sites read as before
 
 // Position of column c in the ascending cols[0, n), or -1.
 static __device__ __forceinline__ int find_slot(const int* cols, int n, int c) {

@@ -2,7 +2,7 @@
 // on top of the C-ABI, printing the reference's stdout lines.
 //
 //   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32]
-//          [--batch NB] [--width W] <file.mtx>
+//          [--batch NB] [--width W] [--semiring NAME] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -52,6 +52,15 @@
 //             every set of both gradients against the unbatched backward of the same type on that set -- each is
 //             within 1.01 m u S of the exact sum (u = 2^-53 or 2^-24), so within twice that of the other, and
 //             exactly 0 where m = 0 (m from the unbatched backward on all-ones; S: the positive values' own result).
+//   --semiring NAME  a modifier of --reuse and --masked (NAME: plus_times, min_plus, max_plus or max_min): after
+//             them, each chosen mode once more on a plan of that semiring (mhs_values_plan_create_semiring) on the
+//             operands' values, N calls of mhs_spgemm_values, and with --f32 also on an FP32 plan on the values
+//             rounded to float: one more line per mode and type with the median time, and with --check the result
+//             against a sequential host loop over the products in the plan's value type, for equality (zeros equal
+//             whatever their sign; plus_times, whose sums have no fixed order, to rounding of the products' absolute
+//             sum): "values NAME pass" / "masked NAME pass" ("... NAME f32 pass"), or "error".
+//             Without --reuse or --masked, or with another name: the usage message.  Without the switch nothing is
+//             added to the output.
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -64,6 +73,7 @@
 #include <fstream>
 #include <iomanip>
 #include <iostream>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -309,6 +319,80 @@ static void run_f32(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool 
     }
 }
 
+// ---- --semiring NAME: a values mode once more on a plan of that semiring, in T (double, or float on rounded values)
+static const char* const SEMIRING_NAMES[4] = {"plus_times", "min_plus", "max_plus", "max_min"};
+static int semiring_of(const char* name) {
+    for (int s = 0; s < 4; ++s)
+        if (!std::strcmp(name, SEMIRING_NAMES[s])) return s;
+    return -1;
+}
+static int semiring_call(mhs_shim::ValuesPlan& p, const double* a, const double* b, double* c) {
+    return mhs_spgemm_values(p.ctx, p.plan, a, b, c, &p.last_ms);
+}
+static int semiring_call(mhs_shim::ValuesPlan& p, const float* a, const float* b, float* c) {
+    return mhs_spgemm_values_f32(p.ctx, p.plan, a, b, c, &p.last_ms);
+}
+// The sequential reference: every product of A's and B's entries in their order, reduced into its slot of P's row.
+// mag (plus_times): per entry the sum of its products' absolute values, what a sum's rounding is measured against
+template <class T>
+static std::vector<T> semiring_host(int sr, const CSR& A, const CSR& B, const CSR& P, const std::vector<T>& av,
+                                    const std::vector<T>& bv, std::vector<double>& mag) {
+    const T inf = std::numeric_limits<T>::infinity();
+    const T identity = sr == MHS_SR_PLUS_TIMES ? T(0) : sr == MHS_SR_MIN_PLUS ? inf : -inf;
+    std::vector<T> c((size_t)P.nnz, identity);
+    mag.assign((size_t)P.nnz, 0.0);
+    for (int i = 0; i < A.M; ++i) {
+        const int *row = P.col + P.ptr[i], *end = P.col + P.ptr[i + 1];
+        for (int k = A.ptr[i]; k < A.ptr[i + 1]; ++k)
+            for (int j = B.ptr[A.col[k]]; j < B.ptr[A.col[k] + 1]; ++j) {
+                const int* hit = std::lower_bound(row, end, B.col[j]);
+                if (hit == end || *hit != B.col[j]) continue;  // (outside a mask)
+                T& x = c[(size_t)(hit - P.col)];
+                const T a = av[(size_t)k], b = bv[(size_t)j];
+                if (sr == MHS_SR_PLUS_TIMES) x += a * b, mag[(size_t)(hit - P.col)] += std::fabs((double)a * (double)b);
+                else if (sr == MHS_SR_MIN_PLUS) x = std::min(x, a + b);
+                else if (sr == MHS_SR_MAX_PLUS) x = std::max(x, a + b);
+                else x = std::max(x, std::min(a, b));
+            }
+    }
+    return c;
+}
+// P: the plan's C pattern, with its host arrays (masked: a mask)
+template <class T>
+static void run_semiring(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool masked, int sr, int calls, bool check,
+                         const char* label, const char* tag) {
+    const bool f32 = sizeof(T) == sizeof(float);
+    const char* name = SEMIRING_NAMES[sr];
+    try {
+        const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)P.nnz;
+        std::vector<T> av(nA), bv(nB);
+        for (size_t i = 0; i < nA; ++i) av[i] = (T)A.val[i];
+        for (size_t i = 0; i < nB; ++i) bv[i] = (T)B.val[i];
+        mhs_shim::ValuesPlan plan(tools, A, B, P, masked, MHS_MASK_AUTO, f32 ? MHS_F32 : MHS_F64, 1, sr);
+        DevArr<T> da(nA), db(nB), dc(nC);
+        da.put(av), db.put(bv);
+        std::vector<double> t;
+        for (int i = 0; i < calls; ++i) {
+            f32_ok(plan.ctx, semiring_call(plan, da.p, db.p, dc.p));
+            t.push_back(plan.last_ms);
+        }
+        std::printf("MH-SpGEMM %s %s %s median of %d calls is %.3lf ms\n", label, name, f32 ? "FP32" : "FP64", calls, median(t));
+        if (check) {
+            // (plus_times sums in another order than the kernels, so to rounding: equality is the other three's contract)
+            std::vector<double> mag;
+            const std::vector<T> want = semiring_host<T>(sr, A, B, P, av, bv, mag), got = dc.get();
+            bool ok = got.size() == want.size();
+            for (size_t i = 0; ok && i < nC; ++i) {
+                const double g = (double)got[i], w = (double)want[i];
+                ok = sr == MHS_SR_PLUS_TIMES ? std::fabs(g - w) <= (f32 ? 1e-4 : 1e-12) * mag[i] : got[i] == want[i];
+            }
+            std::printf("%s %s%s %s\n", tag, name, f32 ? " f32" : "", ok ? "pass" : "error");
+        }
+    } catch (const std::exception&) {
+        std::printf("%s %s%s error\n", tag, name, f32 ? " f32" : "");
+    }
+}
+
 // --batch NB: NB seeded value sets in one batched call on a plan of `width`, beside NB unbatched calls on a
 // width-1 plan of the same type T; with check every set of the batched call against its reference (see the top).
 template <class T>
@@ -443,7 +527,8 @@ static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C
 }
 
 int main(int argc, char** argv) {
-    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0;
+    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0, semiring = -1;
+    bool has_semiring = false;
     bool aat = false, vendor = false, check = false, cache = false, f32 = false;
     std::string csv;
     const char* filename = nullptr;
@@ -465,14 +550,20 @@ int main(int argc, char** argv) {
             width = std::atoi(argv[++i]);
             bad = bad || !(width == 1 || width == 2 || width == 4);
         }
+        else if (!std::strcmp(argv[i], "--semiring") && i + 1 < argc) {
+            semiring = semiring_of(argv[++i]);
+            has_semiring = true;
+            bad = bad || semiring < 0;
+        }
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
+    if (has_semiring && reuse <= 0 && masked <= 0) bad = true;  // (a modifier of --reuse and --masked)
     if ((batch > 0 && reuse <= 0) || (width > 0 && batch <= 0)) bad = true;  // (modifiers of --reuse and of --batch)
     if (width == 0) width = MHS_VAL_WIDTH_MAX;
     if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0 || grad < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--batch NB] [--width W] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--batch NB] [--width W] [--semiring NAME] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -600,6 +691,20 @@ int main(int argc, char** argv) {
             if (grad > 0) {
                 run_grad_batch<double>(tools, A, B, C, grad, batch, width, check);
                 if (f32) run_grad_batch<float>(tools, A, B, C, grad, batch, width, check);
+            }
+        }
+        if (has_semiring) {
+            if (reuse > 0) {
+                C.D2H();  // (the pattern's host arrays)
+                run_semiring<double>(tools, A, B, C, false, semiring, reuse, check, "values-only (pattern reused)", "values");
+                if (f32) run_semiring<float>(tools, A, B, C, false, semiring, reuse, check, "values-only (pattern reused)", "values");
+            }
+            if (masked > 0 && A.M == A.N) {
+                CSR mask;  // A's pattern (a plan reads no values)
+                const bool owns = mask_of(A, B.N, mask);
+                run_semiring<double>(tools, A, B, mask, true, semiring, masked, check, "masked (A's pattern)", "masked");
+                if (f32) run_semiring<float>(tools, A, B, mask, true, semiring, masked, check, "masked (A's pattern)", "masked");
+                unborrow_mask(mask, owns);
             }
         }
         C.d_release_csr();

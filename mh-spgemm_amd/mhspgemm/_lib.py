@@ -48,6 +48,11 @@ MHS_MASK_DOT = 2
 MHS_F64 = 0
 MHS_F32 = 1
 MHS_VAL_WIDTH_MAX = 4  # a values plan's width is 1, 2 or 4
+# mhs_semiring: what a values plan reduces the kept products with
+MHS_SR_PLUS_TIMES = 0
+MHS_SR_MIN_PLUS = 1
+MHS_SR_MAX_PLUS = 2
+MHS_SR_MAX_MIN = 3
 
 STATUS_NAMES = {0: "MHS_OK", 1: "MHS_ERR_HIP", 2: "MHS_ERR_OOM", 3: "MHS_ERR_INVALID",
                 4: "MHS_ERR_OVERFLOW", 5: "MHS_ERR_IO"}
@@ -206,6 +211,12 @@ def lib() -> ctypes.CDLL:
                 fn.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                c_void_p, c_int64, c_void_p, c_int64, P(ctypes.c_double)]
                 fn.restype = c_int
+        if hasattr(L, "mhs_values_plan_create_semiring"):  # (semiring values plans: a later addition to ABI 10)
+            L.mhs_values_plan_create_semiring.argtypes = [c_void_p, P(mhs_csr), P(mhs_csr), P(mhs_csr), c_int, c_int, c_int,
+                                                          c_int, P(c_void_p)]
+            L.mhs_values_plan_create_semiring.restype = c_int
+            L.mhs_values_plan_semiring.argtypes = [c_void_p, P(c_int)]
+            L.mhs_values_plan_semiring.restype = c_int
     if hasattr(L, "mhs_ctx_fence_default_stream"):  # (a later addition to ABI 10)
         L.mhs_ctx_fence_default_stream.argtypes = [c_void_p, c_int]
         L.mhs_ctx_fence_default_stream.restype = c_int

@@ -371,6 +371,8 @@ VALUES_CLASSES = ("none", "team", "wave_direct", "wave_search", "block_direct", 
 MASK_FORMS = {"auto": L.MHS_MASK_AUTO, "product": L.MHS_MASK_PRODUCT, "dot": L.MHS_MASK_DOT}
 VALUES_DTYPES = {"float64": L.MHS_F64, "float32": L.MHS_F32}
 VALUES_WIDTHS = (1, 2, 4)
+SEMIRINGS = {"plus_times": L.MHS_SR_PLUS_TIMES, "min_plus": L.MHS_SR_MIN_PLUS, "max_plus": L.MHS_SR_MAX_PLUS,
+             "max_min": L.MHS_SR_MAX_MIN}
 
 
 def values_width(width) -> int:
@@ -417,10 +419,25 @@ class ValuesPlan:
     patterns sums in ``run_batched``: rows are classified for ``width`` sums per C entry, so ``info()`` differs
     from the width-1 plan's.  Any plan runs any batch.  ``grad_batched`` is the backward of ``run_batched``
     (mhs_spgemm_values_grad_batched) and ``apply_batched`` the pair as a ``torch.autograd.Function``, both on a plan
-    of any width; the unbatched ``grad`` and ``apply`` serve width-1 plans only."""
+    of any width; the unbatched ``grad`` and ``apply`` serve width-1 plans only.
 
-    def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto", dtype="float64", width=1):
+    ``semiring`` (``"plus_times"``, the default, ``"min_plus"``, ``"max_plus"`` or ``"max_min"``;
+    mhs_values_plan_create_semiring) is what the kept products are reduced with: ``C(i,j) = min_k A(i,k) + B(k,j)``
+    and its kin.  Such a plan has width 1 (``ValueError`` otherwise), classifies its rows as the plus-times plan
+    does, gives entries no kept product reaches the identity (+Inf, -Inf, -Inf) and results that are bit-identical to
+    a sequential evaluation; ``run`` and ``run_batched`` serve it, ``grad``, ``grad_batched``, ``apply`` and
+    ``apply_batched`` raise the library's refusal (there is no backward of min and max)."""
+
+    _semiring = "plus_times"
+
+    def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto", dtype="float64", width=1,
+                 semiring="plus_times"):
         self.width = values_width(width)
+        if not isinstance(semiring, str) or semiring not in SEMIRINGS:
+            raise ValueError(f"semiring: one of {sorted(SEMIRINGS)}, not {semiring!r}")
+        self._semiring = semiring
+        if semiring != "plus_times" and self.width != 1:
+            raise ValueError(f"width: a {semiring} plan has width 1, not {self.width}")
         if not hasattr(L.lib(), "mhs_values_plan_create"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no values-only entry points")
         if masked and not hasattr(L.lib(), "mhs_values_plan_create_masked"):
@@ -431,6 +448,8 @@ class ValuesPlan:
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no batched values entry points")
         if self.f32 and not hasattr(L.lib(), "mhs_values_plan_create_typed"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no FP32 values entry points")
+        if semiring != "plus_times" and not hasattr(L.lib(), "mhs_values_plan_create_semiring"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no semiring values entry points")
         if isinstance(form, str):
             if form not in MASK_FORMS:
                 raise ValueError(f"form: one of {sorted(MASK_FORMS)}, not {form!r}")
@@ -446,7 +465,12 @@ class ValuesPlan:
         self.nnzA, self.nnzB, self.nnzC = int(a.nnz), int(b.nnz), int(c.nnz)
         self.plan = ctypes.c_void_p()
         self._pad = None
-        if self.width > 1:
+        if semiring != "plus_times":
+            rc = L.lib().mhs_values_plan_create_semiring(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                         int(self.masked), self.form, VALUES_DTYPES[self.dtype_name],
+                                                         SEMIRINGS[semiring], ctypes.byref(self.plan))
+            _check(tool.ctx, rc, "mhs_values_plan_create_semiring")
+        elif self.width > 1:
             rc = L.lib().mhs_values_plan_create_batched(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
                                                         int(self.masked), self.form, VALUES_DTYPES[self.dtype_name],
                                                         self.width, ctypes.byref(self.plan))
@@ -468,6 +492,18 @@ class ValuesPlan:
     def dtype(self):
         """The plan's value type as a torch dtype."""
         return getattr(_torch(), self.dtype_name)
+
+    @property
+    def semiring(self) -> str:
+        """The plan's semiring by name (a key of ``SEMIRINGS``)."""
+        return self._semiring
+
+    def _refuse_backward(self, what):
+        """The library's refusal of a backward call on a plan of another semiring than plus-times, before anything
+        runs or is written."""
+        if self._semiring != "plus_times":
+            call = L.lib().mhs_spgemm_values_grad_f32 if self.f32 else L.lib().mhs_spgemm_values_grad
+            _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None, None), what)
 
     def _ptr(self, t, n, what):
         if t is None:
@@ -574,6 +610,7 @@ class ValuesPlan:
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no mhs_spgemm_values_grad")
         if not (need_A or need_B):
             raise ValueError("ValuesPlan.grad: need_A or need_B")
+        self._refuse_backward("ValuesPlan.grad")
         torch = _torch()
         dev = f"cuda:{self.tool.device}"
         gp = self._ptr(dC, self.nnzC, "dC")
@@ -603,6 +640,7 @@ class ValuesPlan:
         (once differentiable).  Both are ordered on torch's current stream, also with MHS_OPT_SYNC 0: a stream
         of torch's making is handed to the tool; torch's default stream (the null stream, handle 0) cannot be,
         so there the calls run on the tool's own stream between two fences (``Tool.fence_default_stream``)."""
+        self._refuse_backward("ValuesPlan.apply")
         if self.width > 1:  # no backward on a batched plan: the library's refusal, before the forward runs
             call = L.lib().mhs_spgemm_values_grad_f32 if self.f32 else L.lib().mhs_spgemm_values_grad
             _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None, None), "ValuesPlan.apply")
@@ -624,6 +662,7 @@ class ValuesPlan:
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no batched backward entry points")
         if not (need_A or need_B):
             raise ValueError("ValuesPlan.grad_batched: need_A or need_B")
+        self._refuse_backward("ValuesPlan.grad_batched")
         torch = _torch()
         if not (isinstance(dC, torch.Tensor) and dC.dim() == 2):
             raise ValueError(f"dC: a {self.dtype_name} tensor of shape [nb, {self.nnzC}]")
@@ -681,6 +720,7 @@ class ValuesPlan:
         a plan of any width: the forward is ``run_batched`` into a fresh ``[nb, nnz(C)]`` tensor, the backward
         ``grad_batched`` for the inputs that need it (once differentiable), both ordered on torch's current stream
         as in ``apply``.  The gradient of a 1-D (shared) operand is the per-set gradients summed over the sets."""
+        self._refuse_backward("ValuesPlan.apply_batched")
         return _values_batched_function().apply(self, Aval, Bval)
 
     def _ordered_on_current_stream(self, call):
@@ -700,7 +740,8 @@ class ValuesPlan:
     def info(self) -> dict:
         """Rows per class (by name and as the ``rows`` list indexed by class id), products, nnzC, plan_bytes,
         kept_products: the products that land in C's pattern (all of them unless the plan is masked), dtype:
-        the plan's value type by name, and width: its value sets per walk (both as the library reports them)."""
+        the plan's value type by name, width: its value sets per walk, and semiring: its semiring by name (all three
+        as the library reports them)."""
         i = L.mhs_values_info()
         _check(self.tool.ctx, L.lib().mhs_values_plan_info(self.plan, ctypes.byref(i)), "mhs_values_plan_info")
         rows = [int(x) for x in i.rows]
@@ -721,6 +762,11 @@ class ValuesPlan:
             w = ctypes.c_int(0)
             _check(self.tool.ctx, L.lib().mhs_values_plan_width(self.plan, ctypes.byref(w)), "mhs_values_plan_width")
             d["width"] = int(w.value)
+        d["semiring"] = "plus_times"
+        if hasattr(L.lib(), "mhs_values_plan_semiring"):
+            sr = ctypes.c_int(0)
+            _check(self.tool.ctx, L.lib().mhs_values_plan_semiring(self.plan, ctypes.byref(sr)), "mhs_values_plan_semiring")
+            d["semiring"] = {v: k for k, v in SEMIRINGS.items()}[int(sr.value)]
         return d
 
     def close(self):

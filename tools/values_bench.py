@@ -2,6 +2,7 @@
 """values_bench.py -- the repeated full call against the values-only call, one config per run.
 
     python tools/values_bench.py [--config cant] [--blocks 5] [--window 0.4] [--full-only] [--dtype f32|f64]
+                                 [--semiring plus_times|min_plus|max_plus|max_min]
 
 (a) the repeated full call, timed as bench.py times its steps: mhs_spgemm on one pair of
     operands, speculation on, MHS_OPT_SYNC 0 on torch's current stream, each C handed back to
@@ -19,6 +20,11 @@ as faster only when it is below (a) by more than the larger spread.
 --dtype f32 runs (b) through an FP32 plan on float32 values.  Its check is then against an FP64 plan on the same
 rounded values: every entry within 1.01 m 2^-24 S, m and S from the FP64 plan on all-ones and on absolute
 values; the FP64 plan's rows by class are reported beside the FP32 plan's (`classes_f64`).
+
+--semiring NAME (default plus_times) runs (b) through a plan of that semiring, of either --dtype, on the same
+values.  Its check is then an equality: every entry against a sequential reduce of the products in the plan's
+dtype (index arithmetic and scatter_reduce in torch, A's entries a slice at a time).  The JSON line carries the
+name as `semiring` and is otherwise the one of the plus-times run.
 
 --full-only times (a) alone and needs nothing of the values-only entry points, so it also runs
 against an older library (MHS_LIB=/path/to/libmhspgemm.so).  Prints one JSON line."""
@@ -44,6 +50,34 @@ from mhspgemm import _lib as L  # noqa: E402
 from mhspgemm import synth  # noqa: E402
 
 
+def semiring_reference(name, A, Cptr, Ccol, av, bv, chunk=1 << 24):
+    """C's values of A (x) A under `name` on the pattern (Cptr, Ccol): every product av[p] (x) bv[q] reduced into its
+    slot, about `chunk` products at a time.  av, bv: device tensors of one dtype; the result has it."""
+    dev = av.device
+    Ap, Ac = (torch.from_numpy(np.asarray(x, np.int64)).to(dev) for x in (A.ptr, A.col))
+    Cp, Cc = (torch.from_numpy(np.asarray(x, np.int64)).to(dev) for x in (Cptr, Ccol))
+    N = int(A.N)
+    rowA = torch.repeat_interleave(torch.arange(A.M, device=dev), Ap[1:] - Ap[:-1])
+    keyC = torch.repeat_interleave(torch.arange(A.M, device=dev), Cp[1:] - Cp[:-1]) * N + Cc
+    lens = Ap[Ac + 1] - Ap[Ac]
+    ends = torch.cumsum(lens, 0)
+    identity = float("inf") if name == "min_plus" else float("-inf")
+    out = torch.full((len(Ccol),), identity, dtype=av.dtype, device=dev)
+    a0 = 0
+    while a0 < len(Ac):
+        done = int(ends[a0 - 1]) if a0 else 0
+        a1 = max(a0 + 1, int(torch.searchsorted(ends, torch.tensor(done + chunk, device=dev), right=True)))
+        n = lens[a0:a1]
+        p = torch.repeat_interleave(torch.arange(a0, a1, device=dev), n)
+        start = ends[a0:a1] - n - done
+        q = Ap[Ac[p]] + torch.arange(len(p), device=dev) - torch.repeat_interleave(start, n)
+        slot = torch.searchsorted(keyC, rowA[p] * N + Ac[q])
+        prod = torch.minimum(av[p], bv[q]) if name == "max_min" else av[p] + bv[q]
+        out.scatter_reduce_(0, slot, prod, "amin" if name == "min_plus" else "amax", include_self=True)
+        a0 = a1
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="cant", help="a BASELINE matrix name (mhspgemm.synth.SYNTH); default cant")
@@ -52,8 +86,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--full-only", action="store_true", help="time the repeated full call alone")
     ap.add_argument("--dtype", default="f64", choices=("f32", "f64"), help="the values plan's value type")
+    ap.add_argument("--semiring", default="plus_times", choices=tuple(getattr(mhspgemm.core, "SEMIRINGS", {"plus_times": 0})),
+                    help="the values plan's semiring")
     args = ap.parse_args()
     f32 = args.dtype == "f32"
+    semiring = args.semiring != "plus_times"
 
     dev = 0
     torch.cuda.set_device(dev)
@@ -67,7 +104,7 @@ def main():
         torch.cuda.synchronize(dev)
 
     out = {"config": args.config, "source": source, "M": A.M, "nnzA": A.nnz, "flop": int(flop), "blocks": args.blocks,
-           "lib": L.lib_path(), "dtype": args.dtype}
+           "lib": L.lib_path(), "dtype": args.dtype, "semiring": args.semiring}
 
     # ---- the pattern, and (b)'s check against the full product of the same new operands
     C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
@@ -75,7 +112,24 @@ def main():
     plan = None
     vals = []
     res32 = None
-    if not args.full_only and f32:
+    if not args.full_only and semiring:
+        tdtype = torch.float32 if f32 else torch.float64
+        plan = mhspgemm.ValuesPlan(tool, A, A, C, dtype="float32" if f32 else "float64", semiring=args.semiring)
+        info = plan.info()
+        out["classes"] = {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}
+        out["plan_bytes"] = info["plan_bytes"]
+        rng = np.random.default_rng(17)
+        for _ in range(2):
+            vals.append(tuple(torch.from_numpy(rng.uniform(0.1, 1.0, A.nnz)).to(f"cuda:{dev}").to(tdtype) for _ in range(2)))
+        res32 = torch.full((C.nnz,), float("nan"), dtype=tdtype, device=f"cuda:{dev}")  # (the output of either dtype)
+        sync()
+        p0, c0, _ = C.to_host()
+        for av, bv in vals:
+            plan.run(av, bv, out=res32)
+            sync()
+            assert torch.equal(res32, semiring_reference(args.semiring, A, p0, c0, av, bv)), "not the sequential reduce"
+        out["checked"] = "equal to a sequential reduce of the products in the plan's dtype (2 value sets)"
+    elif not args.full_only and f32:
         plan = mhspgemm.ValuesPlan(tool, A, A, C, dtype="float32")
         info = plan.info()
         out["classes"] = {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}
