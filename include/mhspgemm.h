@@ -431,13 +431,59 @@ int mhs_spgemm_values_grad_batched_f32(mhs_ctx *ctx, mhs_values_plan *plan, int 
  *   FP32: a subnormal product or result may be flushed to zero, as on FP32 plus-times plans.
  * The four backward entry points (mhs_spgemm_values_grad, _f32, _grad_batched, _grad_batched_f32) on a plan whose
  * semiring is not MHS_SR_PLUS_TIMES return MHS_ERR_INVALID before any HIP call, with a message naming the semiring,
- * and write nothing: min and max have subgradients only, which are not built.
+ * and write nothing: min and max have subgradients only, which mhs_spgemm_values_subgrad computes (next section).
  * Cost on MI355X: DESIGN section 16.  Additions to ABI version 10, like the entries above. */
 typedef enum mhs_semiring { MHS_SR_PLUS_TIMES = 0, MHS_SR_MIN_PLUS = 1, MHS_SR_MAX_PLUS = 2, MHS_SR_MAX_MIN = 3 } mhs_semiring;
 int mhs_values_plan_create_semiring(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
                                     int masked, int form, int dtype, int semiring, mhs_values_plan **plan);
 /* The plan's semiring (mhs_semiring). */
 int mhs_values_plan_semiring(const mhs_values_plan *plan, int *semiring);
+
+/* ---- semiring subgradients: the backward of min-plus, max-plus and max-min plans -------------
+ * For the same callers when the tropical product sits inside a differentiable program: differentiable dynamic
+ * programming, learned edge weights under a shortest-path loss, structured prediction with a hard max.  min and max
+ * have subgradients only; this is the one the library computes.  On a plan of semiring MHS_SR_MIN_PLUS, _MAX_PLUS or
+ * _MAX_MIN, Cval is the forward result for (Aval, Bval) and G = dCval.  A kept product (p, q, s) has A entry p, B
+ * entry q and C slot s.
+ *   Winner.  A product is a winner of s when mul(Aval[p], Bval[q]) == Cval[s], compared as values in the plan's
+ *   type, and Cval[s] is not the identity of add.  So an entry that equals the identity has no winners and passes
+ *   nothing: an entry no product reaches, and also "no path" (every product +Inf under min-plus).  A NaN never
+ *   compares equal: a NaN product is never a winner and a NaN Cval[s] has no winners.  The forward is bit-identical
+ *   to a sequential evaluation and the backward forms mul with the same one rounding, so every reached entry that is
+ *   neither NaN nor the identity has at least one winner.  (+0 and -0 compare equal.)
+ *   Ties.  ties[s] is the number of winners of s, an exact integer.
+ *   Weight.  Each winner of s carries w = G[s] / ties[s], divided once in the plan's type: the even split of
+ *   torch.amin / torch.amax, which keeps the gradient mass of an entry equal to G[s].  G[s] is not read where
+ *   ties[s] == 0.
+ *   Gradient of mul.  Both _PLUS semirings: w goes to dAval[p] and to dBval[q].  MHS_SR_MAX_MIN (mul = min(a, b)):
+ *   w goes to dAval[p] if a < b, to dBval[q] if b < a, and w / 2 to each if a == b (torch.minimum's rule).
+ *   Duplicates and masks.  Every duplicate entry of A or B is a product of its own, as in the forward; a product
+ *   outside a mask is no product.
+ *   Outputs.  Every entry of a requested output is written; entries no winner reaches are exactly 0.
+ *   Summation order.  dAval is summed without atomics in a fixed order: two calls give the same bits.  dBval is
+ *   summed by atomics in any order.  For an output entry summed from m winning terms, with S the sum of their absolute
+ *   values, the result is within (m + 1) u S of the exact sum of the exact weights, u = 2^-53 (FP64) or 2^-24 (FP32);
+ *   the + 1 is the division's rounding.
+ *   FP32.  An entry whose forward product or result was subnormal is exempt (the flush the forward documents).
+ * ties holds nnz(C) device ints: the scratch of the tie count and an output of its own -- the number of optimal
+ * intermediate vertices per entry.  Either of dAval and dBval may be NULL, not both.  Aval, Bval, Cval, dCval and ties
+ * are always needed: the winner test reads both operands.  Outputs must not overlap inputs or each other.
+ * The call queues, on the context's stream, one pre-step -- the zero fills of ties and of the requested outputs -- and
+ * two passes of the plan's backward launch list (classes, LDS regions and grids are the plus-times backward's): pass 1
+ * counts the winners into ties, pass 2 hands each winner's weight on.  ms and MHS_OPT_SYNC as in
+ * mhs_spgemm_values_grad; with ms == NULL and MHS_OPT_SYNC 0 the call allocates nothing, reads nothing back and does
+ * not synchronise.  Masked plans of all three forms are served.
+ * Refused with MHS_ERR_INVALID and a message before any HIP call, writing nothing: a NULL ctx or plan, a needed array
+ * NULL, both outputs NULL, a call of the wrong type, a plan of another device, and a MHS_SR_PLUS_TIMES plan -- the
+ * message names the semiring and points at mhs_spgemm_values_grad.  The four backward entry points above keep
+ * refusing semiring plans.  There is no batched form: semiring plans have width 1.
+ * Cost on MI355X: DESIGN section 17.  Additions to ABI version 10, like the entries above. */
+int mhs_spgemm_values_subgrad(mhs_ctx *ctx, mhs_values_plan *plan, const double *Aval, const double *Bval,
+                              const double *Cval, const double *dCval, int32_t *ties,
+                              double *dAval, double *dBval, double *ms);
+int mhs_spgemm_values_subgrad_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float *Aval, const float *Bval,
+                                  const float *Cval, const float *dCval, int32_t *ties,
+                                  float *dAval, float *dBval, double *ms);
 
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).

@@ -16,7 +16,12 @@
 // evaluation (the sign of a zero apart).  A NaN product is not ordered: reg() keeps the other side where it can, as
 // the hardware atomics (minNum / maxNum) do, so such an entry is NaN or the reduce of its other products.  The mul of
 // SR_MAX_MIN hands a NaN operand on, so that a NaN operand makes a NaN product under every semiring.
-// No pointer and no HIP type in here: tests/semiring_check.cpp runs it on the host.
+// The three new semirings also carry the value-level rule of their subgradient (mhs_spgemm_values_subgrad; the rule is
+// in include/mhspgemm.h): wins(a, b, c) -- whether the product of a and b is a winner of an entry whose forward result
+// is c: mul(a, b) == c as values (so +0 == -0, and a NaN on either side is no winner) and c is not the identity of add
+// -- and share_a(a, b, w) / share_b(a, b, w), what of a winner's weight w goes to the A entry and to the B entry: all
+// of it to both under the _PLUS semirings, under max-min to the smaller operand, half to each where they are equal.
+// No pointer and no HIP type in here: tests/semiring_check.cpp and tests/subgrad_check.cpp run it on the host.
 #pragma once
 #include <limits>
 
@@ -52,6 +57,9 @@ struct SrValue<SR_MIN_PLUS> {
     template <class V> static constexpr V identity() { return std::numeric_limits<V>::infinity(); }
     template <class V> static constexpr V mul(V a, V b) { return a + b; }
     template <class V> static constexpr V reg(V x, V v) { return sr_min(x, v); }
+    template <class V> static constexpr bool wins(V a, V b, V c) { return mul(a, b) == c && c != identity<V>(); }
+    template <class V> static constexpr V share_a(V, V, V w) { return w; }
+    template <class V> static constexpr V share_b(V, V, V w) { return w; }
 };
 template <>
 struct SrValue<SR_MAX_PLUS> {
@@ -59,6 +67,9 @@ struct SrValue<SR_MAX_PLUS> {
     template <class V> static constexpr V identity() { return -std::numeric_limits<V>::infinity(); }
     template <class V> static constexpr V mul(V a, V b) { return a + b; }
     template <class V> static constexpr V reg(V x, V v) { return sr_max(x, v); }
+    template <class V> static constexpr bool wins(V a, V b, V c) { return mul(a, b) == c && c != identity<V>(); }
+    template <class V> static constexpr V share_a(V, V, V w) { return w; }
+    template <class V> static constexpr V share_b(V, V, V w) { return w; }
 };
 template <>
 struct SrValue<SR_MAX_MIN> {
@@ -67,6 +78,9 @@ struct SrValue<SR_MAX_MIN> {
     // min(a, b) that hands a NaN of either side on
     template <class V> static constexpr V mul(V a, V b) { return (a < b || a != a) ? a : b; }
     template <class V> static constexpr V reg(V x, V v) { return sr_max(x, v); }
+    template <class V> static constexpr bool wins(V a, V b, V c) { return mul(a, b) == c && c != identity<V>(); }
+    template <class V> static constexpr V share_a(V a, V b, V w) { return a < b ? w : a == b ? w / V(2) : V(0); }
+    template <class V> static constexpr V share_b(V a, V b, V w) { return b < a ? w : a == b ? w / V(2) : V(0); }
 };
 
 }  // namespace mhs

@@ -545,6 +545,7 @@ hipError_t init_values_attributes() {
     hipError_t e = val_register_widths<double>();
     if (e == hipSuccess) e = val_register_widths<float>();
     if (e == hipSuccess) e = init_values_grad_attributes();  // their backward (mhs_values_grad.hip)
+    if (e == hipSuccess) e = init_values_subgrad_attributes();  // the semiring plans' subgradient (mhs_values_subgrad.hip)
     return e;
 }
 

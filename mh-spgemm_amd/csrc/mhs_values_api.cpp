@@ -15,8 +15,9 @@
 // batched backward (mhs_spgemm_values_grad_batched) makes the same passes over the backward's launch list.
 // A plan has a semiring too (mhs_values_plan_create_semiring; mhs_semiring.hpp), fixed likewise: classes and launch
 // plans do not depend on it, the forward's issue passes it on to the kernels' policy, and the backward entry points
-// refuse a plan of another semiring than plus-times (check_grad_semiring).
-// Kernels and launchers: mhs_values.hip, mhs_values_grad.hip (declared in mhs_valwalk.hpp); classes,
+// refuse a plan of another semiring than plus-times (check_grad_semiring).  Such a plan's backward is its subgradient
+// (spgemm_values_subgrad): two passes of the backward's launch list, which in turn refuses a plus-times plan.
+// Kernels and launchers: mhs_values.hip, mhs_values_grad.hip, mhs_values_subgrad.hip (declared in mhs_valwalk.hpp); classes,
 // launch plans, counter block and status words: mhs_valplan.hpp.
 #include "mhs_ctx.hpp"
 #include "mhs_valwalk.hpp"
@@ -345,7 +346,7 @@ int check_grad_width(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
                     "): a width-1 plan has to be used");
 }
 
-// Whether a backward entry point may run on the plan: min and max have subgradients only, which are not built
+// Whether a backward entry point may run on the plan: min and max have subgradients only (spgemm_values_subgrad)
 int check_grad_semiring(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
     if (p->semiring == SR_PLUS_TIMES) return MHS_OK;
     return fail(ctx, MHS_ERR_INVALID,
@@ -378,6 +379,43 @@ int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V*
             return (int)MHS_OK;
         },
         [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_grad(l, 1, a, list, s); });
+}
+
+// mhs_spgemm_values_subgrad and mhs_spgemm_values_subgrad_f32: the subgradient of a min-plus, max-plus or max-min
+// plan (the rule: include/mhspgemm.h).  One pre-step -- the zero fills of ties and of the requested outputs -- then
+// the backward's launch list twice: pass 1 counts the winners of every C entry into ties, pass 2 hands each winner's
+// G / ties to dA and dB.  A pass's launches all precede the next pass's on the stream, so pass 2 reads final counts.
+template <class V>
+int spgemm_values_subgrad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V* Bval, const V* Cval, const V* dCval, int* ties,
+                          V* dAval, V* dBval, double* ms, const char* call) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
+    if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (p->semiring == SR_PLUS_TIMES)
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string(call) + ": the plan's semiring is " + val_semiring_name(p->semiring) +
+                        ", which has a gradient: mhs_spgemm_values_grad (the subgradient serves min_plus, max_plus and max_min)");
+    if (!Aval || !Bval || !Cval || !dCval || !ties)
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string(call) + ": null Aval, Bval, Cval, dCval or ties (the winner test reads both operands)");
+    if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": no output (dAval and dBval are both null)");
+    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
+    const ValSubArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, Cval},
+                          dCval, ties, dAval, dBval};
+    return run_values(
+        ctx, p, p->gplan, ms,
+        [&](hipStream_t s) {
+            // ties and dB are summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
+            if (p->nnzC > 0) MHS_HIP(hipMemsetAsync(ties, 0, sizeof(int) * (size_t)p->nnzC, s));
+            if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(V) * (size_t)p->nnzA, s));
+            if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(V) * (size_t)p->nnzB, s));
+            for (int i = 0; i < p->gplan.n; ++i) {  // pass 1, whole, before run_values issues pass 2
+                const ValLaunch& l = p->gplan.launch[i];
+                issue_values_subgrad(l, p->semiring, 1, a, p->lists + p->list_off[l.cls], s);
+            }
+            return (int)MHS_OK;
+        },
+        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_subgrad(l, p->semiring, 2, a, list, s); });
 }
 
 // Zero fill of nb segments of n values, `stride` elements apart, as one call: a plain fill where the segments
@@ -535,6 +573,16 @@ int mhs_spgemm_values_grad_batched_f32(mhs_ctx* ctx, mhs_values_plan* p, int nb,
                                        int64_t strideDA, float* dBval, int64_t strideDB, double* ms) {
     return spgemm_values_grad_batched<float>(ctx, p, nb, Aval, strideA, Bval, strideB, dCval, strideG, dAval, strideDA, dBval,
                                              strideDB, ms, "mhs_spgemm_values_grad_batched_f32");
+}
+
+int mhs_spgemm_values_subgrad(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* Cval,
+                              const double* dCval, int32_t* ties, double* dAval, double* dBval, double* ms) {
+    return spgemm_values_subgrad<double>(ctx, p, Aval, Bval, Cval, dCval, ties, dAval, dBval, ms, "mhs_spgemm_values_subgrad");
+}
+
+int mhs_spgemm_values_subgrad_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, const float* Cval,
+                                  const float* dCval, int32_t* ties, float* dAval, float* dBval, double* ms) {
+    return spgemm_values_subgrad<float>(ctx, p, Aval, Bval, Cval, dCval, ties, dAval, dBval, ms, "mhs_spgemm_values_subgrad_f32");
 }
 
 int mhs_values_plan_info(const mhs_values_plan* p, mhs_values_info* info) {

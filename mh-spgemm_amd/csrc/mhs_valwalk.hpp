@@ -1,5 +1,5 @@
-// mhs_valwalk.hpp -- what the values kernels (mhs_values.hip), their backward (mhs_values_grad.hip)
-// and their host side (mhs_values_api.cpp) share.  First the declarations: the argument structs and
+// mhs_valwalk.hpp -- what the values kernels (mhs_values.hip), their backward (mhs_values_grad.hip), the
+// semiring plans' subgradient (mhs_values_subgrad.hip) and their host side (mhs_values_api.cpp) share.  First the declarations: the argument structs and
 // the launchers.  Then the device helpers of the forward and the backward walk: the wave-level LDS
 // ordering point, the slot search, the XCD stretch of a block's list, the row frame (a class row's C
 // segment, guarded against the launch's LDS region), the stage of A entries that the wave and block
@@ -91,6 +91,24 @@ void issue_values(const ValLaunch& l, int width, int semiring, const ValArgs<V>&
 template <class V>
 void issue_values_grad(const ValLaunch& l, int width, const ValGradArgs<V>& a, const int* list, hipStream_t s);
 hipError_t init_values_grad_attributes();  // (called by init_values_attributes)
+// The subgradient's (mhs_spgemm_values_subgrad, a plan of min-plus, max-plus or max-min; mhs_values_subgrad.hip).
+// C.val is Cval, the forward's result for (A.val, B.val); G the cotangent on C's pattern; ties: nnz(C) ints, the
+// winners per C entry -- zero-filled by the caller, counted by pass 1, read by pass 2.  dA / dB: the gradients,
+// zero-filled by the caller, either nullptr (that side is not computed); the winner test reads both operands always.
+template <class V>
+struct ValSubArgs {
+    using Value = V;
+    ValCsr<const V> A, B, C;
+    const V* G;
+    int* ties;
+    V *dA, *dB;
+};
+// One launch of a semiring plan's subgradient over its class's row list, on `s`: a launch of the plan's backward
+// list (plan_grad) at width 1, run by its class's subgradient kernel for `semiring` (not SR_PLUS_TIMES: nothing is
+// launched) and `pass` -- 1: every winner adds 1 to its entry of ties; 2: every winner carries G / ties to dA and dB.
+template <class V>
+void issue_values_subgrad(const ValLaunch& l, int semiring, int pass, const ValSubArgs<V>& a, const int* list, hipStream_t s);
+hipError_t init_values_subgrad_attributes();  // (called by init_values_attributes)
 
 // -------------------------------------------------------- device helpers ---
 // Ordering point for LDS traffic between lanes of one wave (a wave's LDS operations are

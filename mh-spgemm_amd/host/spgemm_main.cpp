@@ -2,7 +2,7 @@
 // on top of the C-ABI, printing the reference's stdout lines.
 //
 //   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32]
-//          [--batch NB] [--width W] [--semiring NAME] <file.mtx>
+//          [--batch NB] [--width W] [--semiring NAME] [--subgrad N] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -61,6 +61,15 @@
 //             sum): "values NAME pass" / "masked NAME pass" ("... NAME f32 pass"), or "error".
 //             Without --reuse or --masked, or with another name: the usage message.  Without the switch nothing is
 //             added to the output.
+//   --subgrad N  a modifier of --semiring NAME (NAME not plus_times) with --reuse or --masked: after each semiring
+//             values line (and its check), N subgradient calls (mhs_spgemm_values_subgrad / _f32, both gradients) on a
+//             plan of that semiring, on seeded values -- quarters in [-2, 2), so that products tie -- and seeded
+//             cotangents: one more line per mode and type with the median time, and with --check the call against a
+//             sequential host loop of the rule (include/mhspgemm.h): the forward for equality, ties exactly, each
+//             gradient entry within 1.01 (m + 1) u S of the long-double sum of its m winning weights: "values NAME
+//             subgrad pass" / "masked NAME subgrad pass" ("... NAME f32 subgrad pass"), or "error".  Without --semiring,
+//             with plus_times, without --reuse or --masked, or N < 1: the usage message.  Without the switch nothing
+//             is added to the output.
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -393,6 +402,102 @@ static void run_semiring(Tool& tools, const CSR& A, const CSR& B, const CSR& P, 
     }
 }
 
+// ---- --subgrad N: the subgradient of a semiring values mode (mhs_spgemm_values_subgrad / _f32), in T
+static int subgrad_call(mhs_shim::ValuesPlan& p, const double* a, const double* b, const double* c, const double* g, int32_t* t,
+                        double* da, double* db) {
+    return mhs_spgemm_values_subgrad(p.ctx, p.plan, a, b, c, g, t, da, db, &p.last_ms);
+}
+static int subgrad_call(mhs_shim::ValuesPlan& p, const float* a, const float* b, const float* c, const float* g, int32_t* t,
+                        float* da, float* db) {
+    return mhs_spgemm_values_subgrad_f32(p.ctx, p.plan, a, b, c, g, t, da, db, &p.last_ms);
+}
+// One plan of semiring sr (not plus_times) for A * B on P's pattern (masked: a mask): seeded values -- quarters in
+// [-2, 2), so that products tie -- and seeded cotangents in [0.1, 1), one values call for Cval and `calls` subgradient
+// calls (both gradients).  check: a sequential host loop of the rule over the products in T -- the forward for
+// equality, ties exactly, and each gradient entry within 1.01 (m + 1) u S of the long-double sum of its m winning
+// weights, S the sum of their absolute values; exactly 0 where m = 0.
+template <class T>
+static void run_subgrad(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool masked, int sr, int calls, bool check,
+                        const char* label, const char* tag) {
+    const bool f32 = sizeof(T) == sizeof(float);
+    const char* name = SEMIRING_NAMES[sr];
+    try {
+        const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)P.nnz;
+        unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
+        auto next = [&]() {
+            state = state * 6364136223846793005ULL + 1442695040888963407ULL;
+            return state >> 11;
+        };
+        std::vector<T> av(nA), bv(nB), gv(nC);
+        for (T& x : av) x = (T)(((int)(next() % 16) - 8) * 0.25);
+        for (T& x : bv) x = (T)(((int)(next() % 16) - 8) * 0.25);
+        for (T& x : gv) x = (T)(0.1 + 0.9 * (double)next() / 9007199254740992.0);
+        mhs_shim::ValuesPlan plan(tools, A, B, P, masked, MHS_MASK_AUTO, f32 ? MHS_F32 : MHS_F64, 1, sr);
+        DevArr<T> da(nA), db(nB), dc(nC), dg(nC), dda(nA), ddb(nB);
+        DevArr<int32_t> dt(nC);
+        da.put(av), db.put(bv), dg.put(gv);
+        f32_ok(plan.ctx, semiring_call(plan, da.p, db.p, dc.p));
+        std::vector<double> t;
+        for (int i = 0; i < calls; ++i) {
+            f32_ok(plan.ctx, subgrad_call(plan, da.p, db.p, dc.p, dg.p, dt.p, dda.p, ddb.p));
+            t.push_back(plan.last_ms);
+        }
+        std::printf("MH-SpGEMM %s %s subgradient %s (both gradients) median of %d calls is %.3lf ms\n", label, name,
+                    f32 ? "FP32" : "FP64", calls, median(t));
+        if (check) {
+            std::vector<double> mag;
+            const std::vector<T> c = semiring_host<T>(sr, A, B, P, av, bv, mag), gotC = dc.get(), gotA = dda.get(), gotB = ddb.get();
+            const std::vector<int32_t> gotT = dt.get();
+            const T inf = std::numeric_limits<T>::infinity(), identity = sr == MHS_SR_MIN_PLUS ? inf : -inf;
+            // every kept product in the host's order: fn(A entry, B entry, C position, whether it wins)
+            auto walk = [&](auto fn) {
+                for (int i = 0; i < A.M; ++i) {
+                    const int *row = P.col + P.ptr[i], *end = P.col + P.ptr[i + 1];
+                    for (int k = A.ptr[i]; k < A.ptr[i + 1]; ++k)
+                        for (int j = B.ptr[A.col[k]]; j < B.ptr[A.col[k] + 1]; ++j) {
+                            const int* hit = std::lower_bound(row, end, B.col[j]);
+                            if (hit == end || *hit != B.col[j]) continue;  // (outside a mask)
+                            const size_t s = (size_t)(hit - P.col);
+                            const T a = av[(size_t)k], b = bv[(size_t)j], prod = sr == MHS_SR_MAX_MIN ? std::min(a, b) : a + b;
+                            fn((size_t)k, (size_t)j, s, prod == c[s] && c[s] != identity);
+                        }
+                }
+            };
+            std::vector<int32_t> ties(nC, 0);
+            walk([&](size_t, size_t, size_t s, bool win) { ties[s] += win ? 1 : 0; });
+            struct Sum {
+                long double x = 0, S = 0;
+                int m = 0;
+            };
+            std::vector<Sum> wa(nA), wb(nB);
+            auto add = [](Sum& e, long double w) { e.x += w, e.S += std::fabs(w), ++e.m; };
+            walk([&](size_t k, size_t j, size_t s, bool win) {
+                if (!win) return;
+                const long double w = (long double)gv[s] / (long double)ties[s];
+                const T a = av[k], b = bv[j];
+                if (sr != MHS_SR_MAX_MIN) add(wa[k], w), add(wb[j], w);
+                else if (a < b) add(wa[k], w);
+                else if (b < a) add(wb[j], w);
+                else add(wa[k], w / 2), add(wb[j], w / 2);
+            });
+            const long double u = f32 ? 5.9604644775390625e-8L : 1.1102230246251565e-16L;
+            auto within = [&](const std::vector<T>& got, const std::vector<Sum>& want) {
+                for (size_t i = 0; i < want.size(); ++i) {
+                    const long double d = std::fabs((long double)got[i] - want[i].x);
+                    if (want[i].m == 0 ? got[i] != T(0) : !(d <= 1.01L * (want[i].m + 1) * u * want[i].S)) return false;
+                }
+                return true;
+            };
+            bool ok = gotC.size() == c.size() && gotT == ties;
+            for (size_t i = 0; ok && i < nC; ++i) ok = gotC[i] == c[i];
+            ok = ok && within(gotA, wa) && within(gotB, wb);
+            std::printf("%s %s%s subgrad %s\n", tag, name, f32 ? " f32" : "", ok ? "pass" : "error");
+        }
+    } catch (const std::exception&) {
+        std::printf("%s %s%s subgrad error\n", tag, name, f32 ? " f32" : "");
+    }
+}
+
 // --batch NB: NB seeded value sets in one batched call on a plan of `width`, beside NB unbatched calls on a
 // width-1 plan of the same type T; with check every set of the batched call against its reference (see the top).
 template <class T>
@@ -527,7 +632,7 @@ static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C
 }
 
 int main(int argc, char** argv) {
-    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0, semiring = -1;
+    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0, semiring = -1, subgrad = 0;
     bool has_semiring = false;
     bool aat = false, vendor = false, check = false, cache = false, f32 = false;
     std::string csv;
@@ -555,15 +660,17 @@ int main(int argc, char** argv) {
             has_semiring = true;
             bad = bad || semiring < 0;
         }
+        else if (!std::strcmp(argv[i], "--subgrad") && i + 1 < argc) subgrad = std::atoi(argv[++i]), bad = bad || subgrad < 1;
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
     if (has_semiring && reuse <= 0 && masked <= 0) bad = true;  // (a modifier of --reuse and --masked)
+    if (subgrad > 0 && (!has_semiring || semiring <= MHS_SR_PLUS_TIMES)) bad = true;  // (a modifier of --semiring, not plus_times)
     if ((batch > 0 && reuse <= 0) || (width > 0 && batch <= 0)) bad = true;  // (modifiers of --reuse and of --batch)
     if (width == 0) width = MHS_VAL_WIDTH_MAX;
     if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0 || grad < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--batch NB] [--width W] [--semiring NAME] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--batch NB] [--width W] [--semiring NAME] [--subgrad N] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -697,13 +804,17 @@ int main(int argc, char** argv) {
             if (reuse > 0) {
                 C.D2H();  // (the pattern's host arrays)
                 run_semiring<double>(tools, A, B, C, false, semiring, reuse, check, "values-only (pattern reused)", "values");
+                if (subgrad > 0) run_subgrad<double>(tools, A, B, C, false, semiring, subgrad, check, "values-only (pattern reused)", "values");
                 if (f32) run_semiring<float>(tools, A, B, C, false, semiring, reuse, check, "values-only (pattern reused)", "values");
+                if (f32 && subgrad > 0) run_subgrad<float>(tools, A, B, C, false, semiring, subgrad, check, "values-only (pattern reused)", "values");
             }
             if (masked > 0 && A.M == A.N) {
                 CSR mask;  // A's pattern (a plan reads no values)
                 const bool owns = mask_of(A, B.N, mask);
                 run_semiring<double>(tools, A, B, mask, true, semiring, masked, check, "masked (A's pattern)", "masked");
+                if (subgrad > 0) run_subgrad<double>(tools, A, B, mask, true, semiring, subgrad, check, "masked (A's pattern)", "masked");
                 if (f32) run_semiring<float>(tools, A, B, mask, true, semiring, masked, check, "masked (A's pattern)", "masked");
+                if (f32 && subgrad > 0) run_subgrad<float>(tools, A, B, mask, true, semiring, subgrad, check, "masked (A's pattern)", "masked");
                 unborrow_mask(mask, owns);
             }
         }

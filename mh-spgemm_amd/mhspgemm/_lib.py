@@ -217,6 +217,11 @@ def lib() -> ctypes.CDLL:
             L.mhs_values_plan_create_semiring.restype = c_int
             L.mhs_values_plan_semiring.argtypes = [c_void_p, P(c_int)]
             L.mhs_values_plan_semiring.restype = c_int
+        if hasattr(L, "mhs_spgemm_values_subgrad"):  # (semiring subgradients: a later addition to ABI 10)
+            for fn in (L.mhs_spgemm_values_subgrad, L.mhs_spgemm_values_subgrad_f32):
+                fn.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               P(ctypes.c_double)]
+                fn.restype = c_int
     if hasattr(L, "mhs_ctx_fence_default_stream"):  # (a later addition to ABI 10)
         L.mhs_ctx_fence_default_stream.argtypes = [c_void_p, c_int]
         L.mhs_ctx_fence_default_stream.restype = c_int

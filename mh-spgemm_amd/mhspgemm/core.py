@@ -426,7 +426,11 @@ class ValuesPlan:
     and its kin.  Such a plan has width 1 (``ValueError`` otherwise), classifies its rows as the plus-times plan
     does, gives entries no kept product reaches the identity (+Inf, -Inf, -Inf) and results that are bit-identical to
     a sequential evaluation; ``run`` and ``run_batched`` serve it, ``grad``, ``grad_batched``, ``apply`` and
-    ``apply_batched`` raise the library's refusal (there is no backward of min and max)."""
+    ``apply_batched`` raise the library's refusal (min and max have subgradients only).  Its backward is ``subgrad``
+    (mhs_spgemm_values_subgrad): every product that attains its C entry's value shares the entry's cotangent evenly
+    (``torch.amin`` / ``torch.amax``'s split, ``torch.minimum``'s inside max_min), with the tie counts as a third
+    result; ``apply_subgrad`` is the pair as a ``torch.autograd.Function``.  Both raise the library's refusal on a
+    plus_times plan."""
 
     _semiring = "plus_times"
 
@@ -723,6 +727,68 @@ class ValuesPlan:
         self._refuse_backward("ValuesPlan.apply_batched")
         return _values_batched_function().apply(self, Aval, Bval)
 
+    def _refuse_subgrad(self, what):
+        """The library's refusal of a subgradient call on a plus-times plan, before anything runs or is written."""
+        if not hasattr(L.lib(), "mhs_spgemm_values_subgrad"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no semiring subgradient entry points")
+        if self._semiring == "plus_times":
+            call = L.lib().mhs_spgemm_values_subgrad_f32 if self.f32 else L.lib().mhs_spgemm_values_subgrad
+            _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None, None, None, None), what)
+
+    def subgrad(self, dC, Cval, Aval, Bval, need_A: bool = True, need_B: bool = True, out_A=None, out_B=None, ties=None,
+                timed: bool = False):
+        """The backward of ``run`` on a min_plus, max_plus or max_min plan (mhs_spgemm_values_subgrad): for the
+        cotangent ``dC`` on C's pattern and ``Cval``, the forward's result for ``Aval`` and ``Bval`` (all device
+        tensors of the plan's dtype; all four are always needed), the subgradients of ``Aval`` and ``Bval`` into
+        ``out_A`` / ``out_B`` (allocated when not given) and the winners per C entry into ``ties`` (an int32 device
+        tensor of nnz(C) entries; allocated when not given).  A product is a winner of its C entry when it equals
+        ``Cval`` there and that is not the identity; each winner of an entry carries ``dC / ties``, handed to both
+        operands under the _plus semirings and to the smaller one under max_min (half each when equal).  Returns
+        ``(dA, dB, ties)`` with None for a side not asked for, whose buffer is not touched, and
+        ``(dA, dB, ties, ms)`` when ``timed``.  A plus_times plan raises the library's refusal."""
+        if not self.plan:
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "ValuesPlan.subgrad: the plan is closed")
+        if not (need_A or need_B):
+            raise ValueError("ValuesPlan.subgrad: need_A or need_B")
+        self._refuse_subgrad("ValuesPlan.subgrad")
+        torch = _torch()
+        dev = f"cuda:{self.tool.device}"
+        # (an empty array has no address; the library wants one for every array it is given: nothing reads it)
+        if self._pad is None:
+            self._pad = torch.zeros(1, dtype=self.dtype, device=dev)
+        pad = self._pad.data_ptr()
+        gp = self._ptr(dC, self.nnzC, "dC") or pad
+        cp = self._ptr(Cval, self.nnzC, "Cval") or pad
+        av = self._ptr(Aval, self.nnzA, "Aval") or pad
+        bv = self._ptr(Bval, self.nnzB, "Bval") or pad
+        if ties is None:
+            ties = torch.empty(self.nnzC, dtype=torch.int32, device=dev)
+        if not (isinstance(ties, torch.Tensor) and ties.is_cuda and ties.dtype == torch.int32 and ties.is_contiguous()
+                and ties.numel() == self.nnzC):
+            raise ValueError(f"ties: a contiguous int32 device tensor of {self.nnzC} entries")
+        pa = pb = None
+        dA = dB = None
+        if need_A:
+            dA = torch.empty(self.nnzA, dtype=self.dtype, device=dev) if out_A is None else out_A
+            pa = self._ptr(dA, self.nnzA, "out_A") or pad
+        if need_B:
+            dB = torch.empty(self.nnzB, dtype=self.dtype, device=dev) if out_B is None else out_B
+            pb = self._ptr(dB, self.nnzB, "out_B") or pad
+        ms = ctypes.c_double(0.0)
+        name = "mhs_spgemm_values_subgrad_f32" if self.f32 else "mhs_spgemm_values_subgrad"
+        rc = getattr(L.lib(), name)(self.tool.ctx, self.plan, av, bv, cp, gp, ties.data_ptr() if self.nnzC else pad, pa, pb,
+                                    ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, name)
+        return (dA, dB, ties, float(ms.value)) if timed else (dA, dB, ties)
+
+    def apply_subgrad(self, Aval, Bval):
+        """C's values on a min_plus, max_plus or max_min plan as a differentiable function of ``Aval`` and ``Bval`` (a
+        ``torch.autograd.Function``): the forward is ``run`` into a fresh nnz(C) tensor, saved with both inputs, the
+        backward ``subgrad`` for the inputs that need it (once differentiable).  Both are ordered on torch's current
+        stream as in ``apply``.  A plus_times plan raises the library's refusal (``apply`` serves it)."""
+        self._refuse_subgrad("ValuesPlan.apply_subgrad")
+        return _values_subgrad_function().apply(self, Aval, Bval)
+
     def _ordered_on_current_stream(self, call):
         """Run ``call()`` with its library work ordered after what torch's current stream holds, and before
         what it is given next."""
@@ -815,6 +881,42 @@ def _values_function():
 
     _VALUES_FUNCTION = ValuesProduct
     return ValuesProduct
+
+
+_VALUES_SUBGRAD_FUNCTION = None
+
+
+def _values_subgrad_function():
+    """The autograd function behind ``ValuesPlan.apply_subgrad`` (made on first use, as ``_values_function``)."""
+    global _VALUES_SUBGRAD_FUNCTION
+    if _VALUES_SUBGRAD_FUNCTION is not None:
+        return _VALUES_SUBGRAD_FUNCTION
+    torch = _torch()
+    from torch.autograd.function import once_differentiable
+
+    class SemiringProduct(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, Aval, Bval):
+            out = torch.empty(plan.nnzC, dtype=plan.dtype, device=f"cuda:{plan.tool.device}")
+            plan._ordered_on_current_stream(lambda: plan.run(Aval, Bval, out=out))
+            ctx.plan = plan
+            ctx.save_for_backward(Aval, Bval, out)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dC):
+            Aval, Bval, Cval = ctx.saved_tensors
+            _, need_A, need_B = ctx.needs_input_grad
+            if not (need_A or need_B):
+                return None, None, None
+            plan, dC = ctx.plan, dC.contiguous()
+            dA, dB, _ = plan._ordered_on_current_stream(
+                lambda: plan.subgrad(dC, Cval, Aval, Bval, need_A=need_A, need_B=need_B))
+            return None, dA, dB
+
+    _VALUES_SUBGRAD_FUNCTION = SemiringProduct
+    return SemiringProduct
 
 
 _VALUES_BATCHED_FUNCTION = None
