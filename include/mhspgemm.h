@@ -163,10 +163,16 @@ long long mhs_ctx_chunked_calls(const mhs_ctx *ctx);
  *                         B's arrays: nnz(B) + 3 nnz(A) >= 2^29, or every call of a context created
  *                         with the environment variable MHS_NO_O32=1 (a test switch: small operands
  *                         run the kernels of huge ones).  Once per call, also after a speculation miss.
+ *   MHS_STAT_POISON_FILLS (an addition to ABI v10) not calls but fills: the buffers a context created with
+ *                         the environment variable MHS_POISON=<byte, 0..255> has filled with that byte
+ *                         (a test switch: every device buffer the library allocates for its own work, every
+ *                         buffer its output pool hands out, and the cached workspace at the start of every
+ *                         attempt of mhs_spgemm, so that nothing a call reads without writing it first holds
+ *                         what an earlier call left).  0 without the variable.
  * Returns -1 for a null context or an unknown counter. */
 typedef enum mhs_stat { MHS_STAT_CHUNKED = 0, MHS_STAT_SPLIT = 1, MHS_STAT_SYM_FORK = 2, MHS_STAT_NFT = 3,
                         MHS_STAT_NEAR = 4, MHS_STAT_MULTI_STREAM = 5, MHS_STAT_SPEC = 6, MHS_STAT_SPEC_MISS = 7,
-                        MHS_STAT_SPEC_SKIPPED = 8, MHS_STAT_WIDE_OFFSETS = 9 } mhs_stat;
+                        MHS_STAT_SPEC_SKIPPED = 8, MHS_STAT_WIDE_OFFSETS = 9, MHS_STAT_POISON_FILLS = 10 } mhs_stat;
 long long mhs_ctx_stat(const mhs_ctx *ctx, int which);
 /* Numeric-phase durations (ms) of the last min(n, recorded) calls, oldest
  * first; waits for them.  Returns the count written, or -status on error. */

@@ -75,7 +75,7 @@ hipError_t pool_get(mhs_ctx* ctx, void** p, size_t bytes) {
     if (best != (size_t)-1) {
         *p = ctx->pool[bi].first;
         ctx->pool.erase(ctx->pool.begin() + (long)bi);
-        return hipSuccess;
+        return poison_fill(ctx, *p, best, ctx->stream);  // (MHS_POISON: not what its last owner left in it)
     }
     hipError_t e = hipMalloc(p, bytes);
     if (e == hipErrorOutOfMemory && !ctx->pool.empty()) {
@@ -84,6 +84,7 @@ hipError_t pool_get(mhs_ctx* ctx, void** p, size_t bytes) {
         (void)hipGetLastError();
         e = hipMalloc(p, bytes);
     }
+    if (e == hipSuccess) e = poison_fill(ctx, *p, bytes, ctx->stream);
     return e;
 }
 
@@ -204,6 +205,7 @@ int ensure(mhs_ctx* ctx, char** buf, size_t* have, size_t need) {
         return fail(ctx, MHS_ERR_OOM, "workspace exceeds the context's memory budget");
     MHS_HIP(hipMalloc((void**)buf, want));
     *have = want;
+    MHS_HIP(poison_fill(ctx, *buf, want, ctx->stream));
     return MHS_OK;
 }
 
@@ -689,6 +691,12 @@ int Call::plan_workspace() {
     if (rc == MHS_ERR_OOM && M > 1) return go_chunked();
     if (rc) return rc;
     if (ctx->ws != ws_before) ctx->stats_zero = false;
+    if (ctx->poison >= 0) {  // MHS_POISON: every attempt finds its cached buffers as a workspace that has just grown
+        MHS_HIP(poison_fill(ctx, ctx->ws, ctx->ws_bytes, s));
+        MHS_HIP(poison_fill(ctx, ctx->gscratch, ctx->gscratch_bytes, s));
+        MHS_HIP(poison_fill(ctx, ctx->slots, ctx->slots_bytes, s));
+        ctx->stats_zero = false;  // (the device Stats went with them: the memset below follows)
+    }
     const hipError_t e = pool_get(ctx, (void**)&own.out.ptr, (size_t)(M + 1) * 4);
     if (e == hipErrorOutOfMemory && M > 1) {
         (void)hipGetLastError();
@@ -1063,6 +1071,8 @@ int mhs_ctx_create(mhs_ctx** out, int device) {
     if (const char* e = getenv("MHS_SPEC_NSS")) ctx->spec_nss = std::max(1, std::min(atoi(e), mhs_ctx::NAUX + 1));
     if (const char* e = getenv("MHS_SPEC_NO_ROOM")) ctx->spec_no_room = atoi(e) != 0;
     if (const char* e = getenv("MHS_NO_O32")) ctx->no_o32 = atoi(e) != 0;  // tests: the 64-bit-offset numeric kernels
+    if (const char* e = getenv("MHS_POISON"))  // tests: a byte in every buffer a call did not write itself (poison_fill)
+        if (*e && atoi(e) >= 0 && atoi(e) <= 255) ctx->poison = atoi(e);
     *out = ctx;
     return MHS_OK;
 }
@@ -1179,6 +1189,10 @@ int mhs_transpose(mhs_ctx* ctx, const mhs_csr* A, mhs_csr* At) {
     if (e == hipSuccess) e = hipMalloc((void**)&T.col, sizeof(int32_t) * (size_t)(A->nnz ? A->nnz : 1));
     if (e == hipSuccess) e = hipMalloc((void**)&T.val, sizeof(double) * (size_t)(A->nnz ? A->nnz : 1));
     if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16);
+    if (e == hipSuccess) e = poison_fill(ctx, T.ptr, sizeof(int32_t) * ((size_t)A->N + 1), ctx->stream);
+    if (e == hipSuccess) e = poison_fill(ctx, T.col, sizeof(int32_t) * (size_t)(A->nnz ? A->nnz : 1), ctx->stream);
+    if (e == hipSuccess) e = poison_fill(ctx, T.val, sizeof(double) * (size_t)(A->nnz ? A->nnz : 1), ctx->stream);
+    if (e == hipSuccess) e = poison_fill(ctx, tmp, tmp_bytes ? tmp_bytes : 16, ctx->stream);
     if (e == hipSuccess) e = transpose_csr(a, T.ptr, T.col, T.val, tmp, &tmp_bytes, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (tmp) (void)hipFree(tmp);
@@ -1232,7 +1246,7 @@ int mhs_ctx_set_option(mhs_ctx* ctx, int option, int value) {
 long long mhs_ctx_chunked_calls(const mhs_ctx* ctx) { return ctx ? ctx->chunked_calls : -1; }
 
 long long mhs_ctx_stat(const mhs_ctx* ctx, int which) {
-    if (!ctx || which < 0 || which > MHS_STAT_WIDE_OFFSETS) return -1;
+    if (!ctx || which < 0 || which > MHS_STAT_POISON_FILLS) return -1;
     return which == MHS_STAT_CHUNKED ? ctx->chunked_calls : ctx->stat[which];
 }
 

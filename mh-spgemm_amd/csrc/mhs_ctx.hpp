@@ -54,7 +54,7 @@ struct mhs_ctx {
     size_t c_held = 0;       // C bytes a row-chunked call holds while it lays out its second pass
     long long front_passes = 0;  // front_pass calls (row-chunked passes; mhs_ctx_chunked_calls diagnostics)
     long long chunked_calls = 0;  // calls that ran row-chunked (mhs_ctx_chunked_calls)
-    long long stat[10] = {};       // path counters (mhs_ctx_stat; [0] unused: chunked_calls)
+    long long stat[11] = {};       // path counters (mhs_ctx_stat; [0] unused: chunked_calls)
     int dense_span_max = 0;  // NM_DENSE for rows spanning <= this many 64-column tiles (MHS_DENSE_SPAN; off: occupancy)
     // output pool (caching allocator for C arrays): (buffer, allocation size)
     std::vector<std::pair<void*, size_t>> pool;
@@ -91,6 +91,10 @@ struct mhs_ctx {
     // MHS_NO_O32=1 (tests): every numeric plan takes the 64-bit-offset kernels, which the size rule of
     // plan_numeric selects only from 2^29 entries of B on (MHS_STAT_WIDE_OFFSETS counts the calls)
     bool no_o32 = false;
+    // MHS_POISON=<byte> (tests; -1: off): poison_fill() below fills with this byte every device buffer the library
+    // allocates for its own work, every buffer the output pool hands out and, at the start of every attempt of
+    // mhs_spgemm, the cached workspace, global-bin scratch and value slots (MHS_STAT_POISON_FILLS counts the fills)
+    int poison = -1;
     // the grouped numeric bin's cursor walk (plan_numeric): the device's compute units size its
     // resident set (MHS_GROUP_WALK=0: cus stays 0, the static walk); MHS_OPT_GROUP_GRID caps its blocks
     int cus = 0;
@@ -119,5 +123,13 @@ inline int fail_hip(mhs_ctx* ctx, hipError_t e, const char* what) {
     } while (0)
 
 inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
+
+// MHS_POISON: `bytes` of the library's own buffer `p` filled with the context's poison byte on `s`, the stream
+// its next consumer runs on.  Off (the default): one branch.
+inline hipError_t poison_fill(mhs_ctx* ctx, void* p, size_t bytes, hipStream_t s) {
+    if (ctx->poison < 0 || !p || bytes == 0) return hipSuccess;
+    ++ctx->stat[MHS_STAT_POISON_FILLS];
+    return hipMemsetAsync(p, ctx->poison, bytes, s);
+}
 
 }  // namespace mhs

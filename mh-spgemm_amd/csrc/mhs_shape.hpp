@@ -235,9 +235,13 @@ constexpr int ERR_COL_RANGE = 2;
 constexpr int ERR_ACOL_RANGE = 4;
 constexpr int ERR_OVERFLOW = 8;
 
+// (x above 2^30 gives 2^30: no int power of two reaches it, and `p <<= 1` past 2^30 never would either -- k_scan
+// classifies every row, also the rows of symbolic launches a speculated call left out, whose tile and entry counts
+// are whatever their words held: the verdict on such a call is a miss, but the kernel has to end to give it)
 __host__ __device__ inline int next_pow2(int x) {
+    const int lim = x < (1 << 30) ? x : (1 << 30);
     int p = 1;
-    while (p < x) p <<= 1;
+    while (p < lim) p <<= 1;
     return p;
 }
 __host__ __device__ inline int ilog2(int x) {  // x power of two

@@ -118,6 +118,7 @@ struct PlanBuild {
         const size_t lists_bytes = al((size_t)(A->M > 0 ? A->M : 1) * 4);
         p->mem_bytes = lists_bytes + al((size_t)VAL_CNT_INTS * 4) + al((size_t)VAL_STATUS_INTS * 4);
         if (const int rc = hip(hipMalloc((void**)&p->mem, p->mem_bytes), "mhs_values_plan_create: plan memory")) return rc;
+        if (const int rc = hip(poison_fill(ctx, p->mem, p->mem_bytes, s), "plan memory (MHS_POISON)")) return rc;
         for (hipEvent_t& ev : p->ev)
             if (const int rc = hip(hipEventCreate(&ev), "mhs_values_plan_create: events")) return rc;
         p->lists = (int*)p->mem;
@@ -170,12 +171,14 @@ struct PlanBuild {
             if (const int rc = hip(hipMalloc((void**)&p->tmem, ptr_bytes + 2 * ent_bytes), "mhs_values_plan_create: B^T memory"))
                 return rc;
             p->tmem_bytes = ptr_bytes + 2 * ent_bytes;
+            if (const int rc = hip(poison_fill(ctx, p->tmem, p->tmem_bytes, s), "B^T memory (MHS_POISON)")) return rc;
             int* tptr = (int*)p->tmem;
             int* trow = (int*)(p->tmem + ptr_bytes);
             int* tperm = (int*)(p->tmem + ptr_bytes + ent_bytes);
             void* tmp = nullptr;
             hipError_t e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16);
             sort_tmp.reset(tmp);
+            if (e == hipSuccess) e = poison_fill(ctx, tmp, tmp_bytes ? tmp_bytes : 16, s);
             if (e == hipSuccess) e = transpose_pattern(b, tptr, trow, tperm, tmp, &tmp_bytes, s);
             if (const int rc = hip(e, "mhs_values_plan_create: B^T")) return rc;
             p->trans = ValTrans{tptr, trow, tperm};

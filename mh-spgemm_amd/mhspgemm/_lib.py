@@ -40,6 +40,7 @@ MHS_STAT_SPEC = 6
 MHS_STAT_SPEC_MISS = 7
 MHS_STAT_SPEC_SKIPPED = 8
 MHS_STAT_WIDE_OFFSETS = 9  # numeric kernels with 64-bit offsets (huge B, or MHS_NO_O32=1)
+MHS_STAT_POISON_FILLS = 10  # buffers filled with the poison byte (MHS_POISON=<byte>, a test switch)
 
 MHS_MASK_AUTO = 0
 MHS_MASK_PRODUCT = 1

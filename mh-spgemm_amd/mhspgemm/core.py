@@ -90,11 +90,12 @@ class Tool:
         return int(L.lib().mhs_ctx_chunked_calls(self.ctx))
 
     STATS = {"chunked": 0, "split": 1, "sym_fork": 2, "nft": 3, "near": 4, "multi_stream": 5,
-             "spec": 6, "spec_miss": 7, "spec_skipped": 8, "wide_offsets": 9}
+             "spec": 6, "spec_miss": 7, "spec_skipped": 8, "wide_offsets": 9, "poison_fills": 10}
 
     def stat(self, name: str) -> int:
         """Calls of this context that took a path (mhs_ctx_stat: 'split', 'sym_fork', 'nft',
-        'near', 'multi_stream', 'chunked', 'spec', 'spec_miss', 'spec_skipped', 'wide_offsets')."""
+        'near', 'multi_stream', 'chunked', 'spec', 'spec_miss', 'spec_skipped', 'wide_offsets'), and
+        'poison_fills': the buffers a context created under MHS_POISON=<byte> has filled with that byte."""
         return int(L.lib().mhs_ctx_stat(self.ctx, self.STATS[name]))
 
     def hbm_peak(self, nbytes: int = 2 << 30, iters: int = 10) -> dict:

@@ -206,9 +206,11 @@ def pattern_of(A, B):
     return Cp, Ci
 
 
-def plan_check(tool, A, B, Cp, Ci, what, masked=False, form="auto", seed=1):
+def plan_check(tool, A, B, Cp, Ci, what, masked=False, form="auto", seed=1, between=None):
     """A plan of A*B on the pattern (Cp, Ci) with wide values and a wide cotangent: one forward and one backward
-    call into NaN-filled buffers, all three outputs against the bound.  Returns info()."""
+    call into NaN-filled buffers, all three outputs against the bound.  Returns info().  between: called after
+    the forward (other work on the plan's context); the forward then runs again, into NaNs again, and is held
+    to the bound like the first (the header promises no order of the forward's sums, so not to its bits)."""
     A.H2D(tool.device)
     if B is not A:
         B.H2D(tool.device)
@@ -220,15 +222,26 @@ def plan_check(tool, A, B, Cp, Ci, what, masked=False, form="auto", seed=1):
         dAv, dBv = upload(tool, av), upload(tool, bv)
         oC, oA, oB = filled(tool, len(Ci)), filled(tool, A.nnz), filled(tool, B.nnz)
         plan.run(dAv, dBv, out=oC)
+        torch.cuda.synchronize()
+        gC = [oC.cpu().numpy()]
+        if between is not None:
+            between()
+            oC.fill_(float("nan"))
+            plan.run(dAv, dBv, out=oC)
+            torch.cuda.synchronize()
+            gC.append(oC.cpu().numpy())
+            assert plan.info() == info, f"{what}: the plan after other work on its context"
         plan.grad(upload(tool, G), dAv, dBv, out_A=oA, out_B=oB)
         torch.cuda.synchronize()
-        gC, gA, gB = oC.cpu().numpy(), oA.cpu().numpy(), oB.cpu().numpy()
+        gA, gB = oA.cpu().numpy(), oB.cpu().numpy()
     finally:
         plan.close()
     pqs = expand(A.ptr, A.col, B.ptr, B.col, Cp, Ci, B.N)
     assert len(pqs[0]) == info["kept_products"]
     exA, exB = exact_grad(pqs, av, bv, G, A.nnz, B.nnz)
-    assert_f64_bound(gC, *exact_forward(A, B, Cp, Ci, av, bv), f"{what}, C, wide values")
+    exC = exact_forward(A, B, Cp, Ci, av, bv)
+    for k, g in enumerate(gC):
+        assert_f64_bound(g, *exC, f"{what}, C, wide values" + ", after other work on the context" * k)
     assert_f64_bound(gA, *exA, f"{what}, dA, wide values")
     assert_f64_bound(gB, *exB, f"{what}, dB, wide values")
     return info

@@ -216,7 +216,7 @@ def test_counter_stays_zero_without_the_switch(tool):
         for it in range(2):
             judged_call(t2, "bin_zoo", "narrow", f"32-bit offsets, call {it}")
         assert t2.stat("spec") == 1 and t2.stat("wide_offsets") == 0
-        assert L.lib().mhs_ctx_stat(t2.ctx, L.MHS_STAT_WIDE_OFFSETS) == 0 and L.lib().mhs_ctx_stat(t2.ctx, 10) == -1
+        assert L.lib().mhs_ctx_stat(t2.ctx, L.MHS_STAT_WIDE_OFFSETS) == 0 and L.lib().mhs_ctx_stat(t2.ctx, 11) == -1
     finally:
         t2.close()
         A.d_release_csr()

@@ -60,8 +60,9 @@ def nan_filled(tool, n, dtype="float64"):
     return out
 
 
-def run_plan(tool, A, B, C, sr, av, bv, dtype="float64", masked=False, form="auto", calls=1):
-    """A plan of `sr` on device-resident A, B and the pattern C; `calls` calls into NaN-filled outputs.
+def run_plan(tool, A, B, C, sr, av, bv, dtype="float64", masked=False, form="auto", calls=1, between=None):
+    """A plan of `sr` on device-resident A, B and the pattern C; `calls` calls into NaN-filled outputs, with
+    between() -- other work on the plan's context -- ahead of every call after the first.
     Returns (the values of each call, info())."""
     plan = mhspgemm.ValuesPlan(tool, A, B, C, masked=masked, form=form, dtype=dtype, semiring=sr)
     try:
@@ -69,7 +70,10 @@ def run_plan(tool, A, B, C, sr, av, bv, dtype="float64", masked=False, form="aut
         info = plan.info()
         dA, dB = dev(tool, av, dtype), dev(tool, bv, dtype)
         got = []
-        for _ in range(calls):
+        for k in range(calls):
+            if k and between is not None:
+                between()
+                assert plan.info() == info, "the plan after other work on its context"
             out = nan_filled(tool, C.nnz, dtype)
             assert plan.run(dA, dB, out=out) is None
             torch.cuda.synchronize()

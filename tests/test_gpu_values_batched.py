@@ -153,23 +153,39 @@ def product_sets(name, dt):
 _INFO = {}
 
 
+def run_every_set(tool, name, dt, W, between=None):
+    """The NB1 sets of an input through a plan of (dt, W) made on `tool`, every set against its reference.  Returns
+    info().  between: called after the batched call (other work on the plan's context); the call then runs again,
+    into NaNs again, and is held to the references like the first."""
+    A, B, Cp, Ci, _ = product_input(name)
+    av, bv, refs = product_sets(name, dt)
+    plan = make_plan(tool, A, B, Cp, Ci, dt, W)
+    try:
+        info = plan.info()
+        assert info["width"] == W and plan.width == W and info["dtype"] == ("float64" if dt == "f64" else "float32")
+        out = nans(tool, (NB1, len(Ci)), dt)
+        dav, dbv = up(tool, av, dt), up(tool, bv, dt)
+        assert plan.run_batched(dav, dbv, out=out) is out
+        torch.cuda.synchronize()
+        got = [out.cpu().numpy()]
+        if between is not None:
+            between()
+            out.fill_(float("nan"))
+            assert plan.run_batched(dav, dbv, out=out) is out
+            torch.cuda.synchronize()
+            got.append(out.cpu().numpy())
+            assert plan.info() == info, "the plan after other work on its context"
+    finally:
+        plan.close()
+    for k, g in enumerate(got):
+        for b in range(NB1):
+            assert_set(g[b], refs[b], dt, f"{name} {dt} W={W} set {b}" + ", after other work on the context" * k)
+    return info
+
+
 def every_set(tool, name, dt, W):
     if (name, dt, W) not in _INFO:
-        A, B, Cp, Ci, _ = product_input(name)
-        av, bv, refs = product_sets(name, dt)
-        plan = make_plan(tool, A, B, Cp, Ci, dt, W)
-        try:
-            info = plan.info()
-            assert info["width"] == W and plan.width == W and info["dtype"] == ("float64" if dt == "f64" else "float32")
-            out = nans(tool, (NB1, len(Ci)), dt)
-            assert plan.run_batched(up(tool, av, dt), up(tool, bv, dt), out=out) is out
-            torch.cuda.synchronize()
-            got = out.cpu().numpy()
-        finally:
-            plan.close()
-        for b in range(NB1):
-            assert_set(got[b], refs[b], dt, f"{name} {dt} W={W} set {b}")
-        _INFO[name, dt, W] = info
+        _INFO[name, dt, W] = run_every_set(tool, name, dt, W)
     return _INFO[name, dt, W]
 
 

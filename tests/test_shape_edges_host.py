@@ -39,6 +39,17 @@ def test_fixture_equals_helper_under_sanitizers(tmp_path):
         "tests/golden/shape_edges.json is not what tests/shape_edges.cpp prints from the headers: regenerate it"
 
 
+def test_row_classification_ends_on_any_ints(tmp_path):
+    """tests/shape_total_check.cpp: the functions k_scan classifies a row with return on hostile tile and entry
+    counts -- what a row of a left-out symbolic launch holds (next_pow2 did not, above 2^30: the kernel hung)."""
+    exe = tmp_path / "shape_total_check"
+    cc = subprocess.run(["c++", "-std=c++17", "-O0", "-Wall", "-Werror", "-I", str(ROOT / "mh-spgemm_amd" / "csrc"),
+                         str(ROOT / "tests" / "shape_total_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=20)
+    assert run.returncode == 0 and run.stdout.startswith("2000 calls"), (run.stdout, run.stderr)
+
+
 def test_every_rung_of_the_ladder_is_there():
     names = {g: [r["name"] for r in EDGES[g]] for g in ("numeric", "dense", "symbolic", "values")}
     assert (len(names["numeric"]), len(names["dense"]), len(names["symbolic"]), len(names["values"])) == (18, 4, 7, 9)
