@@ -491,6 +491,37 @@ int mhs_spgemm_values_subgrad_f32(mhs_ctx *ctx, mhs_values_plan *plan, const flo
                                   const float *Cval, const float *dCval, int32_t *ties,
                                   float *dAval, float *dBval, double *ms);
 
+/* ---- semiring witnesses: the arg of min-plus, max-plus and max-min plans ----------------------
+ * For the same callers when the value is not enough: the predecessor on a shortest path, the Viterbi back-pointer,
+ * the parent in a BFS tree.  On a plan of semiring MHS_SR_MIN_PLUS, _MAX_PLUS or _MAX_MIN, Cval is the forward result
+ * for (Aval, Bval); a kept product (p, q, s) has A entry p, B entry q and C slot s, and its inner index k is the column
+ * of p, which is the row of q.
+ *   Winner.  The subgradient's rule (previous section), the same test in the same kernels: mul(Aval[p], Bval[q]) ==
+ *   Cval[s] as values in the plan's type, and Cval[s] is not the identity of add.  A NaN never wins; +0 and -0 are
+ *   equal.
+ *   Witness.  wit[s] is the smallest inner index k among the winners of s, and -1 where s has no winner: an entry no
+ *   product reaches, an entry equal to the identity ("no path"), a NaN Cval[s].
+ *   Duplicates and masks.  Every duplicate entry of A or B is a product of its own, but duplicates share their k: the
+ *   result does not depend on them.  A product outside a mask is no product.
+ *   Consistency.  wit[s] >= 0 exactly where the subgradient's ties[s] >= 1.
+ *   Outputs.  Every entry of wit is written.
+ *   Determinism.  A minimum of integers: the result does not depend on order, and two calls give the same ints, on
+ *   every class.
+ *   FP32.  An entry whose forward product or result was subnormal is exempt (the flush the forward documents).
+ * wit holds nnz(C) device ints and must not overlap the inputs.
+ * The call queues, on the context's stream, one pre-step -- the fill of wit with -1 -- and one pass of the plan's
+ * backward launch list, run by the subgradient's kernels as their third pass: every winner takes the minimum of its k
+ * into wit[s].  ms and MHS_OPT_SYNC as in mhs_spgemm_values_subgrad; with ms == NULL and MHS_OPT_SYNC 0 the call
+ * allocates nothing, reads nothing back and does not synchronise.  Masked plans of all three forms are served.
+ * Refused with MHS_ERR_INVALID and a message before any HIP call, writing nothing: a NULL ctx or plan, a NULL Aval,
+ * Bval, Cval or wit, a call of the wrong type, a plan of another device, and a MHS_SR_PLUS_TIMES plan -- the message
+ * names the semiring and says that a sum has no witness.  There is no batched form: semiring plans have width 1.
+ * Cost on MI355X: DESIGN section 18.  Additions to ABI version 10, like the entries above. */
+int mhs_spgemm_values_witness(mhs_ctx *ctx, mhs_values_plan *plan, const double *Aval, const double *Bval,
+                              const double *Cval, int32_t *wit, double *ms);
+int mhs_spgemm_values_witness_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float *Aval, const float *Bval,
+                                  const float *Cval, int32_t *wit, double *ms);
+
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).
  * At->M = A->N, At->N = A->M; rows of At list their columns ascending; arrays are

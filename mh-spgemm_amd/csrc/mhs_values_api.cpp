@@ -16,7 +16,9 @@
 // A plan has a semiring too (mhs_values_plan_create_semiring; mhs_semiring.hpp), fixed likewise: classes and launch
 // plans do not depend on it, the forward's issue passes it on to the kernels' policy, and the backward entry points
 // refuse a plan of another semiring than plus-times (check_grad_semiring).  Such a plan's backward is its subgradient
-// (spgemm_values_subgrad): two passes of the backward's launch list, which in turn refuses a plus-times plan.
+// (spgemm_values_subgrad): two passes of the backward's launch list, which in turn refuses a plus-times plan.  Its
+// witness (spgemm_values_witness) is a third pass of the same kernels on a call of its own: the smallest inner index
+// among the winners of every C entry.
 // Kernels and launchers: mhs_values.hip, mhs_values_grad.hip, mhs_values_subgrad.hip (declared in mhs_valwalk.hpp); classes,
 // launch plans, counter block and status words: mhs_valplan.hpp.
 #include "mhs_ctx.hpp"
@@ -404,7 +406,7 @@ int spgemm_values_subgrad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const
     if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": no output (dAval and dBval are both null)");
     if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
     const ValSubArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, Cval},
-                          dCval, ties, dAval, dBval};
+                          dCval, ties, dAval, dBval, nullptr};
     return run_values(
         ctx, p, p->gplan, ms,
         [&](hipStream_t s) {
@@ -419,6 +421,34 @@ int spgemm_values_subgrad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const
             return (int)MHS_OK;
         },
         [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_subgrad(l, p->semiring, 2, a, list, s); });
+}
+
+// mhs_spgemm_values_witness and mhs_spgemm_values_witness_f32: the arg of a min-plus, max-plus or max-min plan (the
+// rule: include/mhspgemm.h).  One pre-step -- wit filled with 0xFF bytes: -1 as an int, the largest unsigned -- then the
+// backward's launch list once, as pass 3: every winner takes the unsigned minimum of its inner index into wit.  An
+// entry no winner reaches keeps its -1: there is no post-step.
+template <class V>
+int spgemm_values_witness(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V* Bval, const V* Cval, int* wit, double* ms,
+                          const char* call) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
+    if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (p->semiring == SR_PLUS_TIMES)
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string(call) + ": the plan's semiring is " + val_semiring_name(p->semiring) +
+                        ": a sum has no witness (the witness serves min_plus, max_plus and max_min)");
+    if (!Aval || !Bval || !Cval || !wit)
+        return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null Aval, Bval, Cval or wit (the winner test reads both operands)");
+    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
+    const ValSubArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, Cval},
+                          nullptr, nullptr, nullptr, nullptr, wit};
+    return run_values(
+        ctx, p, p->gplan, ms,
+        [&](hipStream_t s) {
+            if (p->nnzC > 0) MHS_HIP(hipMemsetAsync(wit, 0xFF, sizeof(int) * (size_t)p->nnzC, s));
+            return (int)MHS_OK;
+        },
+        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_subgrad(l, p->semiring, 3, a, list, s); });
 }
 
 // Zero fill of nb segments of n values, `stride` elements apart, as one call: a plain fill where the segments
@@ -586,6 +616,16 @@ int mhs_spgemm_values_subgrad(mhs_ctx* ctx, mhs_values_plan* p, const double* Av
 int mhs_spgemm_values_subgrad_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, const float* Cval,
                                   const float* dCval, int32_t* ties, float* dAval, float* dBval, double* ms) {
     return spgemm_values_subgrad<float>(ctx, p, Aval, Bval, Cval, dCval, ties, dAval, dBval, ms, "mhs_spgemm_values_subgrad_f32");
+}
+
+int mhs_spgemm_values_witness(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* Cval,
+                              int32_t* wit, double* ms) {
+    return spgemm_values_witness<double>(ctx, p, Aval, Bval, Cval, wit, ms, "mhs_spgemm_values_witness");
+}
+
+int mhs_spgemm_values_witness_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, const float* Cval,
+                                  int32_t* wit, double* ms) {
+    return spgemm_values_witness<float>(ctx, p, Aval, Bval, Cval, wit, ms, "mhs_spgemm_values_witness_f32");
 }
 
 int mhs_values_plan_info(const mhs_values_plan* p, mhs_values_info* info) {

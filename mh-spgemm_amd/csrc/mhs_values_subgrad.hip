@@ -21,6 +21,13 @@
 // shuffles and stored once, in a fixed order, as grad_store does -- and adds its share to dB[q] by one unsafeAtomicAdd.
 // In the wave and block walks a lane tests its VAL_PIECES pieces on LDS first and then takes its winners one after another.
 // After staging LDS is read-only.  Which sides are wanted is a wave-uniform flag (the output's pointer).
+//
+// Pass 3 is the witness (mhs_spgemm_values_witness): the same walks and the same winner test once more, on their own
+// call.  wit is filled with 0xFF bytes by the caller -- -1 as an int, the largest unsigned -- and every winner takes the
+// unsigned minimum of its inner index k = A.col of its A entry into wit[position] (an integer global atomic without
+// return): the smallest k among the winners, -1 where there is none, whatever the order.  It forms no weight, reduces
+// nothing over the group and stores no gradient; the staged walk, whose stage keeps no column, reloads A.col for a
+// winner (one address over the group).
 #include "mhs_valwalk.hpp"
 
 namespace mhs {
@@ -34,11 +41,16 @@ __device__ __forceinline__ V sub_group_sum(V v) {
     return v;
 }
 
-// One winner: B entry q, C position pos, its operands; sum is the lane's share of the A entry's gradient.
+// One winner: B entry q, C position pos, its operands; sum is the lane's share of the A entry's gradient; k the inner
+// index of the product, the column of its A entry (read by pass 3 only).
 template <class S, int PASS, class V>
-__device__ __forceinline__ void sub_winner(const ValSubArgs<V>& a, bool wa, bool wb, int q, int pos, V av, V bv, V& sum) {
+__device__ __forceinline__ void sub_winner(const ValSubArgs<V>& a, bool wa, bool wb, int q, int pos, V av, V bv, V& sum, int k) {
     if constexpr (PASS == 1) {
         (void)__hip_atomic_fetch_add(a.ties + pos, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_atomic_add_u32
+    } else if constexpr (PASS == 3) {
+        // wit is -1 = 0xFFFFFFFF until a winner comes: the unsigned minimum is the smallest k (k >= 0)
+        // (a plain load of wit[pos] first, to skip the atomic where it is already <= k, was measured and lost: DESIGN 18)
+        (void)__hip_atomic_fetch_min((unsigned*)a.wit + pos, (unsigned)k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_atomic_umin
     } else {
         const V w = a.G[pos] / V(a.ties[pos]);  // (ties >= 1: pass 1 counted this winner)
         if (wa) sum += S::share_a(av, bv, w);
@@ -112,7 +124,8 @@ __device__ __forceinline__ void sub_staged(const ValSubArgs<V>& a, int a0, int a
                         for (int w = 1; w < P; ++w)
                             if (u == w) hu = h[w], cu = c[w], vu = v[w];
                         const int pos = where(hu, cu);
-                        if (pos >= 0) sub_winner<S, PASS>(a, wa, wb, bs + j + u * G, pos, av, vu, sum);
+                        // (the stage keeps no column: pass 3 reloads its A entry's, one address over the group)
+                        if (pos >= 0) sub_winner<S, PASS>(a, wa, wb, bs + j + u * G, pos, av, vu, sum, PASS == 3 ? a.A.col[k0 + e] : 0);
                     }
                 }
             }
@@ -211,7 +224,7 @@ __global__ __launch_bounds__(256) void k_sub_team(ValSubArgs<V> a, const int* __
                     const int slot = find_slot(cols, n, a.B.col[j]);
                     if (slot >= 0) {
                         const V bv = a.B.val[j];
-                        if (S::wins(av, bv, cv[slot])) sub_winner<S, PASS>(a, wa, wb, j, s + slot, av, bv, sum);
+                        if (S::wins(av, bv, cv[slot])) sub_winner<S, PASS>(a, wa, wb, j, s + slot, av, bv, sum, ac);
                     }
                 }
             }
@@ -269,7 +282,7 @@ __global__ __launch_bounds__(LANES < 256 ? 256 : LANES) void k_sub_global(ValSub
                     const int slot = find_slot(a.C.col + s, n, a.B.col[j]);
                     if (slot >= 0) {
                         const V bv = a.B.val[j];
-                        if (S::wins(av, bv, a.C.val[s + slot])) sub_winner<S, PASS>(a, wa, wb, j, s + slot, av, bv, sum);
+                        if (S::wins(av, bv, a.C.val[s + slot])) sub_winner<S, PASS>(a, wa, wb, j, s + slot, av, bv, sum, ac);
                     }
                 }
             }
@@ -301,8 +314,9 @@ static_assert(!val_team_registers(VAL_VB_F64) && !val_team_registers(VAL_VB_F32)
 
 template <class V, int SR>
 hipError_t sub_register() {
-    const hipError_t e = val_allow_max_lds<SubKernels<V, SR, 1>>();
-    return e == hipSuccess ? val_allow_max_lds<SubKernels<V, SR, 2>>() : e;
+    hipError_t e = val_allow_max_lds<SubKernels<V, SR, 1>>();
+    if (e == hipSuccess) e = val_allow_max_lds<SubKernels<V, SR, 2>>();
+    return e == hipSuccess ? val_allow_max_lds<SubKernels<V, SR, 3>>() : e;
 }
 template <class V>
 hipError_t sub_register_semirings() {
@@ -327,6 +341,7 @@ template <class V, int SR>
 void issue_sub_pass(const ValLaunch& l, int pass, const ValSubArgs<V>& a, const int* list, hipStream_t s) {
     if (pass == 1) issue_sub<V, SR, 1>(l, a, list, s);
     else if (pass == 2) issue_sub<V, SR, 2>(l, a, list, s);
+    else if (pass == 3) issue_sub<V, SR, 3>(l, a, list, s);
 }
 
 }  // namespace

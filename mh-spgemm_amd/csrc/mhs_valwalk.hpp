@@ -95,6 +95,8 @@ hipError_t init_values_grad_attributes();  // (called by init_values_attributes)
 // C.val is Cval, the forward's result for (A.val, B.val); G the cotangent on C's pattern; ties: nnz(C) ints, the
 // winners per C entry -- zero-filled by the caller, counted by pass 1, read by pass 2.  dA / dB: the gradients,
 // zero-filled by the caller, either nullptr (that side is not computed); the winner test reads both operands always.
+// wit: the witness's output (mhs_spgemm_values_witness, pass 3), nnz(C) ints filled with -1 by the caller; G, ties,
+// dA and dB are nullptr in that pass, and wit in passes 1 and 2.
 template <class V>
 struct ValSubArgs {
     using Value = V;
@@ -102,10 +104,12 @@ struct ValSubArgs {
     const V* G;
     int* ties;
     V *dA, *dB;
+    int* wit;
 };
 // One launch of a semiring plan's subgradient over its class's row list, on `s`: a launch of the plan's backward
 // list (plan_grad) at width 1, run by its class's subgradient kernel for `semiring` (not SR_PLUS_TIMES: nothing is
-// launched) and `pass` -- 1: every winner adds 1 to its entry of ties; 2: every winner carries G / ties to dA and dB.
+// launched) and `pass` -- 1: every winner adds 1 to its entry of ties; 2: every winner carries G / ties to dA and dB;
+// 3 (the witness): every winner takes the unsigned minimum of its inner index into its entry of wit.
 template <class V>
 void issue_values_subgrad(const ValLaunch& l, int semiring, int pass, const ValSubArgs<V>& a, const int* list, hipStream_t s);
 hipError_t init_values_subgrad_attributes();  // (called by init_values_attributes)

@@ -2,7 +2,7 @@
 // on top of the C-ABI, printing the reference's stdout lines.
 //
 //   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32]
-//          [--batch NB] [--width W] [--semiring NAME] [--subgrad N] <file.mtx>
+//          [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -70,6 +70,14 @@
 //             subgrad pass" / "masked NAME subgrad pass" ("... NAME f32 subgrad pass"), or "error".  Without --semiring,
 //             with plus_times, without --reuse or --masked, or N < 1: the usage message.  Without the switch nothing
 //             is added to the output.
+//   --witness N  a modifier of --semiring NAME (NAME not plus_times) with --reuse or --masked, like --subgrad N and
+//             after it: after each semiring values line, N witness calls (mhs_spgemm_values_witness / _f32) on a plan
+//             of that semiring, on --subgrad's seeded values: one more line per mode and type with the median time,
+//             and with --check the call against a sequential host loop of the rule (include/mhspgemm.h): the forward
+//             for equality and per entry the smallest inner index among the products equal to it, -1 where there is
+//             none: "values NAME witness pass" / "masked NAME witness pass" ("... NAME f32 witness pass"), or "error".
+//             Without --semiring, with plus_times, without --reuse or --masked, or N < 1: the usage message.  Without
+//             the switch nothing is added to the output.
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -498,6 +506,70 @@ static void run_subgrad(Tool& tools, const CSR& A, const CSR& B, const CSR& P, b
     }
 }
 
+// ---- --witness N: the arg of a semiring values mode (mhs_spgemm_values_witness / _f32), in T
+static int witness_call(mhs_shim::ValuesPlan& p, const double* a, const double* b, const double* c, int32_t* w) {
+    return mhs_spgemm_values_witness(p.ctx, p.plan, a, b, c, w, &p.last_ms);
+}
+static int witness_call(mhs_shim::ValuesPlan& p, const float* a, const float* b, const float* c, int32_t* w) {
+    return mhs_spgemm_values_witness_f32(p.ctx, p.plan, a, b, c, w, &p.last_ms);
+}
+// One plan of semiring sr (not plus_times) for A * B on P's pattern (masked: a mask): run_subgrad's seeded values --
+// quarters in [-2, 2), so that products tie -- one values call for Cval and `calls` witness calls.  check: a sequential
+// host loop of the rule over the products in T -- the forward for equality, and per entry the smallest inner index
+// among the products equal to it (-1: none, or the entry is the identity), for equality.
+template <class T>
+static void run_witness(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool masked, int sr, int calls, bool check,
+                        const char* label, const char* tag) {
+    const bool f32 = sizeof(T) == sizeof(float);
+    const char* name = SEMIRING_NAMES[sr];
+    try {
+        const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)P.nnz;
+        unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
+        auto next = [&]() {
+            state = state * 6364136223846793005ULL + 1442695040888963407ULL;
+            return state >> 11;
+        };
+        std::vector<T> av(nA), bv(nB);
+        for (T& x : av) x = (T)(((int)(next() % 16) - 8) * 0.25);
+        for (T& x : bv) x = (T)(((int)(next() % 16) - 8) * 0.25);
+        mhs_shim::ValuesPlan plan(tools, A, B, P, masked, MHS_MASK_AUTO, f32 ? MHS_F32 : MHS_F64, 1, sr);
+        DevArr<T> da(nA), db(nB), dc(nC);
+        DevArr<int32_t> dw(nC);
+        da.put(av), db.put(bv);
+        f32_ok(plan.ctx, semiring_call(plan, da.p, db.p, dc.p));
+        std::vector<double> t;
+        for (int i = 0; i < calls; ++i) {
+            f32_ok(plan.ctx, witness_call(plan, da.p, db.p, dc.p, dw.p));
+            t.push_back(plan.last_ms);
+        }
+        std::printf("MH-SpGEMM %s %s witness %s median of %d calls is %.3lf ms\n", label, name, f32 ? "FP32" : "FP64", calls,
+                    median(t));
+        if (check) {
+            std::vector<double> mag;
+            const std::vector<T> c = semiring_host<T>(sr, A, B, P, av, bv, mag), gotC = dc.get();
+            const std::vector<int32_t> gotW = dw.get();
+            const T inf = std::numeric_limits<T>::infinity(), identity = sr == MHS_SR_MIN_PLUS ? inf : -inf;
+            std::vector<int32_t> wit(nC, -1);
+            for (int i = 0; i < A.M; ++i) {
+                const int *row = P.col + P.ptr[i], *end = P.col + P.ptr[i + 1];
+                for (int k = A.ptr[i]; k < A.ptr[i + 1]; ++k)
+                    for (int j = B.ptr[A.col[k]]; j < B.ptr[A.col[k] + 1]; ++j) {
+                        const int* hit = std::lower_bound(row, end, B.col[j]);
+                        if (hit == end || *hit != B.col[j]) continue;  // (outside a mask)
+                        const size_t s = (size_t)(hit - P.col);
+                        const T a = av[(size_t)k], b = bv[(size_t)j], prod = sr == MHS_SR_MAX_MIN ? std::min(a, b) : a + b;
+                        if (prod == c[s] && c[s] != identity && (wit[s] < 0 || A.col[k] < wit[s])) wit[s] = A.col[k];
+                    }
+            }
+            bool ok = gotC.size() == c.size() && gotW == wit;
+            for (size_t i = 0; ok && i < nC; ++i) ok = gotC[i] == c[i];
+            std::printf("%s %s%s witness %s\n", tag, name, f32 ? " f32" : "", ok ? "pass" : "error");
+        }
+    } catch (const std::exception&) {
+        std::printf("%s %s%s witness error\n", tag, name, f32 ? " f32" : "");
+    }
+}
+
 // --batch NB: NB seeded value sets in one batched call on a plan of `width`, beside NB unbatched calls on a
 // width-1 plan of the same type T; with check every set of the batched call against its reference (see the top).
 template <class T>
@@ -632,7 +704,7 @@ static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C
 }
 
 int main(int argc, char** argv) {
-    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0, semiring = -1, subgrad = 0;
+    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0, semiring = -1, subgrad = 0, witness = 0;
     bool has_semiring = false;
     bool aat = false, vendor = false, check = false, cache = false, f32 = false;
     std::string csv;
@@ -661,16 +733,17 @@ int main(int argc, char** argv) {
             bad = bad || semiring < 0;
         }
         else if (!std::strcmp(argv[i], "--subgrad") && i + 1 < argc) subgrad = std::atoi(argv[++i]), bad = bad || subgrad < 1;
+        else if (!std::strcmp(argv[i], "--witness") && i + 1 < argc) witness = std::atoi(argv[++i]), bad = bad || witness < 1;
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
     if (has_semiring && reuse <= 0 && masked <= 0) bad = true;  // (a modifier of --reuse and --masked)
-    if (subgrad > 0 && (!has_semiring || semiring <= MHS_SR_PLUS_TIMES)) bad = true;  // (a modifier of --semiring, not plus_times)
+    if ((subgrad > 0 || witness > 0) && (!has_semiring || semiring <= MHS_SR_PLUS_TIMES)) bad = true;  // (modifiers of --semiring, not plus_times)
     if ((batch > 0 && reuse <= 0) || (width > 0 && batch <= 0)) bad = true;  // (modifiers of --reuse and of --batch)
     if (width == 0) width = MHS_VAL_WIDTH_MAX;
     if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0 || grad < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--batch NB] [--width W] [--semiring NAME] [--subgrad N] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -805,16 +878,20 @@ int main(int argc, char** argv) {
                 C.D2H();  // (the pattern's host arrays)
                 run_semiring<double>(tools, A, B, C, false, semiring, reuse, check, "values-only (pattern reused)", "values");
                 if (subgrad > 0) run_subgrad<double>(tools, A, B, C, false, semiring, subgrad, check, "values-only (pattern reused)", "values");
+                if (witness > 0) run_witness<double>(tools, A, B, C, false, semiring, witness, check, "values-only (pattern reused)", "values");
                 if (f32) run_semiring<float>(tools, A, B, C, false, semiring, reuse, check, "values-only (pattern reused)", "values");
                 if (f32 && subgrad > 0) run_subgrad<float>(tools, A, B, C, false, semiring, subgrad, check, "values-only (pattern reused)", "values");
+                if (f32 && witness > 0) run_witness<float>(tools, A, B, C, false, semiring, witness, check, "values-only (pattern reused)", "values");
             }
             if (masked > 0 && A.M == A.N) {
                 CSR mask;  // A's pattern (a plan reads no values)
                 const bool owns = mask_of(A, B.N, mask);
                 run_semiring<double>(tools, A, B, mask, true, semiring, masked, check, "masked (A's pattern)", "masked");
                 if (subgrad > 0) run_subgrad<double>(tools, A, B, mask, true, semiring, subgrad, check, "masked (A's pattern)", "masked");
+                if (witness > 0) run_witness<double>(tools, A, B, mask, true, semiring, witness, check, "masked (A's pattern)", "masked");
                 if (f32) run_semiring<float>(tools, A, B, mask, true, semiring, masked, check, "masked (A's pattern)", "masked");
                 if (f32 && subgrad > 0) run_subgrad<float>(tools, A, B, mask, true, semiring, subgrad, check, "masked (A's pattern)", "masked");
+                if (f32 && witness > 0) run_witness<float>(tools, A, B, mask, true, semiring, witness, check, "masked (A's pattern)", "masked");
                 unborrow_mask(mask, owns);
             }
         }

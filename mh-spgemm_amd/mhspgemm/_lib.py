@@ -223,6 +223,10 @@ def lib() -> ctypes.CDLL:
                 fn.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                P(ctypes.c_double)]
                 fn.restype = c_int
+        if hasattr(L, "mhs_spgemm_values_witness"):  # (semiring witnesses: a later addition to ABI 10)
+            for fn in (L.mhs_spgemm_values_witness, L.mhs_spgemm_values_witness_f32):
+                fn.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(ctypes.c_double)]
+                fn.restype = c_int
     if hasattr(L, "mhs_ctx_fence_default_stream"):  # (a later addition to ABI 10)
         L.mhs_ctx_fence_default_stream.argtypes = [c_void_p, c_int]
         L.mhs_ctx_fence_default_stream.restype = c_int

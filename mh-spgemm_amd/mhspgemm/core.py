@@ -431,7 +431,9 @@ class ValuesPlan:
     (mhs_spgemm_values_subgrad): every product that attains its C entry's value shares the entry's cotangent evenly
     (``torch.amin`` / ``torch.amax``'s split, ``torch.minimum``'s inside max_min), with the tie counts as a third
     result; ``apply_subgrad`` is the pair as a ``torch.autograd.Function``.  Both raise the library's refusal on a
-    plus_times plan."""
+    plus_times plan.  Its arg is ``witness`` (mhs_spgemm_values_witness): the smallest inner index ``k`` among the
+    products that attain each C entry, -1 where there is none; ``run_arg`` is the forward and the witness together.
+    They raise the library's refusal on a plus_times plan too (a sum has no witness)."""
 
     _semiring = "plus_times"
 
@@ -789,6 +791,60 @@ class ValuesPlan:
         stream as in ``apply``.  A plus_times plan raises the library's refusal (``apply`` serves it)."""
         self._refuse_subgrad("ValuesPlan.apply_subgrad")
         return _values_subgrad_function().apply(self, Aval, Bval)
+
+    def _refuse_witness(self, what):
+        """The library's refusal of a witness call on a plus-times plan, before anything runs or is written."""
+        if not hasattr(L.lib(), "mhs_spgemm_values_witness"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no semiring witness entry points")
+        if self._semiring == "plus_times":
+            call = L.lib().mhs_spgemm_values_witness_f32 if self.f32 else L.lib().mhs_spgemm_values_witness
+            _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None), what)
+
+    def witness(self, Cval, Aval, Bval, out=None, timed: bool = False):
+        """The arg of ``run`` on a min_plus, max_plus or max_min plan (mhs_spgemm_values_witness): for ``Cval``, the
+        forward's result for ``Aval`` and ``Bval`` (device tensors of the plan's dtype; all three are always needed),
+        the inner index ``k`` through which each C entry got its value -- the predecessor on the shortest path, the
+        Viterbi back-pointer -- into ``out`` (an int32 device tensor of nnz(C) entries; allocated when not given).  A
+        product is a winner of its C entry by ``subgrad``'s rule; an entry's witness is the smallest ``k`` (A's
+        column, B's row) among its winners, and -1 where it has none: no product reaches it, it is the identity ("no
+        path"), or it is NaN.  Returns ``wit``, and ``(wit, ms)`` when ``timed``.  A plus_times plan raises the
+        library's refusal."""
+        if not self.plan:
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "ValuesPlan.witness: the plan is closed")
+        self._refuse_witness("ValuesPlan.witness")
+        torch = _torch()
+        dev = f"cuda:{self.tool.device}"
+        # (an empty array has no address; the library wants one for every array it is given: nothing reads it)
+        if self._pad is None:
+            self._pad = torch.zeros(1, dtype=self.dtype, device=dev)
+        pad = self._pad.data_ptr()
+        cp = self._ptr(Cval, self.nnzC, "Cval") or pad
+        av = self._ptr(Aval, self.nnzA, "Aval") or pad
+        bv = self._ptr(Bval, self.nnzB, "Bval") or pad
+        wit = torch.empty(self.nnzC, dtype=torch.int32, device=dev) if out is None else out
+        if not (isinstance(wit, torch.Tensor) and wit.is_cuda and wit.dtype == torch.int32 and wit.is_contiguous()
+                and wit.numel() == self.nnzC):
+            raise ValueError(f"out: a contiguous int32 device tensor of {self.nnzC} entries")
+        ms = ctypes.c_double(0.0)
+        name = "mhs_spgemm_values_witness_f32" if self.f32 else "mhs_spgemm_values_witness"
+        rc = getattr(L.lib(), name)(self.tool.ctx, self.plan, av, bv, cp, wit.data_ptr() if self.nnzC else pad,
+                                    ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, name)
+        return (wit, float(ms.value)) if timed else wit
+
+    def run_arg(self, Aval, Bval):
+        """C's values on a min_plus, max_plus or max_min plan together with their witnesses: ``(Cval, wit)``, the
+        forward ``run`` into a fresh nnz(C) tensor and then ``witness`` on it.  Both are ordered on torch's current
+        stream as in ``apply``.  A plus_times plan raises the library's refusal."""
+        self._refuse_witness("ValuesPlan.run_arg")
+        torch = _torch()
+        out = torch.empty(self.nnzC, dtype=self.dtype, device=f"cuda:{self.tool.device}")
+
+        def both():
+            self.run(Aval, Bval, out=out)
+            return out, self.witness(out, Aval, Bval)
+
+        return self._ordered_on_current_stream(both)
 
     def _ordered_on_current_stream(self, call):
         """Run ``call()`` with its library work ordered after what torch's current stream holds, and before
