@@ -786,6 +786,26 @@ __device__ __forceinline__ void acc_add(double* p, double v) {
 }
 
 // --------------------------------------------------- Form_mask_matrix_B ---
+// Lane gl -/+ d's value within a lane group of G lanes.  Groups of at most 16 lanes lie inside one
+// 16-lane DPP row, so the shift is a DPP row shift (a VALU move, no LDS access); a lane whose source
+// lies outside its group gets a value it must not use (every caller guards on gl), and the lanes of
+// a group are active together, whatever the other groups of the wave do.  Wider groups: ds_bpermute.
+template <int G>
+__device__ __forceinline__ int group_up(int v, int d) {
+    if constexpr (G <= 16) return row_shr(v, d);
+    else return __shfl_up(v, d, G);
+}
+template <int G>
+__device__ __forceinline__ unsigned long long group_up(unsigned long long v, int d) {
+    if constexpr (G <= 16)
+        return ((unsigned long long)(unsigned)row_shr((int)(v >> 32), d) << 32) | (unsigned)row_shr((int)v, d);
+    else return __shfl_up(v, d, G);
+}
+template <int G>
+__device__ __forceinline__ int group_down1(int v) {
+    if constexpr (G <= 16) return __builtin_amdgcn_update_dpp(0, v, 0x101, 0xF, 0xF, true);  // row_shl:1
+    else return __shfl_down(v, 1, G);
+}
 // G lanes per B row.  Per chunk of G entries: head = first entry of a tile run,
 // a forward segmented OR scan collects each run's bits, the run's last lane
 // (tail) writes (tile, mask) at row_start + run index.  A run that crosses a
@@ -832,7 +852,7 @@ __device__ __forceinline__ void mask_row(int row, bool valid, int N, const int* 
             const int c = cc[u];
             if (same_len && in && pp[u] != c) differ = true;
             const int first_next = __shfl(cc[u + 1], gbase);
-            const int up = __shfl_up(c, 1, G);
+            const int up = group_up<G>(c, 1);
             const int pc = (gl == 0) ? prev_col : up;
             const int tile = c >> TILE_SHIFT;
             const int ptile = pc < 0 ? -1 : (pc >> TILE_SHIFT);
@@ -841,7 +861,7 @@ __device__ __forceinline__ void mask_row(int row, bool valid, int N, const int* 
             if (in && (c < 0 || c >= N)) err |= ERR_COL_RANGE;
             // next entry's column: within the chunk from the neighbour lane, at the
             // chunk edge from the next chunk's first
-            const int dn = __shfl_down(c, 1, G);
+            const int dn = group_down1<G>(c);
             int nc = (gl == G - 1) ? first_next : dn;
             if (j + 1 >= e) nc = INT_MAX;
             const bool tail = in && ((nc >> TILE_SHIFT) != tile || nc == INT_MAX);
@@ -850,8 +870,8 @@ __device__ __forceinline__ void mask_row(int row, bool valid, int N, const int* 
             if (gl == 0 && !head) m |= carry;
 #pragma unroll
             for (int d = 1; d < G; d <<= 1) {
-                const unsigned long long om = __shfl_up(m, d, G);
-                const int ot = __shfl_up(tile, d, G);
+                const unsigned long long om = group_up<G>(m, d);
+                const int ot = group_up<G>(tile, d);
                 if (gl >= d && ot == tile) m |= om;
             }
             const unsigned long long hb = __ballot(head) & gmask;
