@@ -270,15 +270,21 @@ public:
     // for MH_spgemm_values_batched.  Width 1 is the typed constructor's plan.
     // semiring: an mhs_semiring (mhs_values_plan_create_semiring).  A plan of another one than MHS_SR_PLUS_TIMES has
     // width 1; MH_spgemm_values and MH_spgemm_values_batched run it, the backward calls throw the library's refusal.
+    // accum: an mhs_accum (mhs_values_plan_create_accum).  MHS_ACC_F64 with MHS_F32 is a mixed plan -- float values,
+    // double sums, the float overloads run it -- and is plus-times only; with MHS_F64 it is the plain FP64 plan.
     ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C, bool masked, int form, mhs_dtype dtype, int width,
-               int semiring = MHS_SR_PLUS_TIMES)
+               int semiring = MHS_SR_PLUS_TIMES, int accum = MHS_ACC_NATIVE)
         : ctx(tools.ctx) {
         mhs_csr a{A.M, A.N, A.nnz, A.d_ptr, A.d_col, A.d_val};
         mhs_csr b{B.M, B.N, B.nnz, B.d_ptr, B.d_col, B.d_val};
         mhs_csr c{C.M, C.N, C.nnz, C.d_ptr, C.d_col, C.d_val};
         if (semiring != MHS_SR_PLUS_TIMES && width != 1) throw std::runtime_error("ValuesPlan: a semiring plan has width 1");
+        if (semiring != MHS_SR_PLUS_TIMES && accum != MHS_ACC_NATIVE)
+            throw std::runtime_error("ValuesPlan: a semiring plan has no sum type (accum must be MHS_ACC_NATIVE)");
         const int rc = semiring != MHS_SR_PLUS_TIMES
                            ? mhs_values_plan_create_semiring(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, semiring, &plan)
+                       : accum != MHS_ACC_NATIVE
+                           ? mhs_values_plan_create_accum(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, width, accum, &plan)
                            : mhs_values_plan_create_batched(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, width, &plan);
         if (rc != MHS_OK) {
             std::printf("%s\n", mhs_last_error(ctx));
@@ -310,6 +316,12 @@ public:
         int w = 1;
         mhs_values_plan_width(plan, &w);
         return w;
+    }
+    // the plan's sum type: MHS_ACC_F64 on a mixed plan (float values, double sums) only
+    mhs_accum accum() const {
+        int a = MHS_ACC_NATIVE;
+        mhs_values_plan_accum(plan, &a);
+        return (mhs_accum)a;
     }
     // the hipEvent time of the last MH_spgemm_values call through this plan (ms)
     double last_ms = 0;

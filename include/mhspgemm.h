@@ -307,7 +307,9 @@ int mhs_spgemm_values_grad(mhs_ctx *ctx, mhs_values_plan *plan, const double *Av
  * MHS_ERR_INVALID with a message naming both types, before any HIP call; nothing is written.
  * Cost on MI355X: the backward gains from the halved value bytes; the forward does not
  * where LDS sums carry the call (many products per C entry) -- the LDS float add is far slower than the
- * double one there, and such an FP32 forward is slower than the FP64 forward of the same pattern.
+ * double one there, and such an FP32 forward is slower than the FP64 forward of the same pattern.  The remedy is a
+ * mixed plan, float values summed in double (mhs_values_plan_create_accum with MHS_ACC_F64, below; DESIGN section 19:
+ * 0.22x the FP32 forward on cant-like, 1.04x the FP64 one).
  * Additions to ABI version 10, like the entries above. */
 typedef enum mhs_dtype { MHS_F64 = 0, MHS_F32 = 1 } mhs_dtype;
 int mhs_values_plan_create_typed(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
@@ -521,6 +523,58 @@ int mhs_spgemm_values_witness(mhs_ctx *ctx, mhs_values_plan *plan, const double 
                               const double *Cval, int32_t *wit, double *ms);
 int mhs_spgemm_values_witness_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float *Aval, const float *Bval,
                                   const float *Cval, int32_t *wit, double *ms);
+
+/* ---- mixed-precision values plans: FP32 values summed in FP64 ---------------------------------
+ * For float32 callers on patterns where LDS sums carry the call (many products per C entry): the LDS float add is far
+ * slower than the double one on this chip, and an FP32 forward is then slower than the FP64 one.
+ * A mixed plan takes float arrays and sums in double.  The sum type is a fifth fixed property of a plan, beside its
+ * value type, its width, its mask form and its semiring:
+ *   MHS_ACC_NATIVE   sums in the plan's value type: mhs_values_plan_create_accum is then exactly
+ *                    mhs_values_plan_create_batched
+ *   MHS_ACC_F64      with MHS_F64: the plain FP64 plan (mhs_values_plan_accum reports MHS_ACC_NATIVE);
+ *                    with MHS_F32: the mixed plan
+ * Any other accum returns MHS_ERR_INVALID before any HIP call, with a message naming the argument.  Mixed plans are
+ * plus-times only (min and max are exact in any type: the semiring creation call has no such argument).
+ * A mixed plan's classes, row lists, LDS needs and both launch plans are computed at the sum bytes 8 * width (width
+ * 1, 2 or 4): mhs_values_plan_info shows the rows per class of the FP64 plan of the same patterns and width, and
+ * mhs_values_plan_dtype says MHS_F32.  Validation, borrowing, plan memory, mhs_values_plan_kept, _width and _destroy
+ * are those of any plan.
+ * Hot calls are the existing _f32 entry points -- mhs_spgemm_values_f32, mhs_spgemm_values_batched_f32,
+ * mhs_spgemm_values_grad_f32, mhs_spgemm_values_grad_batched_f32 -- the plan knows its sum type; a double call on a
+ * mixed plan is refused as on any FP32 plan.  Stream, ms, MHS_OPT_SYNC and the contract of no allocation, no
+ * read-back and no synchronise are unchanged.
+ * The forward on a mixed plan.  On the team, wave, block and dot classes (rows[1..5] and rows[7]):
+ *   each product is formed in double from the two floats, which is exact (24 + 24 bits <= 53);
+ *   sums are double -- in LDS, in a register for the dot class;
+ *   each entry is rounded to float once, at its store.
+ *   For an entry of m kept products, E their exact sum and S the sum of their absolute values:
+ *     |got - E| <= 2^-24 |E| + m * 2^-53 * S * (1 + 2^-24).
+ *   Entries that no kept product reaches are exactly 0.0f.  Dot rows keep their fixed order, and their bits from call
+ *   to call and inside any batch.
+ * Global class (rows[6] of mhs_values_plan_info says how many rows this concerns): C's float segment stays the
+ * accumulator -- the FP32 plan's kernel, float atomics, the FP32 bound m * 2^-24 * S.  There is no double scratch for
+ * these rows.
+ * Inf, NaN and stored zeros: products are classified in double on the exactly converted operands, and the data
+ * contract's rule then gives NaN, +Inf or -Inf.  Otherwise the finite double sum is rounded to float once, and becomes
+ * +-Inf only where it leaves the float range: a product of two finite floats that would overflow in float does not
+ * poison its entry on its own (3e38 * 2 - 3e38 * 2 + 2^50 * 2^50 is exactly 2^100 here in any order, Inf or NaN on an
+ * FP32 plan; with a third product of 1 the bound above still holds, but S is then 1.2e39 and 1 is below m 2^-53 S).  An
+ * entry whose float rounding is subnormal is exempt, as on FP32 plans.
+ * The backward on a mixed plan is the FP32 plan's, run on the launch list planned at 8 * width bytes: the float
+ * kernels, float register sums for dAval in a fixed order, FP32 atomics for dBval, the FP32 bound.  The subgradient
+ * and witness entry points keep refusing plus-times plans.
+ * Cost on MI355X: on cant-like, where one LDS add per product carries the call, the mixed forward
+ * takes 0.374 ms against the FP32 plan's 1.68 and the FP64 plan's 0.360 (the 4 % over FP64 is contention among the LDS
+ * adds of the block-direct kernel, whose loads return sooner; not the conversions), and a width-2 batched call 0.76x the
+ * FP64 one;
+ * where loads and searches carry the call (scircuit-like, triangle) it is level with the FP32 plan at width 1 and, having
+ * the FP64 classes, up to twice as slow at width 4: use it on LDS-bound patterns.
+ * Additions to ABI version 10, like the entries above. */
+typedef enum mhs_accum { MHS_ACC_NATIVE = 0, MHS_ACC_F64 = 1 } mhs_accum;
+int mhs_values_plan_create_accum(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
+                                 int masked, int form, int dtype, int width, int accum, mhs_values_plan **plan);
+/* The plan's sum type (mhs_accum): MHS_ACC_F64 on a mixed plan only. */
+int mhs_values_plan_accum(const mhs_values_plan *plan, int *accum);
 
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).

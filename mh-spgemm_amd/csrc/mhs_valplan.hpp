@@ -47,6 +47,7 @@
 //   sb  plans                wave-direct span  wave-search n  block-direct span  block-search n  team row
 //   16  FP64 W=2, FP32 W=4                512            408              9,984           7,986   1,280 B
 //   32  FP64 W=4                          256            226              4,992           4,436   2,304 B
+// A mixed plan (FP32 values, FP64 sums: ValAccum below) of width W has the rows of the FP64 plan of width W: sb = 8 W.
 // A slice holds its sums set-major: acc[w x pitch + slot], pitch the span (direct) or the slice's entry count
 // (search), the one column array behind all W planes.  Counts still do not move.  At sb = 32 the team launch at its
 // cap is 73,728 B, past the VAL_LDS_PLAIN a launch may take unasked: val_team_registers says which team kernels
@@ -102,6 +103,18 @@ constexpr int VAL_WIDTH_MAX = 4;
 __host__ __device__ constexpr bool val_width_ok(int w) { return w == 1 || w == 2 || w == 4; }
 __host__ __device__ constexpr bool val_sb_ok(int sb) { return sb == 4 || sb == 8 || sb == 16 || sb == 32; }
 __host__ __device__ constexpr int val_search_entry(int vb) { return vb + 4; }  // a searched entry: its sum(s) and its column
+
+// The sum type of a plan, its fifth fixed property (mhs_accum of the C ABI): the value type's own, or FP64 sums of
+// FP32 values -- a mixed plan.  Such a plan's sum bytes are sb = W x 8 while its value bytes stay 4: its classes, lists,
+// needs and both launch plans are the FP64 plan's of the same patterns and width (every function here that takes vb
+// serves that sb), and only val_static_lds, the stage of values, is asked at vb = 4.  Its backward runs the float
+// kernels on that launch list: their guards at W x 4 accept whatever the guards at W x 8 accept
+// (tests/valplan_mixed_check.cpp).
+enum ValAccum : int { VAL_ACC_NATIVE = 0, VAL_ACC_F64 = 1 };
+constexpr bool val_accum_ok(int acc) { return acc == VAL_ACC_NATIVE || acc == VAL_ACC_F64; }
+__host__ __device__ constexpr int val_sum_bytes(int vb, int width, int acc) {
+    return width * (acc == VAL_ACC_F64 ? VAL_VB_F64 : vb);
+}
 
 // LDS bytes of one row, per method
 __host__ __device__ constexpr long long val_lds_search(long long n, int vb = VAL_VB_F64) {  // sums, then columns

@@ -18,6 +18,15 @@
 // was there (V(0), av * bv, atomicAdd, unsafeAtomicAdd, +=); plans of mhs_values_plan_create_semiring run the min-plus,
 // max-plus and max-min instantiations, at width 1: ds_min_* / ds_max_* in LDS, global_atomic_min_f64 / _max_f64 in
 // the global class (FP32 there: a compare-and-swap loop).
+// A mixed plan (mhs_values_plan_create_accum: FP32 values, FP64 sums) runs the forward's LDS and dot kernels with an
+// accumulator type Acc beside V, the last template parameter (default V: every other plan's kernels are the code that
+// was there): value arrays, stages and the B pieces in flight are V; a product is Acc(a) * Acc(b), exact for two floats
+// in double; slices, planes and the dot register are Acc, so the LDS add is ds_add_f64; an entry is converted to V
+// once, at its store.  Its global class is k_val_global<float>: C's float segment is the accumulator there.
+// The mixed instantiations are a translation unit -- a code object -- of their own: mhs_values_mixed.hip includes this
+// file with MHS_VALUES_MIXED_TU defined, which leaves the templates, issue_values_mixed and
+// init_values_mixed_attributes and takes out everything else; without it this file is every other plan's kernels and
+// no mixed one, so its code object holds the kernels it held before there were mixed plans.
 #include "mhs_valwalk.hpp"
 
 #include <climits>
@@ -34,8 +43,9 @@ template <int W, class V>
 __device__ __forceinline__ int val_nw(const ValArgs<V>& a) {
     return W == 1 ? 1 : a.nw;
 }
-template <int G, int W, class S = PlusTimes, class V, class F>
+template <int G, int W, class S = PlusTimes, class Acc = void, class V, class F>
 __device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int g, int ng, int t, F add) {
+    using Sum = typename ValAccOf<Acc, ValArgs<V>>::type;
     const int nw = val_nw<W>(a);
     const int ae = a.A.ptr[row + 1];
     for (int k = a.A.ptr[row] + g; k < ae; k += ng) {
@@ -47,10 +57,10 @@ __device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int 
         const int be = a.B.ptr[ac + 1];
         for (int j = a.B.ptr[ac] + t; j < be; j += G) {
             const int c = a.B.col[j];
-            ValSums<V, W> p;
+            ValSums<Sum, W> p;
 #pragma unroll
             for (int w = 0; w < W; ++w)
-                if (w < nw) p.x[w] = S::mul(av[w], a.B.val[(long long)w * a.sB + j]);
+                if (w < nw) p.x[w] = S::mul(Sum(av[w]), Sum(a.B.val[(long long)w * a.sB + j]));
             add(c, p);
         }
     }
@@ -63,9 +73,10 @@ __device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int 
 // sync that publishes them (the row's zero fill rides on that sync).
 // W > 1: the stage holds no A value (ValStage); a group reads each set's at the entry's A position, and
 // val_pieces(W) pieces of W values each are in flight.
-template <int G, int W, class S = PlusTimes, int CH, class V, class Sync, class Pre, class F>
+template <int G, int W, class S = PlusTimes, class Acc = void, int CH, class V, class Sync, class Pre, class F>
 __device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t, int lanes, ValStage<CH, V, W>& d, Sync sync,
                                             Pre pre, F add) {
+    using Sum = typename ValAccOf<Acc, ValArgs<V>>::type;
     constexpr int P = val_pieces(W);
     const int nw = val_nw<W>(a);
     const int g = t / G, ng = lanes / G, tl = t % G;
@@ -111,10 +122,10 @@ __device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t,
 #pragma unroll
                 for (int u = 0; u < P; ++u)
                     if (c[u] >= 0) {
-                        ValSums<V, W> p;
+                        ValSums<Sum, W> p;
 #pragma unroll
                         for (int w = 0; w < W; ++w)
-                            if (w < nw) p.x[w] = S::mul(av[w], v[u][w]);
+                            if (w < nw) p.x[w] = S::mul(Sum(av[w]), Sum(v[u][w]));
                         add(c[u], p);
                     }
             }
@@ -133,6 +144,7 @@ __device__ __forceinline__ void walk_columns(const ValPattern& p, int row, int g
     }
 }
 
+#ifndef MHS_VALUES_MIXED_TU  // (plan creation is no part of the mixed plans' translation unit)
 // ------------------------------------------------------------- validation ---
 // ptr[0] == 0, ptr monotone, ptr[M] == nnz, for A, B and C (which = 0, 1, 2): first bad row per matrix.
 __global__ __launch_bounds__(256) void k_val_check_ptr(const int* __restrict__ ptr, int M, int nnz, int* __restrict__ bad) {
@@ -258,12 +270,14 @@ __global__ __launch_bounds__(256) void k_val_count_kept(ValPattern p, unsigned l
     if (threadIdx.x == 0 && s_kept) atomicAdd(kept, s_kept);
 }
 
+#endif  // MHS_VALUES_MIXED_TU
 // ---------------------------------------------------------- value kernels ---
 // Searched sums of one row by `lanes` lanes (lane t): cols / acc are the row's LDS slice, set w's sums the
 // plane acc + w * pitch.  walk(pre, add) runs pre() and a sync, then add(column, sums) per product; sync orders
 // the steps (a wave's or a block's).  Every set's ds_add has the one slot, so the bank pattern of one set's.
-template <int W, class S = PlusTimes, class V, class Sync, class Walk>
-__device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V* acc, int* cols, int pitch, int t, int lanes,
+// Acc: the type of the sums (V, or a mixed plan's double); an entry is converted to V at its store.
+template <int W, class S = PlusTimes, class V, class Acc, class Sync, class Walk>
+__device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, Acc* acc, int* cols, int pitch, int t, int lanes,
                                            Sync sync, Walk walk) {
     const int nw = val_nw<W>(a);
     walk(
@@ -272,10 +286,10 @@ __device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V*
                 cols[p] = a.C.col[s + p];
 #pragma unroll
                 for (int w = 0; w < W; ++w)
-                    if (w < nw) acc[(size_t)w * pitch + p] = S::template identity<V>();
+                    if (w < nw) acc[(size_t)w * pitch + p] = S::template identity<Acc>();
             }
         },
-        [&](int c, const ValSums<V, W>& v) {
+        [&](int c, const ValSums<Acc, W>& v) {
             const int slot = find_slot(cols, n, c);
             if (slot >= 0) {
 #pragma unroll
@@ -287,12 +301,12 @@ __device__ __forceinline__ void row_search(const ValArgs<V>& a, int s, int n, V*
 #pragma unroll
     for (int w = 0; w < W; ++w)
         if (w < nw)
-            for (int p = t; p < n; p += lanes) a.C.val[(long long)w * a.sC + (s + p)] = acc[(size_t)w * pitch + p];
+            for (int p = t; p < n; p += lanes) a.C.val[(long long)w * a.sC + (s + p)] = V(acc[(size_t)w * pitch + p]);
     sync();
 }
 // Span-indexed sums of one row: acc[w * span + col - first], gathered through C.col afterwards.
-template <int W, class S = PlusTimes, class V, class Sync, class Walk>
-__device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, int first, int span, V* acc, int t, int lanes,
+template <int W, class S = PlusTimes, class V, class Acc, class Sync, class Walk>
+__device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, int first, int span, Acc* acc, int t, int lanes,
                                            Sync sync, Walk walk) {
     const int nw = val_nw<W>(a);
     walk(
@@ -300,9 +314,9 @@ __device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, in
 #pragma unroll
             for (int w = 0; w < W; ++w)
                 if (w < nw)
-                    for (int p = t; p < span; p += lanes) acc[(size_t)w * span + p] = S::template identity<V>();
+                    for (int p = t; p < span; p += lanes) acc[(size_t)w * span + p] = S::template identity<Acc>();
         },
-        [&](int c, const ValSums<V, W>& v) {
+        [&](int c, const ValSums<Acc, W>& v) {
             const unsigned slot = (unsigned)(c - first);
             if (slot < (unsigned)span) {
 #pragma unroll
@@ -315,31 +329,31 @@ __device__ __forceinline__ void row_direct(const ValArgs<V>& a, int s, int n, in
         const int slot = a.C.col[s + p] - first;
 #pragma unroll
         for (int w = 0; w < W; ++w)
-            if (w < nw) a.C.val[(long long)w * a.sC + (s + p)] = acc[(size_t)w * span + slot];
+            if (w < nw) a.C.val[(long long)w * a.sC + (s + p)] = V(acc[(size_t)w * span + slot]);
     }
     sync();
 }
 
 // One row of a wave or block class in the row frame: direct or searched sums over the staged walk.
-template <bool DIRECT, int W, class S, int CH, class V, class Sync>
+template <bool DIRECT, int W, class S, class Acc, int CH, class V, class Sync>
 __device__ __forceinline__ void row_sums(const ValArgs<V>& a, int row, char* base, int region, int t, int lanes,
                                          ValStage<CH, V, W>& d, Sync sync) {
-    val_row<DIRECT, W>(a, row, base, region, [&](int s, int n, int first, int span, V* acc, int* cols) {
-        const int pitch = val_slice_entries(region, W * (int)sizeof(V));  // (search: the slice's entries, as search_slice)
-        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP, W, S>(a, row, t, lanes, d, sync, pre, add); };
+    val_row<DIRECT, W, Acc>(a, row, base, region, [&](int s, int n, int first, int span, Acc* acc, int* cols) {
+        const int pitch = val_slice_entries(region, W * (int)sizeof(Acc));  // (search: the slice's entries, as search_slice)
+        auto walk = [&](auto pre, auto add) { walk_staged<VAL_GROUP, W, S, Acc>(a, row, t, lanes, d, sync, pre, add); };
         if constexpr (DIRECT) row_direct<W, S>(a, s, n, first, span, acc, t, lanes, sync, walk);
         else row_search<W, S>(a, s, n, acc, cols, pitch, t, lanes, sync, walk);
     });
 }
 
 // Team class: VAL_TEAM_LANES lanes per row, the teams of a wave in step (wave-level ordering).
-template <class V, int W, class S = PlusTimes>
+template <class V, int W, class S = PlusTimes, class Acc = V>
 __global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     const int team = threadIdx.x / VAL_TEAM_LANES, t = threadIdx.x % VAL_TEAM_LANES;
     const int nw = val_nw<W>(a);
-    const ValSlice<V> sl = search_slice<V, W>(lds + (size_t)team * region, region);
-    V* acc = sl.val;
+    const ValSlice<Acc> sl = search_slice<Acc, W>(lds + (size_t)team * region, region);
+    Acc* acc = sl.val;
     int* cols = sl.cols;
     for (int base = blockIdx.x * VAL_TEAM_ROWS; base < count; base += gridDim.x * VAL_TEAM_ROWS) {
         int s, n;
@@ -348,11 +362,11 @@ __global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __res
             cols[p] = a.C.col[s + p];
 #pragma unroll
             for (int w = 0; w < W; ++w)
-                if (w < nw) acc[(size_t)w * sl.ne + p] = S::template identity<V>();
+                if (w < nw) acc[(size_t)w * sl.ne + p] = S::template identity<Acc>();
         }
         vwave_sync();
         if (n > 0)
-            walk_products<VAL_TEAM_LANES, W, S>(a, row, 0, 1, t, [&](int c, const ValSums<V, W>& v) {
+            walk_products<VAL_TEAM_LANES, W, S, Acc>(a, row, 0, 1, t, [&](int c, const ValSums<Acc, W>& v) {
                 const int slot = find_slot(cols, n, c);
                 if (slot >= 0) {
 #pragma unroll
@@ -364,31 +378,31 @@ __global__ __launch_bounds__(256) void k_val_team(ValArgs<V> a, const int* __res
 #pragma unroll
         for (int w = 0; w < W; ++w)
             if (w < nw)
-                for (int p = t; p < n; p += VAL_TEAM_LANES) a.C.val[(long long)w * a.sC + (s + p)] = acc[(size_t)w * sl.ne + p];
+                for (int p = t; p < n; p += VAL_TEAM_LANES) a.C.val[(long long)w * a.sC + (s + p)] = V(acc[(size_t)w * sl.ne + p]);
         vwave_sync();
     }
 }
 
 // Wave classes: one wave64 per row, WPB rows per block.
-template <class V, int W, bool DIRECT, class S = PlusTimes>
+template <class V, int W, bool DIRECT, class S = PlusTimes, class Acc = V>
 __global__ __launch_bounds__(256) void k_val_wave(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     __shared__ ValStage<64, V, W> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     auto sync = [] { vwave_sync(); };
     for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB)
-        row_sums<DIRECT, W, S>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
+        row_sums<DIRECT, W, S, Acc>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
 }
 
 // Block classes: one block of T threads per row, up to the whole 160 KiB (VAL_BLOCK_BYTES dynamic + the stage).
-template <class V, int W, int T, bool DIRECT, class S = PlusTimes>
+template <class V, int W, int T, bool DIRECT, class S = PlusTimes, class Acc = V>
 __global__ __launch_bounds__(T) void k_val_block(ValArgs<V> a, const int* __restrict__ list, int count, int region) {
     extern __shared__ __align__(16) char lds[];
     __shared__ ValStage<VAL_STAGE, V, W> stage;
     auto sync = [] { __syncthreads(); };
     const XcdStretch x = xcd_stretch(count);
     for (int idx = x.begin; idx < x.end; idx += x.step)
-        row_sums<DIRECT, W, S>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
+        row_sums<DIRECT, W, S, Acc>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
 }
 
 // Global class: the row's Cval segment -- of every set of the pass -- is the accumulator.
@@ -423,13 +437,14 @@ __global__ __launch_bounds__(1024) void k_val_global(ValArgs<V> a, const int* __
 // duplicates, in B's order).  One sum per entry in a register, in A's entry order: no atomics, the
 // same bits on every call; the entry is stored once, reached or not.  The register sum is a V.
 // W sets: a value per set in the stage, a register sum per set, the one search per (entry, A column);
-// each set's sum in the order of the unbatched call, so with its bits.
+// each set's sum in the order of the unbatched call, so with its bits.  A mixed plan's register sum is an Acc
+// (double) of products formed in it, converted to V at the entry's one store; its stage stays V.
 template <class V, int W>
 struct DotStage {
     int col[64];
     V av[W][64];
 };
-template <class V, int W, class S = PlusTimes>
+template <class V, int W, class S = PlusTimes, class Acc = V>
 __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, const int* __restrict__ list, int count) {
     __shared__ DotStage<V, W> stage[WPB];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -447,9 +462,9 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, cons
                 lo0 = tr.tptr[j];
                 hi0 = tr.tptr[j + 1];
             }
-            V sum[W];
+            Acc sum[W];
 #pragma unroll
-            for (int w = 0; w < W; ++w) sum[w] = S::template identity<V>();
+            for (int w = 0; w < W; ++w) sum[w] = S::template identity<Acc>();
             for (int k0 = a0; k0 < ae; k0 += 64) {
                 const int cnt = ae - k0 < 64 ? ae - k0 : 64;
                 if (lane < cnt) {
@@ -472,7 +487,7 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, cons
                             const int q = tr.tperm[lo];
 #pragma unroll
                             for (int w = 0; w < W; ++w)
-                                if (w < nw) sum[w] = S::reg(sum[w], S::mul(d.av[w][e], a.B.val[(long long)w * a.sB + q]));
+                                if (w < nw) sum[w] = S::reg(sum[w], S::mul(Acc(d.av[w][e]), Acc(a.B.val[(long long)w * a.sB + q])));
                         }
                     }
                 vwave_sync();
@@ -480,28 +495,22 @@ __global__ __launch_bounds__(256) void k_val_dot(ValArgs<V> a, ValTrans tr, cons
             if (p < n) {
 #pragma unroll
                 for (int w = 0; w < W; ++w)
-                    if (w < nw) a.C.val[(long long)w * a.sC + (s + p)] = sum[w];
+                    if (w < nw) a.C.val[(long long)w * a.sC + (s + p)] = V(sum[w]);
             }
         }
     }
 }
 
-int blocks_for(long long items, int per, int cap) {
-    long long b = (items + per - 1) / per;
-    if (b < 1) b = 1;
-    return (int)(b < cap ? b : cap);
-}
-
 // The forward's kernels over the LDS classes' lists (val_lds_kernel), for the value type V and the width W
-// and the semiring policy S
-template <class V, int W, class S = PlusTimes>
+// and the semiring policy S, with sums of Acc (V; a mixed plan's: double over float)
+template <class V, int W, class S = PlusTimes, class Acc = V>
 struct ValKernels {
     using Fn = void (*)(ValArgs<V>, const int*, int, int);
-    static Fn team() { return k_val_team<V, W, S>; }
+    static Fn team() { return k_val_team<V, W, S, Acc>; }
     template <bool DIRECT>
-    static Fn wave() { return k_val_wave<V, W, DIRECT, S>; }
+    static Fn wave() { return k_val_wave<V, W, DIRECT, S, Acc>; }
     template <int T, bool DIRECT>
-    static Fn block() { return k_val_block<V, W, T, DIRECT, S>; }
+    static Fn block() { return k_val_block<V, W, T, DIRECT, S, Acc>; }
 };
 
 // The kernels' static LDS is what the plan header says (val_static_lds: tests/valplan_batched_check.cpp sums it
@@ -517,16 +526,50 @@ static_assert(val_static_lds_holds<double, 1>() && val_static_lds_holds<double, 
               "val_static_lds is the kernels' static LDS");
 
 // The 1024-thread block kernels of (V, W) for the whole 160 KiB, and the team kernel for its launch cap where
-// that is past what a launch may take unasked (val_team_registers: FP64 at width 4)
-template <class V, int W, class S = PlusTimes>
+// that is past what a launch may take unasked (val_team_registers: FP64 sums at width 4).  The sum bytes are the
+// accumulator's: a mixed plan's stages are float (the static_assert above covers them), its slices double.
+template <class V, int W, class S = PlusTimes, class Acc = V>
 hipError_t val_register() {
-    hipError_t e = val_allow_max_lds<ValKernels<V, W, S>>();
-    constexpr int sb = W * (int)sizeof(V);
+    hipError_t e = val_allow_max_lds<ValKernels<V, W, S, Acc>>();
+    constexpr int sb = W * (int)sizeof(Acc);
     if (e == hipSuccess && val_team_registers(sb))
-        e = hipFuncSetAttribute((const void*)ValKernels<V, W, S>::team(), hipFuncAttributeMaxDynamicSharedMemorySize,
+        e = hipFuncSetAttribute((const void*)ValKernels<V, W, S, Acc>::team(), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 val_team_launch_cap(sb));
     return e;
 }
+// One launch over its class's list.  Acc: the LDS and dot kernels' sums; the global class has none but C's segment and
+// is k_val_global<V>, which a launch of Acc other than V therefore does not reach (issue_values sends it the native way)
+template <class V, int W, class S = PlusTimes, class Acc = V>
+void issue_width(const ValLaunch& l, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s) {
+    const dim3 g(l.grid), b(l.block);
+    if (const typename ValKernels<V, W, S, Acc>::Fn k = val_lds_kernel<ValKernels<V, W, S, Acc>>(l.kernel, l.block)) {
+        hipLaunchKernelGGL(k, g, b, l.lds, s, a, list, l.count, l.region);
+    } else if (l.kernel == VK_GLOBAL) {
+        if constexpr (sizeof(Acc) == sizeof(V)) hipLaunchKernelGGL((k_val_global<V, W, S>), g, b, 0, s, a, list, l.count);
+    } else if (l.kernel == VK_DOT) {
+        hipLaunchKernelGGL((k_val_dot<V, W, S, Acc>), g, b, 0, s, a, t, list, l.count);
+    }
+}
+
+#ifdef MHS_VALUES_MIXED_TU
+}  // namespace
+
+// The mixed plans' kernels (FP32 values, FP64 sums), W = 1, 2, 4: their attributes, and one LDS-class or dot launch
+hipError_t init_values_mixed_attributes() {
+    hipError_t e = val_register<float, 1, PlusTimes, double>();
+    if (e == hipSuccess) e = val_register<float, 2, PlusTimes, double>();
+    if (e == hipSuccess) e = val_register<float, 4, PlusTimes, double>();
+    return e;
+}
+void issue_values_mixed(const ValLaunch& l, int width, const ValArgs<float>& a, const ValTrans& t, const int* list,
+                        hipStream_t s) {
+    switch (width) {  // (a width that is none of these made no plan: nothing to launch)
+    case 1: return issue_width<float, 1, PlusTimes, double>(l, a, t, list, s);
+    case 2: return issue_width<float, 2, PlusTimes, double>(l, a, t, list, s);
+    case 4: return issue_width<float, 4, PlusTimes, double>(l, a, t, list, s);
+    }
+}
+#else
 // ... of every width on plus-times, and of the three other semirings at their one width
 template <class V>
 hipError_t val_register_widths() {
@@ -539,11 +582,18 @@ hipError_t val_register_widths() {
     return e;
 }
 
+int blocks_for(long long items, int per, int cap) {
+    long long b = (items + per - 1) / per;
+    if (b < 1) b = 1;
+    return (int)(b < cap ? b : cap);
+}
+
 }  // namespace
 
 hipError_t init_values_attributes() {
     hipError_t e = val_register_widths<double>();
     if (e == hipSuccess) e = val_register_widths<float>();
+    if (e == hipSuccess) e = init_values_mixed_attributes();  // the mixed plans' (mhs_values_mixed.hip)
     if (e == hipSuccess) e = init_values_grad_attributes();  // their backward (mhs_values_grad.hip)
     if (e == hipSuccess) e = init_values_subgrad_attributes();  // the semiring plans' subgradient (mhs_values_subgrad.hip)
     return e;
@@ -580,20 +630,16 @@ void launch_val_verify(const ValPattern& p, int* bad, hipStream_t s) {
     hipLaunchKernelGGL(k_val_verify, dim3(blocks_for(p.M, WPB, 16384)), dim3(256), 0, s, p, bad);
 }
 
-namespace {
-template <class V, int W, class S = PlusTimes>
-void issue_width(const ValLaunch& l, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s) {
-    const dim3 g(l.grid), b(l.block);
-    if (const typename ValKernels<V, W, S>::Fn k = val_lds_kernel<ValKernels<V, W, S>>(l.kernel, l.block))
-        hipLaunchKernelGGL(k, g, b, l.lds, s, a, list, l.count, l.region);
-    else if (l.kernel == VK_GLOBAL) hipLaunchKernelGGL((k_val_global<V, W, S>), g, b, 0, s, a, list, l.count);
-    else if (l.kernel == VK_DOT) hipLaunchKernelGGL((k_val_dot<V, W, S>), g, b, 0, s, a, t, list, l.count);
-}
-}  // namespace
-
 template <class V>
-void issue_values(const ValLaunch& l, int width, int semiring, const ValArgs<V>& a, const ValTrans& t, const int* list,
-                  hipStream_t s) {
+void issue_values(const ValLaunch& l, int width, int semiring, int accum, const ValArgs<V>& a, const ValTrans& t,
+                  const int* list, hipStream_t s) {
+    if constexpr (sizeof(V) == VAL_VB_F32) {
+        // a mixed plan (plus-times: no other is made): its LDS and dot launches; its global class runs as an FP32 plan's
+        if (accum == VAL_ACC_F64 && l.kernel != VK_GLOBAL) {
+            if (semiring == SR_PLUS_TIMES) issue_values_mixed(l, width, a, t, list, s);
+            return;
+        }
+    }
     if (semiring != SR_PLUS_TIMES) {  // (width 1: no other plan of such a semiring is made)
         if (width != 1) return;
         switch (semiring) {
@@ -609,7 +655,9 @@ void issue_values(const ValLaunch& l, int width, int semiring, const ValArgs<V>&
     case 4: return issue_width<V, 4>(l, a, t, list, s);
     }
 }
-template void issue_values<double>(const ValLaunch&, int, int, const ValArgs<double>&, const ValTrans&, const int*, hipStream_t);
-template void issue_values<float>(const ValLaunch&, int, int, const ValArgs<float>&, const ValTrans&, const int*, hipStream_t);
+template void issue_values<double>(const ValLaunch&, int, int, int, const ValArgs<double>&, const ValTrans&, const int*,
+                                   hipStream_t);
+template void issue_values<float>(const ValLaunch&, int, int, int, const ValArgs<float>&, const ValTrans&, const int*, hipStream_t);
+#endif  // MHS_VALUES_MIXED_TU
 
 }  // namespace mhs

@@ -19,6 +19,9 @@
 // (spgemm_values_subgrad): two passes of the backward's launch list, which in turn refuses a plus-times plan.  Its
 // witness (spgemm_values_witness) is a third pass of the same kernels on a call of its own: the smallest inner index
 // among the winners of every C entry.
+// A plan has a sum type as well (mhs_values_plan_create_accum; ValAccum), fixed likewise: a mixed plan -- FP32 values,
+// FP64 sums -- classifies at width x 8 where its values are 4 bytes; its forward's issue passes the sum type on to
+// the kernels, and its backward is the float kernels on the launch list planned at those bytes.
 // Kernels and launchers: mhs_values.hip, mhs_values_grad.hip, mhs_values_subgrad.hip (declared in mhs_valwalk.hpp); classes,
 // launch plans, counter block and status words: mhs_valplan.hpp.
 #include "mhs_ctx.hpp"
@@ -37,6 +40,7 @@ struct mhs_values_plan {
     int dtype = MHS_F64;    // mhs_dtype: the type of every value array of its calls
     int width = 1;          // value sets a walk of its forward kernels sums (1, 2 or 4)
     int semiring = SR_PLUS_TIMES;  // mhs_semiring: what its forward kernels reduce the kept products with
+    int accum = VAL_ACC_NATIVE;    // mhs_accum: VAL_ACC_F64 on a mixed plan (dtype MHS_F32, sums in FP64) only
     ValPattern pat{};
     long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
     long long kept = 0;    // products that land in C's pattern (masked plans count them; else = products)
@@ -57,10 +61,13 @@ struct mhs_values_plan {
 namespace {
 
 constexpr int dtype_bytes(int dtype) { return dtype == MHS_F32 ? VAL_VB_F32 : VAL_VB_F64; }
-// The bytes a plan classifies at: its width x its value's size
-int sum_bytes(const mhs_values_plan* p) { return p->width * dtype_bytes(p->dtype); }
+// The bytes a plan classifies at: its width x the size of its sums (a mixed plan's: 8, its value's 4)
+int sum_bytes(const mhs_values_plan* p) { return val_sum_bytes(dtype_bytes(p->dtype), p->width, p->accum); }
 static_assert(MHS_VAL_WIDTH_MAX == VAL_WIDTH_MAX, "the header's width is the plan's");
+static_assert((int)MHS_ACC_NATIVE == (int)VAL_ACC_NATIVE && (int)MHS_ACC_F64 == (int)VAL_ACC_F64, "mhs_accum is ValAccum");
 const char* dtype_name(int dtype) { return dtype == MHS_F32 ? "FP32" : "FP64"; }
+// ... of a plan: its value type, and its sum type where that is another
+const char* plan_type_name(const mhs_values_plan* p) { return p->accum == VAL_ACC_F64 ? "FP32, FP64 sums" : dtype_name(p->dtype); }
 template <class V>
 constexpr int dtype_of() {
     static_assert(sizeof(V) == VAL_VB_F64 || sizeof(V) == VAL_VB_F32, "double or float");
@@ -224,8 +231,10 @@ struct PlanBuild {
 // width: the value sets a walk sums (mhs_values_plan_create_batched; 1 for every other entry point).
 // semiring: mhs_semiring (mhs_values_plan_create_semiring; MHS_SR_PLUS_TIMES for every other entry point); another
 // one than plus-times has width 1.
+// accum: mhs_accum (mhs_values_plan_create_accum; MHS_ACC_NATIVE for every other entry point); MHS_ACC_F64 on MHS_F64
+// is the native plan, on MHS_F32 the mixed one, which is plus-times.
 int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form, int dtype,
-                       int width, int semiring, mhs_values_plan** out) {
+                       int width, int semiring, int accum, mhs_values_plan** out) {
     if (!ctx) return MHS_ERR_INVALID;
     if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
     *out = nullptr;
@@ -237,6 +246,14 @@ int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const m
                     std::string("mhs_values_plan_create: a ") + val_semiring_name(semiring) + " plan has width 1");
     if (dtype != MHS_F64 && dtype != MHS_F32)
         return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: dtype is not an mhs_dtype (MHS_F64 or MHS_F32)");
+    if (!val_accum_ok(accum))
+        return fail(ctx, MHS_ERR_INVALID,
+                    "mhs_values_plan_create: accum " + std::to_string(accum) + " is not an mhs_accum (MHS_ACC_NATIVE or MHS_ACC_F64)");
+    if (dtype == MHS_F64) accum = VAL_ACC_NATIVE;  // (FP64 sums of FP64 values: the plain plan)
+    if (accum == VAL_ACC_F64 && semiring != SR_PLUS_TIMES)
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string("mhs_values_plan_create: a plan of FP32 values and FP64 sums is plus_times only, not ") +
+                        val_semiring_name(semiring));
     if (!val_width_ok(width))
         return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: width " + std::to_string(width) + " is not 1, 2 or 4");
     if (masked && (form < MHS_MASK_AUTO || form > MHS_MASK_DOT))
@@ -255,6 +272,7 @@ int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const m
     p->dtype = dtype;
     p->width = width;
     p->semiring = semiring;
+    p->accum = accum;
     p->pat = ValPattern{A->M, A->ptr, A->col, B->ptr, B->col, C->ptr, C->col};
     p->nnzA = A->nnz, p->nnzB = B->nnz, p->nnzC = C->nnz;
     Scratch sort_tmp;  // (B^T's sort scratch: it outlives the build's last step, which syncs the stream either way)
@@ -304,7 +322,7 @@ template <class V>
 int check_dtype(mhs_ctx* ctx, const mhs_values_plan* p, const char* call) {
     if (p->dtype == dtype_of<V>()) return MHS_OK;
     return fail(ctx, MHS_ERR_INVALID,
-                std::string(call) + ": the plan's values are " + dtype_name(p->dtype) + ", the call's " + dtype_name(dtype_of<V>()) +
+                std::string(call) + ": the plan's values are " + plan_type_name(p) + ", the call's " + dtype_name(dtype_of<V>()) +
                     " (the value type is fixed at plan creation: mhs_values_plan_create_typed)");
 }
 
@@ -337,7 +355,7 @@ int spgemm_values_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V* Ava
                              {p->pat.Cptr, p->pat.Ccol, Cval + b * sC}};
                 a.sA = sA, a.sB = sB, a.sC = sC;
                 a.nw = nb - b < W ? (int)(nb - b) : W;
-                issue_values(l, W, p->semiring, a, p->trans, list, s);
+                issue_values(l, W, p->semiring, p->accum, a, p->trans, list, s);
             }
         });
 }
@@ -516,29 +534,41 @@ int spgemm_values_grad_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V
 }  // namespace
 
 int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1, MHS_SR_PLUS_TIMES, out);
+    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1, MHS_SR_PLUS_TIMES, MHS_ACC_NATIVE, out);
 }
 
 int mhs_values_plan_create_masked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int form,
                                   mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, 1, MHS_SR_PLUS_TIMES, out);
+    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, 1, MHS_SR_PLUS_TIMES, MHS_ACC_NATIVE, out);
 }
 
 int mhs_values_plan_create_typed(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                  int dtype, mhs_values_plan** out) {
     return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, MHS_SR_PLUS_TIMES,
-                              out);
+                              MHS_ACC_NATIVE, out);
 }
 
 int mhs_values_plan_create_batched(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                    int dtype, int width, mhs_values_plan** out) {
     return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, width, MHS_SR_PLUS_TIMES,
-                              out);
+                              MHS_ACC_NATIVE, out);
 }
 
 int mhs_values_plan_create_semiring(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                     int dtype, int semiring, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, semiring, out);
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, semiring, MHS_ACC_NATIVE, out);
+}
+
+int mhs_values_plan_create_accum(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
+                                 int dtype, int width, int accum, mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, width, MHS_SR_PLUS_TIMES,
+                              accum, out);
+}
+
+int mhs_values_plan_accum(const mhs_values_plan* p, int* accum) {
+    if (!p || !accum) return MHS_ERR_INVALID;
+    *accum = p->accum;
+    return MHS_OK;
 }
 
 int mhs_values_plan_semiring(const mhs_values_plan* p, int* semiring) {

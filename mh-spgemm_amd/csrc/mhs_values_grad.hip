@@ -377,8 +377,17 @@ void issue_grad_width(const ValLaunch& l, const ValGradArgs<V>& a, const int* li
 }  // namespace
 
 hipError_t init_values_grad_attributes() {
-    const hipError_t e = grad_register_widths<double>();
-    return e == hipSuccess ? grad_register_widths<float>() : e;
+    hipError_t e = grad_register_widths<double>();
+    if (e == hipSuccess) e = grad_register_widths<float>();
+    // A mixed plan (FP32 values, FP64 sums) runs the float kernels on a launch list planned at sb = 8 W: at W = 4 its
+    // team launch is the FP64 one, past what the float team kernel's own sb = 16 asks for
+    static_assert(!val_team_registers(val_sum_bytes(VAL_VB_F32, 2, VAL_ACC_F64)) &&
+                      val_team_registers(val_sum_bytes(VAL_VB_F32, 4, VAL_ACC_F64)),
+                  "of the mixed plans, width 4 alone has a team launch to register");
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)GradKernels<float, 4>::team(), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                val_team_launch_cap(val_sum_bytes(VAL_VB_F32, 4, VAL_ACC_F64)));
+    return e;
 }
 
 template <class V>

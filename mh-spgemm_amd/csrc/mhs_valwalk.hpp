@@ -20,8 +20,9 @@ struct ValPattern {
     const int *Aptr, *Acol, *Bptr, *Bcol, *Cptr, *Ccol;
 };
 // ... and what a hot call's kernels take: each matrix as its pattern and the call's value array for it.
-// V is the plan's value type, double or float: the type of every value array, of the LDS sums and of the
-// atomics of a call.
+// V is the plan's value type, double or float: the type of every value array of a call, and -- but for the forward
+// of a mixed plan (mhs_values_plan_create_accum), whose kernels take an accumulator type beside it -- of the LDS sums
+// and of the atomics.
 template <class V>
 struct ValCsr {
     const int *ptr, *col;
@@ -39,7 +40,7 @@ struct ValArgs {
     long long sA = 0, sB = 0, sC = 0;
     int nw = 1;
 };
-// The products of one B entry with a staged A entry, one per set of the pass
+// The products of one B entry with a staged A entry, one per set of the pass (V: the forward's accumulator type)
 template <class V, int W>
 struct ValSums {
     V x[W];
@@ -81,10 +82,18 @@ void launch_val_count_kept(const ValPattern& p, int* cnt, hipStream_t s);
 // One launch of a values plan (plan_values) over its class's row list, on `s` (t: read by VK_DOT only).
 // V (double or float, both instantiated in mhs_values.hip) and `width` (1, 2 or 4) must be the type and the
 // width the plan was classified for: the kernels' slice guards are taken at width x sizeof(V).  `semiring`
-// (ValSemiring) is the plan's: SR_PLUS_TIMES at any width, the others at width 1 only.
+// (ValSemiring) is the plan's: SR_PLUS_TIMES at any width, the others at width 1 only.  `accum` (ValAccum) is the
+// plan's sum type: VAL_ACC_F64 with V = float runs the mixed kernels, whose guards are taken at width x 8, on a
+// plus-times plan; with V = double it is VAL_ACC_NATIVE.
 template <class V>
-void issue_values(const ValLaunch& l, int width, int semiring, const ValArgs<V>& a, const ValTrans& t, const int* list,
-                  hipStream_t s);
+void issue_values(const ValLaunch& l, int width, int semiring, int accum, const ValArgs<V>& a, const ValTrans& t,
+                  const int* list, hipStream_t s);
+// The mixed plans' part of the forward (mhs_values_mixed.hip): the attributes of its kernels (called by
+// init_values_attributes), and one launch of an LDS class or of the dot class of a mixed plan of `width` -- issue_values
+// hands them on; VK_GLOBAL is not among them.
+hipError_t init_values_mixed_attributes();
+void issue_values_mixed(const ValLaunch& l, int width, const ValArgs<float>& a, const ValTrans& t, const int* list,
+                        hipStream_t s);
 // One launch of a values plan's backward (plan_grad) over its class's row list, on `s` (mhs_values_grad.hip).
 // V and `width` as for issue_values: the backward's kernels hold `width` cotangents per C entry where the
 // forward's hold as many sums, behind the same slice guards.
@@ -196,9 +205,19 @@ static __device__ __forceinline__ ValSlice<V> search_slice(char* base, int regio
 }
 // A wave's or a block's row: body(s, n, first, span, val, cols) for C's segment [s, s + n) of `row`,
 // when it has entries and fits (direct: columns first .. first + span - 1; search: first = span = 0).
-template <bool DIRECT, int W = 1, class Args, class Body>
+// Acc: the type of the slice's sums where it is not the arguments' value type (void: it is) -- the forward of a
+// mixed plan, double sums of float values; the guards are then taken at W * sizeof(Acc), as the plan classified.
+template <class Acc, class Args>
+struct ValAccOf {
+    using type = Acc;
+};
+template <class Args>
+struct ValAccOf<void, Args> {
+    using type = typename Args::Value;
+};
+template <bool DIRECT, int W = 1, class Acc = void, class Args, class Body>
 __device__ __forceinline__ void val_row(const Args& p, int row, char* base, int region, Body body) {
-    using V = typename Args::Value;
+    using V = typename ValAccOf<Acc, Args>::type;
     const int s = p.C.ptr[row], n = p.C.ptr[row + 1] - s;
     if (n <= 0) return;
     if constexpr (DIRECT) {

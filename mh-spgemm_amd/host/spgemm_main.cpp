@@ -1,7 +1,7 @@
 // spgemm_main.cpp -- the `spgemm <file.mtx>` driver (reference src/main.cu:74-217)
 // on top of the C-ABI, printing the reference's stdout lines.
 //
-//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32]
+//   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--acc64]
 //          [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
@@ -36,6 +36,16 @@
 //             entry against the FP64 call's: within 1.01 m 2^-24 S for an entry of m kept products whose
 //             absolute values sum to S (m and S from FP64 calls on all-ones and on absolute values), and
 //             exactly 0 where m = 0.  Without --f32 nothing is added to the output.
+//   --acc64   a modifier of --f32: after each --f32 line (--reuse, --masked, --grad, and --batch with its --grad), that
+//             mode once more on a mixed plan -- float values, FP64 sums (mhs_values_plan_create_accum, MHS_F32 with
+//             MHS_ACC_F64) -- with one more line ("FP32, FP64 sums") and, with --check, "values f32 acc64 pass" /
+//             "... error" (likewise masked, grad, batched, grad batched).  The forward is held to the mixed plan's
+//             bound against the FP64 plan on the same float-rounded values: with E the exact sum, the mixed entry is
+//             within 2^-24 |E| + m 2^-53 S (1 + 2^-24) of it and the FP64 one within m 2^-53 S, so the two differ by at
+//             most 1.01 (2^-24 |ref| + 2 m 2^-53 S); rows of the global class (a row of more than
+//             159,744 / (8 W + 4) entries over more than 159,744 / (8 W) columns: C's float segment is their
+//             accumulator) are held to the FP32 bound.  The backward is the float kernels': the FP32 bound.
+//             --acc64 without --f32: the usage message.
 //   --batch NB [--width W]  a modifier of --reuse: after it, NB seeded value sets of A and B on the product's
 //             pattern, a plan of width W (mhs_values_plan_create_batched; 1, 2 or 4, default 4) and N calls of
 //             mhs_spgemm_values_batched on all NB sets beside N x NB unbatched calls on a width-1 plan: one more
@@ -275,10 +285,40 @@ static bool f32_within(const std::vector<float>& got, const std::vector<double>&
     return true;
 }
 
+// The forward of a mixed plan (FP32 values, FP64 sums) of width `width` against the FP64 call on the same values:
+// |got - ref| <= 1.01 (2^-24 |ref| + 2 m 2^-53 S) per entry, exactly 0 where m = 0; the rows the plan sends to its
+// global class -- by the plan's rule at 8 x width sum bytes, restated here on P's host pattern -- within the FP32 bound.
+// The restated rule is held against the plan: its rows must number plan_global, mhs_values_info's rows[6] (a masked
+// plan's dot rows come before the rule, so there the plan may count fewer); otherwise the check fails.
+static bool acc64_global_row(const CSR& P, int i, int width) {
+    const int s = P.ptr[i], n = P.ptr[i + 1] - s, sb = 8 * width, block_bytes = 159744;
+    if (n <= 0) return false;
+    const long long span = (long long)P.col[s + n - 1] - P.col[s] + 1;
+    return span > block_bytes / sb && n > (block_bytes / (sb + 4) & ~1);
+}
+static bool acc64_within(const CSR& P, int width, int plan_global, bool masked, const float* got, const std::vector<double>& ref,
+                         const std::vector<double>& m, const std::vector<double>& S) {
+    int restated = 0;
+    for (int i = 0; i < P.M; ++i) restated += acc64_global_row(P, i, width);
+    if (masked ? restated < plan_global : restated != plan_global) return false;
+    for (int i = 0; i < P.M; ++i) {
+        const bool global = acc64_global_row(P, i, width);
+        for (int q = P.ptr[i]; q < P.ptr[i + 1]; ++q) {
+            const double mm = std::floor(m[q] + 0.5), d = std::fabs((double)got[q] - ref[q]);
+            const double bound = global ? 1.01 * mm * 5.9604644775390625e-8 * S[q]
+                                        : 1.01 * (5.9604644775390625e-8 * std::fabs(ref[q]) + 2 * mm * 1.1102230246251565e-16 * S[q]);
+            if (mm == 0 ? got[q] != 0.0f : !(d <= bound)) return false;
+        }
+    }
+    return true;
+}
+
 // One mode: plans of both types for A * B on P's pattern (masked: a mask), `calls` calls of each -- the values
 // call, or (backward) the backward call with both gradients on a seeded cotangent -- and the check.
+// acc64: the FP32 plan is a mixed one (FP64 sums); P's host pattern is then read by the forward's check.
 static void run_f32(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool masked, bool backward, int calls, bool check,
-                    const char* label, const char* tag) {
+                    const char* label, const char* tag, bool acc64 = false) {
+    const char* sfx = acc64 ? " acc64" : "";
     try {
         const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)P.nnz;
         auto rounded = [](const double* v, size_t n) {
@@ -293,7 +333,8 @@ static void run_f32(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool 
             G[s] = 0.1 + 0.9 * (double)(state >> 11) / 9007199254740992.0;
         }
         const std::vector<float> a32 = rounded(A.val, nA), b32 = rounded(B.val, nB), g32 = rounded(G.data(), nC);
-        mhs_shim::ValuesPlan p32(tools, A, B, P, masked, MHS_MASK_AUTO, MHS_F32), p64(tools, A, B, P, masked, MHS_MASK_AUTO, MHS_F64);
+        mhs_shim::ValuesPlan p32(tools, A, B, P, masked, MHS_MASK_AUTO, MHS_F32, 1, MHS_SR_PLUS_TIMES, acc64 ? MHS_ACC_F64 : MHS_ACC_NATIVE);
+        mhs_shim::ValuesPlan p64(tools, A, B, P, masked, MHS_MASK_AUTO, MHS_F64);
         DevArr<float> fa(nA), fb(nB), fg(nC), fc(nC), fda(nA), fdb(nB);
         DevArr<double> da(nA), db(nB), dg(nC), dc(nC), dda(nA), ddb(nB);
         fa.put(a32), fb.put(b32), fg.put(g32);
@@ -323,16 +364,17 @@ static void run_f32(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool 
             ref = call64([](float x) { return (double)x; }, &ms);
             t64.push_back(ms);
         }
-        std::printf("MH-SpGEMM %s FP32 median of %d calls is %.3lf ms, FP64 on the same rounded values %.3lf ms\n", label, calls,
-                    median(t32), median(t64));
+        std::printf("MH-SpGEMM %s FP32%s median of %d calls is %.3lf ms, FP64 on the same rounded values %.3lf ms\n", label,
+                    acc64 ? ", FP64 sums" : "", calls, median(t32), median(t64));
         if (check) {
             const Out m = call64([](float) { return 1.0; }, nullptr), S = call64([](float x) { return std::fabs((double)x); }, nullptr);
             const bool ok = backward ? f32_within(fda.get(), ref.a, m.a, S.a) && f32_within(fdb.get(), ref.b, m.b, S.b)
+                            : acc64  ? acc64_within(P, 1, p32.info().rows[6], masked, fc.get().data(), ref.c, m.c, S.c)
                                      : f32_within(fc.get(), ref.c, m.c, S.c);
-            std::printf("%s f32 %s\n", tag, ok ? "pass" : "error");
+            std::printf("%s f32%s %s\n", tag, sfx, ok ? "pass" : "error");
         }
     } catch (const std::exception&) {
-        std::printf("%s f32 error\n", tag);
+        std::printf("%s f32%s error\n", tag, sfx);
     }
 }
 
@@ -572,10 +614,13 @@ static void run_witness(Tool& tools, const CSR& A, const CSR& B, const CSR& P, b
 
 // --batch NB: NB seeded value sets in one batched call on a plan of `width`, beside NB unbatched calls on a
 // width-1 plan of the same type T; with check every set of the batched call against its reference (see the top).
+// acc64 (T = float): both plans are mixed ones (FP64 sums), checked by acc64_within on C's host pattern.
 template <class T>
-static void run_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int calls, int nb, int width, bool check) {
+static void run_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int calls, int nb, int width, bool check,
+                      bool acc64 = false) {
     const bool f32 = sizeof(T) == sizeof(float);
-    const char* tag = f32 ? "batched f32" : "batched";
+    const char* tag = acc64 ? "batched f32 acc64" : f32 ? "batched f32" : "batched";
+    const int acc = acc64 ? MHS_ACC_F64 : MHS_ACC_NATIVE;
     try {
         const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)C.nnz, sets = (size_t)nb;
         unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
@@ -589,7 +634,8 @@ static void run_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int
         };
         const std::vector<T> va = seeded(sets * nA), vb = seeded(sets * nB);
         const mhs_dtype dt = f32 ? MHS_F32 : MHS_F64;
-        mhs_shim::ValuesPlan wide(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, width), one(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, 1);
+        mhs_shim::ValuesPlan wide(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, width, MHS_SR_PLUS_TIMES, acc);
+        mhs_shim::ValuesPlan one(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, 1, MHS_SR_PLUS_TIMES, acc);
         DevArr<T> a(sets * nA), b(sets * nB), c(sets * nC), c1(sets * nC);
         a.put(va), b.put(vb);
         std::vector<double> tb, tl;
@@ -606,7 +652,7 @@ static void run_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int
             tl.push_back(sum);
         }
         std::printf("MH-SpGEMM values batched %s (%d sets, width %d) median of %d calls is %.3lf ms, %d unbatched calls %.3lf ms\n",
-                    f32 ? "FP32" : "FP64", nb, width, calls, median(tb), nb, median(tl));
+                    acc64 ? "FP32, FP64 sums" : f32 ? "FP32" : "FP64", nb, width, calls, median(tb), nb, median(tl));
         if (check) {
             // FP64 calls on a width-1 plan: m per entry from all-ones, and per set the reference / S on the set's values
             mhs_shim::ValuesPlan p64(tools, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1);
@@ -622,6 +668,12 @@ static void run_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int
                 db.put(std::vector<double>(vb.begin() + k * nB, vb.begin() + (k + 1) * nB));
                 f32_ok(p64.ctx, mhs_spgemm_values(p64.ctx, p64.plan, da.p, db.p, dc.p, nullptr));
                 const std::vector<double> ref = dc.get();  // (positive values: also S)
+                if constexpr (sizeof(T) == sizeof(float)) {
+                    if (acc64) {
+                        ok = acc64_within(C, width, wide.info().rows[6], false, got.data() + k * nC, ref, m, ref);
+                        continue;
+                    }
+                }
                 for (size_t i = 0; i < nC && ok; ++i) {
                     const double mm = std::floor(m[i] + 0.5), g = (double)got[k * nC + i];
                     ok = mm == 0 ? g == 0.0 : std::fabs(g - ref[i]) <= factor * mm * u * ref[i];
@@ -645,10 +697,13 @@ static void grad_unbatched(mhs_shim::ValuesPlan& p, const float* a, const float*
 // --grad N with --batch NB: the backward of the batched call, NB seeded value and cotangent sets in one call of
 // mhs_spgemm_values_grad_batched on a plan of `width`, beside NB unbatched backward calls on a width-1 plan of the
 // same type T; with check every set of the batched call against the unbatched call on that set (see the top).
+// acc64 (T = float): both plans are mixed ones; their backward is the float kernels', so the check is the FP32 one.
 template <class T>
-static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int calls, int nb, int width, bool check) {
+static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C, int calls, int nb, int width, bool check,
+                           bool acc64 = false) {
     const bool f32 = sizeof(T) == sizeof(float);
-    const char* tag = f32 ? "grad batched f32" : "grad batched";
+    const char* tag = acc64 ? "grad batched f32 acc64" : f32 ? "grad batched f32" : "grad batched";
+    const int acc = acc64 ? MHS_ACC_F64 : MHS_ACC_NATIVE;
     try {
         const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)C.nnz, sets = (size_t)nb;
         unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
@@ -661,7 +716,8 @@ static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C
             return v;
         };
         const mhs_dtype dt = f32 ? MHS_F32 : MHS_F64;
-        mhs_shim::ValuesPlan wide(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, width), one(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, 1);
+        mhs_shim::ValuesPlan wide(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, width, MHS_SR_PLUS_TIMES, acc);
+        mhs_shim::ValuesPlan one(tools, A, B, C, false, MHS_MASK_PRODUCT, dt, 1, MHS_SR_PLUS_TIMES, acc);
         DevArr<T> a(sets * nA), b(sets * nB), g(sets * nC), da(sets * nA), db(sets * nB), da1(sets * nA), db1(sets * nB);
         a.put(seeded(sets * nA)), b.put(seeded(sets * nB)), g.put(seeded(sets * nC));
         std::vector<double> tb, tl;
@@ -679,7 +735,7 @@ static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C
             tl.push_back(sum);
         }
         std::printf("MH-SpGEMM values grad batched %s (%d sets, width %d) median of %d calls is %.3lf ms, %d unbatched calls %.3lf ms\n",
-                    f32 ? "FP32" : "FP64", nb, width, calls, median(tb), nb, median(tl));
+                    acc64 ? "FP32, FP64 sums" : f32 ? "FP32" : "FP64", nb, width, calls, median(tb), nb, median(tl));
         if (check) {
             // m per entry from the unbatched call on all-ones; the seeded values are positive, so a set's unbatched
             // result is also its S, and the two calls -- each within 1.01 m u S of the exact sum -- differ by at most twice that
@@ -706,7 +762,7 @@ static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C
 int main(int argc, char** argv) {
     int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0, semiring = -1, subgrad = 0, witness = 0;
     bool has_semiring = false;
-    bool aat = false, vendor = false, check = false, cache = false, f32 = false;
+    bool aat = false, vendor = false, check = false, cache = false, f32 = false, acc64 = false;
     std::string csv;
     const char* filename = nullptr;
     bool bad = false;
@@ -722,6 +778,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--masked") && i + 1 < argc) masked = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--grad") && i + 1 < argc) grad = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--f32")) f32 = true;
+        else if (!std::strcmp(argv[i], "--acc64")) acc64 = true;
         else if (!std::strcmp(argv[i], "--batch") && i + 1 < argc) batch = std::atoi(argv[++i]), bad = bad || batch < 1;
         else if (!std::strcmp(argv[i], "--width") && i + 1 < argc) {
             width = std::atoi(argv[++i]);
@@ -740,10 +797,11 @@ int main(int argc, char** argv) {
     if (has_semiring && reuse <= 0 && masked <= 0) bad = true;  // (a modifier of --reuse and --masked)
     if ((subgrad > 0 || witness > 0) && (!has_semiring || semiring <= MHS_SR_PLUS_TIMES)) bad = true;  // (modifiers of --semiring, not plus_times)
     if ((batch > 0 && reuse <= 0) || (width > 0 && batch <= 0)) bad = true;  // (modifiers of --reuse and of --batch)
+    if (acc64 && !f32) bad = true;  // (a modifier of --f32)
     if (width == 0) width = MHS_VAL_WIDTH_MAX;
     if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0 || grad < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--acc64] [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -856,21 +914,27 @@ int main(int argc, char** argv) {
         else if (masked > 0) run_masked(tools, A, B, C, masked, check);
         if (grad > 0) run_grad(tools, A, B, C, grad, check);
         if (f32) {
+            if (acc64 && check) C.D2H();  // (the pattern's host arrays: the mixed forward's check picks out the global class)
             if (reuse > 0) run_f32(tools, A, B, C, false, false, reuse, check, "values-only (pattern reused)", "values");
+            if (reuse > 0 && acc64) run_f32(tools, A, B, C, false, false, reuse, check, "values-only (pattern reused)", "values", true);
             if (masked > 0 && A.M == A.N) {
                 CSR mask;  // A's pattern (a plan reads no values)
                 const bool owns = mask_of(A, B.N, mask);
                 run_f32(tools, A, B, mask, true, false, masked, check, "masked (A's pattern)", "masked");
+                if (acc64) run_f32(tools, A, B, mask, true, false, masked, check, "masked (A's pattern)", "masked", true);
                 unborrow_mask(mask, owns);
             }
             if (grad > 0) run_f32(tools, A, B, C, false, true, grad, check, "values backward (both gradients)", "grad");
+            if (grad > 0 && acc64) run_f32(tools, A, B, C, false, true, grad, check, "values backward (both gradients)", "grad", true);
         }
         if (batch > 0) {
             run_batch<double>(tools, A, B, C, reuse, batch, width, check);
             if (f32) run_batch<float>(tools, A, B, C, reuse, batch, width, check);
+            if (acc64) run_batch<float>(tools, A, B, C, reuse, batch, width, check, true);
             if (grad > 0) {
                 run_grad_batch<double>(tools, A, B, C, grad, batch, width, check);
                 if (f32) run_grad_batch<float>(tools, A, B, C, grad, batch, width, check);
+                if (acc64) run_grad_batch<float>(tools, A, B, C, grad, batch, width, check, true);
             }
         }
         if (has_semiring) {

@@ -49,6 +49,9 @@ MHS_MASK_DOT = 2
 MHS_F64 = 0
 MHS_F32 = 1
 MHS_VAL_WIDTH_MAX = 4  # a values plan's width is 1, 2 or 4
+# mhs_accum: the sum type of a values plan (MHS_ACC_F64 on MHS_F32: a mixed plan, float values summed in double)
+MHS_ACC_NATIVE = 0
+MHS_ACC_F64 = 1
 # mhs_semiring: what a values plan reduces the kept products with
 MHS_SR_PLUS_TIMES = 0
 MHS_SR_MIN_PLUS = 1
@@ -218,6 +221,12 @@ def lib() -> ctypes.CDLL:
             L.mhs_values_plan_create_semiring.restype = c_int
             L.mhs_values_plan_semiring.argtypes = [c_void_p, P(c_int)]
             L.mhs_values_plan_semiring.restype = c_int
+        if hasattr(L, "mhs_values_plan_create_accum"):  # (mixed-precision values plans: a later addition to ABI 10)
+            L.mhs_values_plan_create_accum.argtypes = [c_void_p, P(mhs_csr), P(mhs_csr), P(mhs_csr), c_int, c_int, c_int,
+                                                       c_int, c_int, P(c_void_p)]
+            L.mhs_values_plan_create_accum.restype = c_int
+            L.mhs_values_plan_accum.argtypes = [c_void_p, P(c_int)]
+            L.mhs_values_plan_accum.restype = c_int
         if hasattr(L, "mhs_spgemm_values_subgrad"):  # (semiring subgradients: a later addition to ABI 10)
             for fn in (L.mhs_spgemm_values_subgrad, L.mhs_spgemm_values_subgrad_f32):
                 fn.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

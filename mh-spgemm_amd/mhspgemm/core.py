@@ -392,7 +392,33 @@ def values_dtype_name(dtype) -> str:
     return name
 
 
-class ValuesPlan:
+def values_accum(accum):
+    """A values plan's ``accum`` argument as ``None`` (sums in the plan's value type) or ``"float64"``: ``None``,
+    ``"float64"`` / ``"f64"`` or ``torch.float64``.  ValueError for anything else."""
+    if accum is None:
+        return None
+    name = {"f64": "float64"}.get(accum, accum) if isinstance(accum, str) else str(accum).replace("torch.", "")
+    if name != "float64":
+        raise ValueError(f"accum: None (the plan's value type) or torch.float64 (or its name), not {accum!r}")
+    return name
+
+
+class _AccumKeyword(type):
+    """``ValuesPlan(..., accum=...)``: the sum type is taken here, as a keyword only, checked, and left on the instance
+    for ``__init__``, whose own signature stays as released -- ``semiring`` is its trailing argument, so positional
+    callers keep their meaning (tests/test_semiring_host.py pins it).  What follows from that: ``accum`` reaches a plan only
+    through the constructor call ``ValuesPlan(...)`` -- a direct ``ValuesPlan.__init__`` or ``super().__init__`` makes a
+    plan of native sums -- ``inspect.signature(ValuesPlan)`` does not list it, and a subclass that needs a metaclass of
+    its own derives it from this one.  Once the pin may move, ``accum`` becomes an ordinary trailing parameter."""
+
+    def __call__(cls, *args, accum=None, **kw):
+        self = cls.__new__(cls)
+        self.accum = values_accum(accum)
+        self.__init__(*args, **kw)
+        return self
+
+
+class ValuesPlan(metaclass=_AccumKeyword):
     """Values-only SpGEMM on a kept pattern (mhs_values_plan_create / mhs_spgemm_values).
 
     ``A`` and ``B`` are device-resident ``CSR``; ``C`` is a ``DeviceCSR`` (what ``spgemm``
@@ -433,18 +459,32 @@ class ValuesPlan:
     result; ``apply_subgrad`` is the pair as a ``torch.autograd.Function``.  Both raise the library's refusal on a
     plus_times plan.  Its arg is ``witness`` (mhs_spgemm_values_witness): the smallest inner index ``k`` among the
     products that attain each C entry, -1 where there is none; ``run_arg`` is the forward and the witness together.
-    They raise the library's refusal on a plus_times plan too (a sum has no witness)."""
+    They raise the library's refusal on a plus_times plan too (a sum has no witness).
+
+    ``accum`` (``None``, the default: sums in the plan's value type; or ``torch.float64``, also by name;
+    mhs_values_plan_create_accum) is the plan's sum type.  ``dtype="float32", accum="float64"`` is a mixed plan: float32
+    tensors in and out, products and sums in double (an entry is the double sum of exact products, rounded to float
+    once), rows classified as the float64 plan's of the same width -- for float32 callers on patterns where the slow
+    LDS float add carries the forward.  Rows of the global class and the backward keep float sums.  With
+    ``dtype="float64"`` it is the plain float64 plan.  It is refused with another semiring than plus_times
+    (``ValueError``).  ``run``, ``run_batched``, ``grad``, ``grad_batched``, ``apply`` and ``apply_batched`` serve a
+    mixed plan as they serve a float32 plan.  ``accum`` is a keyword of the constructor call only, taken by the
+    metaclass and not by ``__init__`` (see ``_AccumKeyword`` for what that means for subclasses and direct calls)."""
 
     _semiring = "plus_times"
 
     def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto", dtype="float64", width=1,
                  semiring="plus_times"):
         self.width = values_width(width)
+        self.accum = getattr(self, "accum", None)  # (the keyword ``accum``, checked: _AccumKeyword)
         if not isinstance(semiring, str) or semiring not in SEMIRINGS:
             raise ValueError(f"semiring: one of {sorted(SEMIRINGS)}, not {semiring!r}")
         self._semiring = semiring
         if semiring != "plus_times" and self.width != 1:
             raise ValueError(f"width: a {semiring} plan has width 1, not {self.width}")
+        if semiring != "plus_times" and self.accum is not None:
+            raise ValueError(f"accum: a {semiring} plan sums nothing (min and max are exact in any type): accum must be None, "
+                             f"not {self.accum!r}")
         if not hasattr(L.lib(), "mhs_values_plan_create"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no values-only entry points")
         if masked and not hasattr(L.lib(), "mhs_values_plan_create_masked"):
@@ -457,6 +497,8 @@ class ValuesPlan:
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no FP32 values entry points")
         if semiring != "plus_times" and not hasattr(L.lib(), "mhs_values_plan_create_semiring"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no semiring values entry points")
+        if self.accum is not None and not hasattr(L.lib(), "mhs_values_plan_create_accum"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no mixed-precision values entry points")
         if isinstance(form, str):
             if form not in MASK_FORMS:
                 raise ValueError(f"form: one of {sorted(MASK_FORMS)}, not {form!r}")
@@ -477,6 +519,11 @@ class ValuesPlan:
                                                          int(self.masked), self.form, VALUES_DTYPES[self.dtype_name],
                                                          SEMIRINGS[semiring], ctypes.byref(self.plan))
             _check(tool.ctx, rc, "mhs_values_plan_create_semiring")
+        elif self.accum is not None:
+            rc = L.lib().mhs_values_plan_create_accum(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                      int(self.masked), self.form, VALUES_DTYPES[self.dtype_name],
+                                                      self.width, L.MHS_ACC_F64, ctypes.byref(self.plan))
+            _check(tool.ctx, rc, "mhs_values_plan_create_accum")
         elif self.width > 1:
             rc = L.lib().mhs_values_plan_create_batched(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
                                                         int(self.masked), self.form, VALUES_DTYPES[self.dtype_name],
@@ -863,8 +910,9 @@ class ValuesPlan:
     def info(self) -> dict:
         """Rows per class (by name and as the ``rows`` list indexed by class id), products, nnzC, plan_bytes,
         kept_products: the products that land in C's pattern (all of them unless the plan is masked), dtype:
-        the plan's value type by name, width: its value sets per walk, and semiring: its semiring by name (all three
-        as the library reports them)."""
+        the plan's value type by name, width: its value sets per walk, semiring: its semiring by name, and accum: its
+        sum type -- ``"float64"`` on a mixed plan (float32 values summed in double), ``None`` where the sums have the
+        value type (all four as the library reports them)."""
         i = L.mhs_values_info()
         _check(self.tool.ctx, L.lib().mhs_values_plan_info(self.plan, ctypes.byref(i)), "mhs_values_plan_info")
         rows = [int(x) for x in i.rows]
@@ -890,6 +938,11 @@ class ValuesPlan:
             sr = ctypes.c_int(0)
             _check(self.tool.ctx, L.lib().mhs_values_plan_semiring(self.plan, ctypes.byref(sr)), "mhs_values_plan_semiring")
             d["semiring"] = {v: k for k, v in SEMIRINGS.items()}[int(sr.value)]
+        d["accum"] = None
+        if hasattr(L.lib(), "mhs_values_plan_accum"):
+            acc = ctypes.c_int(0)
+            _check(self.tool.ctx, L.lib().mhs_values_plan_accum(self.plan, ctypes.byref(acc)), "mhs_values_plan_accum")
+            d["accum"] = "float64" if int(acc.value) == L.MHS_ACC_F64 else None
         return d
 
     def close(self):

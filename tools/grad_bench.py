@@ -2,7 +2,7 @@
 """grad_bench.py -- the values backward against the values call on the same plan, one workload per run.
 
     python tools/grad_bench.py [--workload cant|scircuit|triangle] [--blocks 5] [--window 0.4] [--dtype f32|f64]
-                               [--batch NB --width W]
+                               [--accum f64] [--batch NB --width W]
 
 Workloads: `cant` and `scircuit` are A*A on the product's own pattern (the stand-ins of
 mhspgemm.synth unless the real matrices are present); `triangle` is L*L on L's pattern, a masked plan
@@ -22,6 +22,8 @@ relative (the same terms summed in another order), for the one-sided calls and f
 products any output entry sums (the values are positive, so each side is within m 2^-24 of the exact sum; m
 from an FP64 plan on all-ones values, B's longest row and A's fullest column); that plan's rows by class are
 reported as `classes_f64`, and the dB side's atomic bytes are 4 a product.
+--accum f64 with --dtype f32: a mixed plan -- FP64 sums in the forward, whose rows by class are then
+the FP64 plan's; the backward is the FP32 plan's kernels on that launch list, and the FP32 tolerances stand.
 Also reported: the dB side's atomic bytes per second, 8 * kept_products / the grad_B time, and
 `masked_alternative_products`: what the two gradients would walk as masked products of their own,
 dA = (G*B^T)<A>: the sum over C's entries (i, j) of len(B^T row j), and dB = (A^T*G)<B>: the sum over
@@ -93,13 +95,15 @@ def batched(args):
         owned, _ = mhspgemm.spgemm(tool, A, A, timing=False)
         C = owned
     kw = {"masked": True, "form": "auto"} if masked else {}
+    if args.accum == "f64":  # mixed plans: the backward is the FP32 plans' on the launch list planned at 8 W bytes
+        kw["accum"] = "float64"
     wide = mhspgemm.ValuesPlan(tool, A, A, C, dtype=tdt, width=W, **kw)
     one = mhspgemm.ValuesPlan(tool, A, A, C, dtype=tdt, width=1, **kw)
     iw, i1 = wide.info(), one.info()
     nC, nnz = iw["nnzC"], A.nnz
     out = {"workload": args.workload, "source": source, "M": A.M, "nnzA": nnz, "nnzC": nC, "products": iw["products"],
-           "kept_products": iw["kept_products"], "dtype": args.dtype, "width": W, "batch": NB, "blocks": args.blocks,
-           "lib": lib_name(), "classes": {k: iw[k] for k in mhspgemm.core.VALUES_CLASSES},
+           "kept_products": iw["kept_products"], "dtype": args.dtype, "accum": args.accum, "width": W, "batch": NB,
+           "blocks": args.blocks, "lib": lib_name(), "classes": {k: iw[k] for k in mhspgemm.core.VALUES_CLASSES},
            "classes_width1": {k: i1[k] for k in mhspgemm.core.VALUES_CLASSES}}
     rng = np.random.default_rng(17)
     av, bv, G = (torch.from_numpy(rng.uniform(0.1, 1.0, (NB, n))).to(tdt).to(device) for n in (nnz, nnz, nC))
@@ -201,11 +205,15 @@ def main():
     ap.add_argument("--window", type=float, default=0.4, help="seconds a timed block should last")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--dtype", default="f64", choices=("f32", "f64"), help="the plan's value type")
+    ap.add_argument("--accum", default=None, choices=("f64",), help="with --dtype f32: FP64 sums in the forward (a mixed plan); "
+                    "its backward is the FP32 plan's, and the FP32 tolerances stand")
     ap.add_argument("--batch", type=int, default=0, help="value sets (NB) of the batched backward; 0: the unbatched line")
     ap.add_argument("--width", type=int, default=None, choices=(1, 2, 4), help="the batched plan's width (with --batch; default 4)")
     args = ap.parse_args()
     if args.batch < 0 or (args.width is not None and args.batch == 0):
         ap.error("--batch: at least one value set; --width goes with --batch")
+    if args.accum == "f64" and args.dtype != "f32":
+        ap.error("--accum f64 goes with --dtype f32")
     if args.batch:
         args.width = args.width or 4
         return batched(args)
@@ -229,8 +237,10 @@ def main():
         torch.cuda.synchronize(dev)
 
     out = {"workload": args.workload, "source": source, "M": A.M, "nnzA": A.nnz, "products": int(flop),
-           "blocks": args.blocks, "lib": lib_name(), "dtype": args.dtype}
+           "blocks": args.blocks, "lib": lib_name(), "dtype": args.dtype, "accum": args.accum}
     kw = {"dtype": "float32"} if f32 else {}  # (an older library's wrapper has no dtype argument)
+    if args.accum == "f64":
+        kw["accum"] = "float64"
     if masked:
         C = mhspgemm.CSR(A.M, A.N, A.ptr, A.col, np.zeros(A.nnz))
         C.H2D(dev)

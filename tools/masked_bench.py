@@ -44,6 +44,7 @@ import torch  # noqa: E402
 import mhspgemm  # noqa: E402
 from mhspgemm import _lib as L  # noqa: E402
 from mhspgemm import synth  # noqa: E402
+from mixed_rows import mixed_global_rows  # noqa: E402  (tools/mixed_rows.py: the script's own directory)
 
 RATIOS = (1, 2, 4, 8, 16, 32, 64)
 
@@ -76,8 +77,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5, help="warm-up calls per kind (1 for a kind slower than 0.1 s a call)")
     ap.add_argument("--full-only", action="store_true", help="time the repeated full call alone")
     ap.add_argument("--dtype", default="f64", choices=("f32", "f64"), help="the masked plans' value type")
+    ap.add_argument("--accum", default=None, choices=("f64",), help="with --dtype f32: FP64 sums (mixed plans); the check is "
+                    "then 1.01 (2^-24 |ref| + 2 m 2^-53 S) against the FP64 plan, 1.01 m 2^-24 S on global-class rows")
     args = ap.parse_args()
     f32 = args.dtype == "f32"
+    mixed = args.accum == "f64"
+    if mixed and not f32:
+        ap.error("--accum f64 goes with --dtype f32")
 
     dev = 0
     torch.cuda.set_device(dev)
@@ -94,7 +100,7 @@ def main():
         torch.cuda.synchronize(dev)
 
     out = {"workload": args.workload, "source": source, "M": A.M, "nnzA": A.nnz, "products": int(flop),
-           "blocks": args.blocks, "lib": L.lib_path(), "dtype": args.dtype}
+           "blocks": args.blocks, "lib": L.lib_path(), "dtype": args.dtype, "accum": args.accum}
     C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
     out["nnzC"] = C.nnz
     print(f"{args.workload}: nnz(A) {A.nnz}, {flop} products, nnz(C) {C.nnz}", file=sys.stderr, flush=True)
@@ -129,7 +135,8 @@ def main():
                 os.environ.pop("MHS_VAL_DOT_RATIO", None)
             else:
                 os.environ["MHS_VAL_DOT_RATIO"] = str(ratio)  # read by the library at plan creation
-            plan = mhspgemm.ValuesPlan(tool, A, A, mask, masked=True, form=form, dtype="float32" if f32 else "float64")
+            plan = mhspgemm.ValuesPlan(tool, A, A, mask, masked=True, form=form, dtype="float32" if f32 else "float64",
+                                       **({"accum": "float64"} if mixed else {}))
             info = plan.info()
             if f32:
                 res32.fill_(float("nan"))
@@ -137,7 +144,13 @@ def main():
                 plan.run(a32, a32, out=res32)
                 sync()
                 assert not torch.isnan(res32).any().item(), f"{name}: an entry was not written"
-                assert torch.all((res32.double() - ref).abs() <= 1.01 * cnt * 2.0 ** -24 * sab).item(), f"{name}: outside m 2^-24 S"
+                bound = 1.01 * cnt * 2.0 ** -24 * sab
+                if mixed:  # (a dot row that the product-form rule would send to the global class keeps the looser bound)
+                    rows = mixed_global_rows(A.ptr, A.col, 1)
+                    assert int(rows.sum()) >= info["global"]
+                    glob = torch.from_numpy(np.repeat(rows, np.diff(A.ptr))).to(f"cuda:{dev}")
+                    bound = torch.where(glob, bound, 1.01 * (2.0 ** -24 * ref.abs() + 2 * cnt * 2.0 ** -53 * sab))
+                assert torch.all((res32.double() - ref).abs() <= bound).item(), f"{name}: outside its bound"
                 assert torch.all(res32[cnt == 0] == 0).item(), f"{name}: an unreached mask entry is not 0.0"
             else:
                 res = torch.full((A.nnz,), float("nan"), dtype=torch.float64, device=f"cuda:{dev}")
@@ -156,6 +169,9 @@ def main():
         if f32:
             out["checked"] = ("every plan against an FP64 masked plan on the same rounded values: every entry within "
                               "1.01 m 2^-24 S, misses exactly 0.0")
+        if mixed:
+            out["checked"] = ("every plan against an FP64 masked plan on the same rounded values: every entry within "
+                              "1.01 (2^-24 |ref| + 2 m 2^-53 S), global-class rows within 1.01 m 2^-24 S, misses exactly 0.0")
 
     # ---- timing
     tool.set_option(L.MHS_OPT_SYNC, 0)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """values_bench.py -- the repeated full call against the values-only call, one config per run.
 
-    python tools/values_bench.py [--config cant] [--blocks 5] [--window 0.4] [--full-only] [--dtype f32|f64]
+    python tools/values_bench.py [--config cant] [--blocks 5] [--window 0.4] [--full-only] [--dtype f32|f64] [--accum f64]
                                  [--semiring plus_times|min_plus|max_plus|max_min]
 
 (a) the repeated full call, timed as bench.py times its steps: mhs_spgemm on one pair of
@@ -20,6 +20,13 @@ as faster only when it is below (a) by more than the larger spread.
 --dtype f32 runs (b) through an FP32 plan on float32 values.  Its check is then against an FP64 plan on the same
 rounded values: every entry within 1.01 m 2^-24 S, m and S from the FP64 plan on all-ones and on absolute
 values; the FP64 plan's rows by class are reported beside the FP32 plan's (`classes_f64`).
+
+--accum f64 with --dtype f32 runs (b) through a mixed plan: float32 values, FP64 sums (ValuesPlan(..., accum="float64")).
+Its check is against the FP64 plan on the same rounded values too, at the mixed plan's bound: with E the exact sum the
+mixed entry is within 2^-24 |E| + m 2^-53 S (1 + 2^-24) of it and the FP64 one within m 2^-53 S, so every entry is
+within 1.01 (2^-24 |ref| + 2 m 2^-53 S) of the FP64 plan's; the entries of global-class rows (more than 13,312 entries
+over more than 19,968 columns: C's float segment is their accumulator) within the FP32 bound.  The mixed plan's rows by
+class (`classes`) are the FP64 plan's (`classes_f64`), which the run asserts.
 
 --semiring NAME (default plus_times) runs (b) through a plan of that semiring, of either --dtype, on the same
 values.  Its check is then an equality: every entry against a sequential reduce of the products in the plan's
@@ -48,6 +55,7 @@ import torch  # noqa: E402
 import mhspgemm  # noqa: E402
 from mhspgemm import _lib as L  # noqa: E402
 from mhspgemm import synth  # noqa: E402
+from mixed_rows import mixed_global_rows  # noqa: E402  (tools/mixed_rows.py: the script's own directory)
 
 
 def semiring_reference(name, A, Cptr, Ccol, av, bv, chunk=1 << 24):
@@ -86,11 +94,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--full-only", action="store_true", help="time the repeated full call alone")
     ap.add_argument("--dtype", default="f64", choices=("f32", "f64"), help="the values plan's value type")
+    ap.add_argument("--accum", default=None, choices=("f64",), help="with --dtype f32: FP64 sums (a mixed plan)")
     ap.add_argument("--semiring", default="plus_times", choices=tuple(getattr(mhspgemm.core, "SEMIRINGS", {"plus_times": 0})),
                     help="the values plan's semiring")
     args = ap.parse_args()
     f32 = args.dtype == "f32"
     semiring = args.semiring != "plus_times"
+    mixed = args.accum == "f64"
+    if mixed and (not f32 or semiring):
+        ap.error("--accum f64 goes with --dtype f32 and the plus_times semiring")
 
     dev = 0
     torch.cuda.set_device(dev)
@@ -104,7 +116,7 @@ def main():
         torch.cuda.synchronize(dev)
 
     out = {"config": args.config, "source": source, "M": A.M, "nnzA": A.nnz, "flop": int(flop), "blocks": args.blocks,
-           "lib": L.lib_path(), "dtype": args.dtype, "semiring": args.semiring}
+           "lib": L.lib_path(), "dtype": args.dtype, "semiring": args.semiring, "accum": args.accum}
 
     # ---- the pattern, and (b)'s check against the full product of the same new operands
     C, _ = mhspgemm.spgemm(tool, A, A, timing=False)
@@ -130,7 +142,7 @@ def main():
             assert torch.equal(res32, semiring_reference(args.semiring, A, p0, c0, av, bv)), "not the sequential reduce"
         out["checked"] = "equal to a sequential reduce of the products in the plan's dtype (2 value sets)"
     elif not args.full_only and f32:
-        plan = mhspgemm.ValuesPlan(tool, A, A, C, dtype="float32")
+        plan = mhspgemm.ValuesPlan(tool, A, A, C, dtype="float32", **({"accum": "float64"} if mixed else {}))
         info = plan.info()
         out["classes"] = {k: info[k] for k in mhspgemm.core.VALUES_CLASSES}
         out["plan_bytes"] = info["plan_bytes"]
@@ -146,14 +158,28 @@ def main():
         i64 = plan64.info()
         out["classes_f64"] = {k: i64[k] for k in mhspgemm.core.VALUES_CLASSES}
         plan64.run(ones, ones, out=cnt)
+        glob = None
+        if mixed:  # the entries of global-class rows, by the plan header's rule at 8 sum bytes
+            assert out["classes"] == out["classes_f64"], "a mixed plan's rows by class are the FP64 plan's"
+            p0, c0, _ = C.to_host()
+            rows = mixed_global_rows(p0, c0, 1)
+            assert int(rows.sum()) == info["global"], "the global class restated"
+            glob = torch.from_numpy(np.repeat(rows, np.diff(p0))).to(f"cuda:{dev}")
         for av, bv in vals:
             plan64.run(av.double(), bv.double(), out=ref)  # (positive values: S is the reference itself)
             plan.run(av, bv, out=res32)
             sync()
             assert not torch.isnan(res32).any().item(), "an entry was not written"
-            assert torch.all((res32.double() - ref).abs() <= 1.01 * cnt * 2.0 ** -24 * ref).item(), "outside m 2^-24 S"
+            f32_bound = 1.01 * cnt * 2.0 ** -24 * ref
+            if mixed:
+                bound = torch.where(glob, f32_bound, 1.01 * (2.0 ** -24 * ref.abs() + 2 * cnt * 2.0 ** -53 * ref))
+                assert torch.all((res32.double() - ref).abs() <= bound).item(), "outside 2^-24 |ref| + 2 m 2^-53 S"
+            else:
+                assert torch.all((res32.double() - ref).abs() <= f32_bound).item(), "outside m 2^-24 S"
         plan64.close()
-        out["checked"] = "against an FP64 plan on the same rounded values: every entry within 1.01 m 2^-24 S (2 value sets)"
+        out["checked"] = ("against an FP64 plan on the same rounded values: every entry within 1.01 (2^-24 |ref| + 2 m 2^-53 S), "
+                          "global-class rows within 1.01 m 2^-24 S (2 value sets)" if mixed else
+                          "against an FP64 plan on the same rounded values: every entry within 1.01 m 2^-24 S (2 value sets)")
     elif not args.full_only:
         plan = mhspgemm.ValuesPlan(tool, A, A, C)
         info = plan.info()
