@@ -273,7 +273,7 @@ public:
     // accum: an mhs_accum (mhs_values_plan_create_accum).  MHS_ACC_F64 with MHS_F32 is a mixed plan -- float values,
     // double sums, the float overloads run it -- and is plus-times only; with MHS_F64 it is the plain FP64 plan.
     ValuesPlan(Tool& tools, const CSR& A, const CSR& B, const CSR& C, bool masked, int form, mhs_dtype dtype, int width,
-               int semiring = MHS_SR_PLUS_TIMES, int accum = MHS_ACC_NATIVE)
+               int semiring = MHS_SR_PLUS_TIMES, int accum = MHS_ACC_NATIVE, int smooth = MHS_SMOOTH_NONE)
         : ctx(tools.ctx) {
         mhs_csr a{A.M, A.N, A.nnz, A.d_ptr, A.d_col, A.d_val};
         mhs_csr b{B.M, B.N, B.nnz, B.d_ptr, B.d_col, B.d_val};
@@ -281,7 +281,11 @@ public:
         if (semiring != MHS_SR_PLUS_TIMES && width != 1) throw std::runtime_error("ValuesPlan: a semiring plan has width 1");
         if (semiring != MHS_SR_PLUS_TIMES && accum != MHS_ACC_NATIVE)
             throw std::runtime_error("ValuesPlan: a semiring plan has no sum type (accum must be MHS_ACC_NATIVE)");
-        const int rc = semiring != MHS_SR_PLUS_TIMES
+        // smooth: an mhs_smooth (mhs_values_plan_create_smooth).  MHS_SMOOTH_LSE on a min-plus or max-plus plan: its
+        // reduce is log-sum-exp, MH_spgemm_values runs it, its backward is mhs_spgemm_values_softgrad.
+        const int rc = smooth != MHS_SMOOTH_NONE
+                           ? mhs_values_plan_create_smooth(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, semiring, smooth, &plan)
+                       : semiring != MHS_SR_PLUS_TIMES
                            ? mhs_values_plan_create_semiring(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, semiring, &plan)
                        : accum != MHS_ACC_NATIVE
                            ? mhs_values_plan_create_accum(ctx, &a, &b, &c, masked ? 1 : 0, form, (int)dtype, width, accum, &plan)

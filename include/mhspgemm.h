@@ -576,6 +576,80 @@ int mhs_values_plan_create_accum(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *
 /* The plan's sum type (mhs_accum): MHS_ACC_F64 on a mixed plan only. */
 int mhs_values_plan_accum(const mhs_values_plan *plan, int *accum);
 
+/* ---- soft semiring plans: log-sum-exp min-plus and max-plus, and their gradient ---------------
+ * For the callers of the subgradient section when the product is the smoothed one: the forward algorithm of an HMM or
+ * CRF, the inner step of soft-DTW, the soft-min relaxation of a shortest-path step.  Smoothing is a sixth fixed
+ * property of a plan, beside its value type, width, mask form, semiring and sum type:
+ *   MHS_SMOOTH_NONE   mhs_values_plan_create_smooth is then exactly mhs_values_plan_create_semiring
+ *   MHS_SMOOTH_LSE    on MHS_SR_MIN_PLUS or MHS_SR_MAX_PLUS: the reduce is log-sum-exp at unit temperature
+ * MHS_SMOOTH_LSE with MHS_SR_PLUS_TIMES, MHS_SR_MAX_MIN or any other semiring, and any other smooth, return
+ * MHS_ERR_INVALID before any HIP call, with a message naming the argument.  The width is 1; masked plans of all three
+ * forms are served.  mhs_values_plan_semiring reports the semiring that was smoothed, mhs_values_plan_smooth
+ * MHS_SMOOTH_LSE on such a plan and MHS_SMOOTH_NONE on every other, mhs_values_plan_width 1.  A smoothed plan holds two
+ * LDS planes per C entry, a running max and a sum: its classes, row lists, LDS needs and both launch plans are computed
+ * at the sum bytes 2 * sizeof(value), so mhs_values_plan_info shows the rows per class of the width-2 plus-times plan
+ * of the same patterns and type.
+ * The forward runs through the existing hot calls -- mhs_spgemm_values, _f32, _batched, _batched_f32 (nb runs, as on any
+ * width-1 plan); stream, ms, MHS_OPT_SYNC and the contract of no allocation, no read-back and no synchronise are
+ * unchanged.  With v_k = fl(A(i,k) + B(k,j)), formed once in the plan's type, for the kept products of an entry:
+ *   smoothed max-plus   C = M + log sum_k exp(v_k - M),        M  = max_k v_k
+ *   smoothed min-plus   C = -(M' + log sum_k exp(-v_k - M')),   M' = max_k (-v_k)
+ *   Unit temperature only: a caller with temperature tau scales the values by 1 / tau and the result by tau.
+ *   Every duplicate entry of A or B is a product of its own, as on the hard plans; a product outside a mask is no
+ *   product.  Every entry of the C segment is written.
+ *   An entry that no kept product reaches, or all of whose products equal the identity of the hard semiring ("no edge"
+ *   everywhere), gets that identity: +Inf (min-plus), -Inf (max-plus).  An identity product beside finite ones adds
+ *   nothing.  A product equal to the opposite infinity makes the entry that infinity.  A NaN product leaves its entry
+ *   either NaN or the result of its other products, and touches no other entry.
+ *   An entry with one kept product has that product's bits.
+ *   Bound.  u = 2^-53 (FP64) or 2^-24 (FP32), E the exact result on the v_k, m the kept products of the entry,
+ *   V = max |v_k|; c_exp = 2 and c_log = 2 (FP64), c_exp = 2 and c_log = 4 (FP32): the worst error in ulps observed
+ *   for the device's exp and log / log1p on 2^20 points each (0.88 and 0.64; 1.00 and 2.33), rounded up, plus 1
+ *   (tools/ulp_probe.hip, profiles/smooth/ulp_probe.txt).
+ *     team, wave, block and dot rows:   |got - E| <= 1.01 u (|E| + 2 m + 2 c_exp + 2 c_log ln m)
+ *     global rows (rows[6] of mhs_values_plan_info says how many: the row's Cval segment is the accumulator, every
+ *     product one compare-and-swap of max + log1p(exp(-|c - v|))):
+ *                                       |got - E| <= 1.01 m u (V + ln m + 2 c_exp + 2 c_log + 1)
+ *   Dot rows have a fixed order and the same bits on every call; the other classes sum by LDS atomics in any order.
+ * The gradient, mhs_spgemm_values_softgrad, is the true gradient, in one pass; there are no ties.  Cval is the forward's
+ * result for (Aval, Bval), handed in as for the subgradient, and G = dCval.  A kept product (p, q, s) carries
+ *   w = G[s] * exp(v - Cval[s])   (max-plus)        w = G[s] * exp(Cval[s] - v)   (min-plus)
+ * -- softmax weights: the marginals -- and the same w goes to dAval[p] and to dBval[q].  An entry whose Cval[s] is not
+ * finite (identity, opposite infinity or NaN) passes nothing: exactly zero weights.  Either of dAval and dBval may be
+ * NULL, not both; Aval, Bval, Cval and dCval are always needed.  Outputs must not overlap inputs or each other.  Every
+ * entry of a requested output is written; entries no product reaches are exactly 0.  dAval is summed without atomics
+ * in a fixed order: two calls give the same bits.  dBval is summed by atomics in any order.
+ *   Bound.  For an output entry summed from m' terms w_k = G[s] exp(-+(v_k - Cval[s])), exact on the Cval handed in,
+ *   with S = sum |w_k| and D = max |v_k - Cval[s]|:  |got - exact| <= 1.01 (m' + D + 2 c_exp + 1) u S; FP32 adds
+ *   m' 2^-126 max |G|, because a subnormal weight may be flushed.
+ * The call queues, on the context's stream, one pre-step -- the zero fills of the requested outputs -- and one pass of
+ * the plan's backward launch list, the two planes holding G and Cval.  ms and MHS_OPT_SYNC as in
+ * mhs_spgemm_values_grad; with ms == NULL and MHS_OPT_SYNC 0 the call allocates nothing, reads nothing back and does
+ * not synchronise.
+ * Refused with MHS_ERR_INVALID and a message before any HIP call, writing nothing: mhs_spgemm_values_softgrad on a plan
+ * that is not smoothed (the message points at mhs_spgemm_values_subgrad or mhs_spgemm_values_grad); the subgradient and
+ * the witness entry points on a smoothed plan (a soft reduce has weights, not winners, and no witness: the message
+ * points at mhs_spgemm_values_softgrad); the four plus-times backward entry points, which refuse by semiring and name
+ * mhs_spgemm_values_softgrad when the plan is smoothed; a call of the wrong type; a plan of another device; a NULL ctx,
+ * plan or needed array; both outputs NULL.
+ * Cost on MI355X.  The forward walks the pattern twice (max, then the sum of exp): 2.1x the hard
+ * forward of the same semiring where loads and searches carry the call (scircuit-like: 0.455 against 0.217 ms in FP64),
+ * 2.3-2.4x on a masked triangle, and more than expected where LDS atomics carry it -- cant-like: 1.19 against 0.358 ms in
+ * FP64 (3.3x: one double exp per product beside the add) and 1.96 against 0.244 ms in FP32 (8.0x: the second walk's
+ * reduce is the slow LDS float add, which the hard FP32 plan never issues); on such patterns prefer an FP64 plan.  The
+ * gradient is one pass where the subgradient makes two: 0.24-0.26x the subgradient call for dAval alone, 0.46-0.77x for
+ * dBval or both, and 1.0-1.3x the plus-times backward of the same pattern and type (dAval alone: 1.1-2.0x).
+ * Additions to ABI version 10, like the entries above. */
+typedef enum mhs_smooth { MHS_SMOOTH_NONE = 0, MHS_SMOOTH_LSE = 1 } mhs_smooth;
+int mhs_values_plan_create_smooth(mhs_ctx *ctx, const mhs_csr *A, const mhs_csr *B, const mhs_csr *C,
+                                  int masked, int form, int dtype, int semiring, int smooth, mhs_values_plan **plan);
+/* Whether the plan is smoothed (mhs_smooth). */
+int mhs_values_plan_smooth(const mhs_values_plan *plan, int *smooth);
+int mhs_spgemm_values_softgrad(mhs_ctx *ctx, mhs_values_plan *plan, const double *Aval, const double *Bval,
+                               const double *Cval, const double *dCval, double *dAval, double *dBval, double *ms);
+int mhs_spgemm_values_softgrad_f32(mhs_ctx *ctx, mhs_values_plan *plan, const float *Aval, const float *Bval,
+                                   const float *Cval, const float *dCval, float *dAval, float *dBval, double *ms);
+
 /* At = A^T on the device (the reference's AAT operand: B = transpose(A),
  * src/main.cu:98-99 with AAT=1, inc/common.h:37; host transpose src/utils.cpp:20-46).
  * At->M = A->N, At->N = A->M; rows of At list their columns ascending; arrays are

@@ -596,6 +596,7 @@ hipError_t init_values_attributes() {
     if (e == hipSuccess) e = init_values_mixed_attributes();  // the mixed plans' (mhs_values_mixed.hip)
     if (e == hipSuccess) e = init_values_grad_attributes();  // their backward (mhs_values_grad.hip)
     if (e == hipSuccess) e = init_values_subgrad_attributes();  // the semiring plans' subgradient (mhs_values_subgrad.hip)
+    if (e == hipSuccess) e = init_values_smooth_attributes();  // the smoothed plans' forward and gradient (mhs_values_smooth.hip)
     return e;
 }
 

@@ -22,9 +22,14 @@
 // A plan has a sum type as well (mhs_values_plan_create_accum; ValAccum), fixed likewise: a mixed plan -- FP32 values,
 // FP64 sums -- classifies at width x 8 where its values are 4 bytes; its forward's issue passes the sum type on to
 // the kernels, and its backward is the float kernels on the launch list planned at those bytes.
-// Kernels and launchers: mhs_values.hip, mhs_values_grad.hip, mhs_values_subgrad.hip (declared in mhs_valwalk.hpp); classes,
+// A plan may be smoothed (mhs_values_plan_create_smooth; mhs_smooth.hpp), fixed likewise: a min-plus or max-plus plan
+// whose reduce is log-sum-exp.  It classifies at twice its value's bytes -- a max plane and a sum plane per C entry --
+// at width 1; the forward's issue sends it to the smoothed kernels, its backward is its gradient
+// (spgemm_values_softgrad: one pass of the backward's launch list), and the subgradient and the witness refuse it.
+// Kernels and launchers: mhs_values.hip, mhs_values_grad.hip, mhs_values_subgrad.hip, mhs_values_smooth.hip (declared in mhs_valwalk.hpp); classes,
 // launch plans, counter block and status words: mhs_valplan.hpp.
 #include "mhs_ctx.hpp"
+#include "mhs_smooth.hpp"
 #include "mhs_valwalk.hpp"
 
 #include <cstdlib>
@@ -41,6 +46,7 @@ struct mhs_values_plan {
     int width = 1;          // value sets a walk of its forward kernels sums (1, 2 or 4)
     int semiring = SR_PLUS_TIMES;  // mhs_semiring: what its forward kernels reduce the kept products with
     int accum = VAL_ACC_NATIVE;    // mhs_accum: VAL_ACC_F64 on a mixed plan (dtype MHS_F32, sums in FP64) only
+    int smooth = SMOOTH_NONE;      // mhs_smooth: SMOOTH_LSE on a min-plus or max-plus plan whose reduce is log-sum-exp
     ValPattern pat{};
     long long nnzA = 0, nnzB = 0, nnzC = 0, products = 0;
     long long kept = 0;    // products that land in C's pattern (masked plans count them; else = products)
@@ -61,8 +67,12 @@ struct mhs_values_plan {
 namespace {
 
 constexpr int dtype_bytes(int dtype) { return dtype == MHS_F32 ? VAL_VB_F32 : VAL_VB_F64; }
-// The bytes a plan classifies at: its width x the size of its sums (a mixed plan's: 8, its value's 4)
-int sum_bytes(const mhs_values_plan* p) { return val_sum_bytes(dtype_bytes(p->dtype), p->width, p->accum); }
+// The bytes a plan classifies at: its width x the size of its sums (a mixed plan's: 8, its value's 4); a smoothed
+// plan's two planes stand where a width-2 plan's two sums do
+int sum_bytes(const mhs_values_plan* p) {
+    return val_sum_bytes(dtype_bytes(p->dtype), p->width * val_smooth_planes(p->smooth), p->accum);
+}
+static_assert((int)MHS_SMOOTH_NONE == (int)SMOOTH_NONE && (int)MHS_SMOOTH_LSE == (int)SMOOTH_LSE, "mhs_smooth is ValSmooth");
 static_assert(MHS_VAL_WIDTH_MAX == VAL_WIDTH_MAX, "the header's width is the plan's");
 static_assert((int)MHS_ACC_NATIVE == (int)VAL_ACC_NATIVE && (int)MHS_ACC_F64 == (int)VAL_ACC_F64, "mhs_accum is ValAccum");
 const char* dtype_name(int dtype) { return dtype == MHS_F32 ? "FP32" : "FP64"; }
@@ -233,11 +243,20 @@ struct PlanBuild {
 // one than plus-times has width 1.
 // accum: mhs_accum (mhs_values_plan_create_accum; MHS_ACC_NATIVE for every other entry point); MHS_ACC_F64 on MHS_F64
 // is the native plan, on MHS_F32 the mixed one, which is plus-times.
+// smooth: mhs_smooth (mhs_values_plan_create_smooth; MHS_SMOOTH_NONE for every other entry point); MHS_SMOOTH_LSE needs
+// min-plus or max-plus.
 int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, bool masked, int form, int dtype,
-                       int width, int semiring, int accum, mhs_values_plan** out) {
+                       int width, int semiring, int accum, int smooth, mhs_values_plan** out) {
     if (!ctx) return MHS_ERR_INVALID;
     if (!A || !B || !C || !out) return fail(ctx, MHS_ERR_INVALID, "mhs_values_plan_create: null argument");
     *out = nullptr;
+    if (!val_smooth_ok(smooth))
+        return fail(ctx, MHS_ERR_INVALID,
+                    "mhs_values_plan_create: smooth " + std::to_string(smooth) + " is not an mhs_smooth (MHS_SMOOTH_NONE or MHS_SMOOTH_LSE)");
+    if (smooth != SMOOTH_NONE && !val_smooth_serves(semiring))
+        return fail(ctx, MHS_ERR_INVALID,
+                    "mhs_values_plan_create: smooth MHS_SMOOTH_LSE needs the semiring min_plus or max_plus, not " +
+                        (val_semiring_ok(semiring) ? std::string(val_semiring_name(semiring)) : "semiring " + std::to_string(semiring)));
     if (!val_semiring_ok(semiring))
         return fail(ctx, MHS_ERR_INVALID,
                     "mhs_values_plan_create: semiring " + std::to_string(semiring) + " is not an mhs_semiring (0 to 3)");
@@ -273,6 +292,7 @@ int values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const m
     p->width = width;
     p->semiring = semiring;
     p->accum = accum;
+    p->smooth = smooth;
     p->pat = ValPattern{A->M, A->ptr, A->col, B->ptr, B->col, C->ptr, C->col};
     p->nnzA = A->nnz, p->nnzB = B->nnz, p->nnzC = C->nnz;
     Scratch sort_tmp;  // (B^T's sort scratch: it outlives the build's last step, which syncs the stream either way)
@@ -355,7 +375,8 @@ int spgemm_values_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V* Ava
                              {p->pat.Cptr, p->pat.Ccol, Cval + b * sC}};
                 a.sA = sA, a.sB = sB, a.sC = sC;
                 a.nw = nb - b < W ? (int)(nb - b) : W;
-                issue_values(l, W, p->semiring, p->accum, a, p->trans, list, s);
+                if (p->smooth == SMOOTH_LSE) issue_values_smooth(l, p->semiring, a, p->trans, list, s);  // (W = 1)
+                else issue_values(l, W, p->semiring, p->accum, a, p->trans, list, s);
             }
         });
 }
@@ -374,7 +395,16 @@ int check_grad_semiring(mhs_ctx* ctx, const mhs_values_plan* p, const char* call
     if (p->semiring == SR_PLUS_TIMES) return MHS_OK;
     return fail(ctx, MHS_ERR_INVALID,
                 std::string(call) + ": the plan's semiring is " + val_semiring_name(p->semiring) +
-                    ": the backward is built for plus_times plans only");
+                    ": the backward is built for plus_times plans only" +
+                    (p->smooth == SMOOTH_LSE ? " (a smoothed plan's gradient is mhs_spgemm_values_softgrad)" : ""));
+}
+
+// Whether the subgradient or the witness may run on the plan: a smoothed plan would pass their semiring check
+int check_hard_reduce(mhs_ctx* ctx, const mhs_values_plan* p, const char* call, const char* what) {
+    if (p->smooth == SMOOTH_NONE) return MHS_OK;
+    return fail(ctx, MHS_ERR_INVALID,
+                std::string(call) + ": the plan is smoothed (MHS_SMOOTH_LSE on " + val_semiring_name(p->semiring) +
+                    "): a soft reduce has weights, not winners, and " + what + ": its gradient is mhs_spgemm_values_softgrad");
 }
 
 // mhs_spgemm_values_grad and mhs_spgemm_values_grad_f32
@@ -418,6 +448,7 @@ int spgemm_values_subgrad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const
         return fail(ctx, MHS_ERR_INVALID,
                     std::string(call) + ": the plan's semiring is " + val_semiring_name(p->semiring) +
                         ", which has a gradient: mhs_spgemm_values_grad (the subgradient serves min_plus, max_plus and max_min)");
+    if (const int rc = check_hard_reduce(ctx, p, call, "no subgradient")) return rc;
     if (!Aval || !Bval || !Cval || !dCval || !ties)
         return fail(ctx, MHS_ERR_INVALID,
                     std::string(call) + ": null Aval, Bval, Cval, dCval or ties (the winner test reads both operands)");
@@ -455,6 +486,7 @@ int spgemm_values_witness(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const
         return fail(ctx, MHS_ERR_INVALID,
                     std::string(call) + ": the plan's semiring is " + val_semiring_name(p->semiring) +
                         ": a sum has no witness (the witness serves min_plus, max_plus and max_min)");
+    if (const int rc = check_hard_reduce(ctx, p, call, "no witness")) return rc;
     if (!Aval || !Bval || !Cval || !wit)
         return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null Aval, Bval, Cval or wit (the winner test reads both operands)");
     if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
@@ -467,6 +499,37 @@ int spgemm_values_witness(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const
             return (int)MHS_OK;
         },
         [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_subgrad(l, p->semiring, 3, a, list, s); });
+}
+
+// mhs_spgemm_values_softgrad and mhs_spgemm_values_softgrad_f32: the gradient of a smoothed plan (the rule:
+// include/mhspgemm.h).  One pre-step -- the zero fills of the requested outputs -- then the backward's launch list once.
+template <class V>
+int spgemm_values_softgrad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V* Bval, const V* Cval, const V* dCval, V* dAval,
+                           V* dBval, double* ms, const char* call) {
+    if (!ctx) return MHS_ERR_INVALID;
+    if (!p) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null plan");
+    if (const int rc = check_dtype<V>(ctx, p, call)) return rc;
+    if (p->smooth != SMOOTH_LSE)
+        return fail(ctx, MHS_ERR_INVALID,
+                    std::string(call) + ": the plan is not smoothed (its semiring is " + val_semiring_name(p->semiring) + "): " +
+                        (p->semiring == SR_PLUS_TIMES ? "its backward is mhs_spgemm_values_grad"
+                                                      : "its backward is mhs_spgemm_values_subgrad") +
+                        " (the soft gradient serves plans of mhs_values_plan_create_smooth)");
+    if (!Aval || !Bval || !Cval || !dCval)
+        return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": null Aval, Bval, Cval or dCval (every weight reads both operands)");
+    if (!dAval && !dBval) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": no output (dAval and dBval are both null)");
+    if (p->device != ctx->device) return fail(ctx, MHS_ERR_INVALID, std::string(call) + ": the plan belongs to another device");
+    const ValSoftArgs<V> a{{p->pat.Aptr, p->pat.Acol, Aval}, {p->pat.Bptr, p->pat.Bcol, Bval}, {p->pat.Cptr, p->pat.Ccol, Cval},
+                           dCval, dAval, dBval, V(0)};
+    return run_values(
+        ctx, p, p->gplan, ms,
+        [&](hipStream_t s) {
+            // dB is summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
+            if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(V) * (size_t)p->nnzA, s));
+            if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(V) * (size_t)p->nnzB, s));
+            return (int)MHS_OK;
+        },
+        [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_softgrad(l, p->semiring, a, list, s); });
 }
 
 // Zero fill of nb segments of n values, `stride` elements apart, as one call: a plain fill where the segments
@@ -534,35 +597,50 @@ int spgemm_values_grad_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V
 }  // namespace
 
 int mhs_values_plan_create(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1, MHS_SR_PLUS_TIMES, MHS_ACC_NATIVE, out);
+    return values_plan_create(ctx, A, B, C, false, MHS_MASK_PRODUCT, MHS_F64, 1, MHS_SR_PLUS_TIMES, MHS_ACC_NATIVE,
+                              MHS_SMOOTH_NONE, out);
 }
 
 int mhs_values_plan_create_masked(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int form,
                                   mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, 1, MHS_SR_PLUS_TIMES, MHS_ACC_NATIVE, out);
+    return values_plan_create(ctx, A, B, C, true, form, MHS_F64, 1, MHS_SR_PLUS_TIMES, MHS_ACC_NATIVE, MHS_SMOOTH_NONE,
+                              out);
 }
 
 int mhs_values_plan_create_typed(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                  int dtype, mhs_values_plan** out) {
     return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, MHS_SR_PLUS_TIMES,
-                              MHS_ACC_NATIVE, out);
+                              MHS_ACC_NATIVE, MHS_SMOOTH_NONE, out);
 }
 
 int mhs_values_plan_create_batched(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                    int dtype, int width, mhs_values_plan** out) {
     return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, width, MHS_SR_PLUS_TIMES,
-                              MHS_ACC_NATIVE, out);
+                              MHS_ACC_NATIVE, MHS_SMOOTH_NONE, out);
 }
 
 int mhs_values_plan_create_semiring(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                     int dtype, int semiring, mhs_values_plan** out) {
-    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, semiring, MHS_ACC_NATIVE, out);
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, semiring, MHS_ACC_NATIVE,
+                              MHS_SMOOTH_NONE, out);
 }
 
 int mhs_values_plan_create_accum(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
                                  int dtype, int width, int accum, mhs_values_plan** out) {
     return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, width, MHS_SR_PLUS_TIMES,
-                              accum, out);
+                              accum, MHS_SMOOTH_NONE, out);
+}
+
+int mhs_values_plan_create_smooth(mhs_ctx* ctx, const mhs_csr* A, const mhs_csr* B, const mhs_csr* C, int masked, int form,
+                                  int dtype, int semiring, int smooth, mhs_values_plan** out) {
+    return values_plan_create(ctx, A, B, C, masked != 0, masked ? form : (int)MHS_MASK_PRODUCT, dtype, 1, semiring, MHS_ACC_NATIVE,
+                              smooth, out);
+}
+
+int mhs_values_plan_smooth(const mhs_values_plan* p, int* smooth) {
+    if (!p || !smooth) return MHS_ERR_INVALID;
+    *smooth = p->smooth;
+    return MHS_OK;
 }
 
 int mhs_values_plan_accum(const mhs_values_plan* p, int* accum) {
@@ -646,6 +724,16 @@ int mhs_spgemm_values_subgrad(mhs_ctx* ctx, mhs_values_plan* p, const double* Av
 int mhs_spgemm_values_subgrad_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, const float* Cval,
                                   const float* dCval, int32_t* ties, float* dAval, float* dBval, double* ms) {
     return spgemm_values_subgrad<float>(ctx, p, Aval, Bval, Cval, dCval, ties, dAval, dBval, ms, "mhs_spgemm_values_subgrad_f32");
+}
+
+int mhs_spgemm_values_softgrad(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* Cval,
+                               const double* dCval, double* dAval, double* dBval, double* ms) {
+    return spgemm_values_softgrad<double>(ctx, p, Aval, Bval, Cval, dCval, dAval, dBval, ms, "mhs_spgemm_values_softgrad");
+}
+
+int mhs_spgemm_values_softgrad_f32(mhs_ctx* ctx, mhs_values_plan* p, const float* Aval, const float* Bval, const float* Cval,
+                                   const float* dCval, float* dAval, float* dBval, double* ms) {
+    return spgemm_values_softgrad<float>(ctx, p, Aval, Bval, Cval, dCval, dAval, dBval, ms, "mhs_spgemm_values_softgrad_f32");
 }
 
 int mhs_spgemm_values_witness(mhs_ctx* ctx, mhs_values_plan* p, const double* Aval, const double* Bval, const double* Cval,

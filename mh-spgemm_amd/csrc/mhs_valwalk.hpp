@@ -122,6 +122,28 @@ struct ValSubArgs {
 template <class V>
 void issue_values_subgrad(const ValLaunch& l, int semiring, int pass, const ValSubArgs<V>& a, const int* list, hipStream_t s);
 hipError_t init_values_subgrad_attributes();  // (called by init_values_attributes)
+// The smoothed plans' (mhs_values_plan_create_smooth, a min-plus or max-plus plan whose reduce is log-sum-exp;
+// mhs_values_smooth.hip).  One launch of such a plan's forward (plan_values at twice the value's bytes: a max plane and
+// a sum plane per C entry, laid out as a width-2 plan's) over its class's row list, on `s`; `semiring` is SR_MIN_PLUS
+// or SR_MAX_PLUS (another: nothing is launched), t is read by VK_DOT only, a.nw is 1.
+template <class V>
+void issue_values_smooth(const ValLaunch& l, int semiring, const ValArgs<V>& a, const ValTrans& t, const int* list, hipStream_t s);
+// Its gradient's (mhs_spgemm_values_softgrad).  C.val is Cval, the forward's result for (A.val, B.val); G the cotangent
+// on C's pattern; dA / dB: the gradients, zero-filled by the caller, either nullptr (that side is not computed); both
+// operands are read always.  sg: the sign of the plan's products (val_smooth_sign), set by issue_values_softgrad.
+template <class V>
+struct ValSoftArgs {
+    using Value = V;
+    ValCsr<const V> A, B, C;
+    const V* G;
+    V *dA, *dB;
+    V sg;
+};
+// One launch of the gradient over its class's row list, on `s`: a launch of the plan's backward list (plan_grad at
+// twice the value's bytes), the two planes holding G and Cval.
+template <class V>
+void issue_values_softgrad(const ValLaunch& l, int semiring, const ValSoftArgs<V>& a, const int* list, hipStream_t s);
+hipError_t init_values_smooth_attributes();  // (called by init_values_attributes)
 
 // -------------------------------------------------------- device helpers ---
 // Ordering point for LDS traffic between lanes of one wave (a wave's LDS operations are

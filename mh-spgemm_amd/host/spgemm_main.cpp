@@ -2,7 +2,7 @@
 // on top of the C-ABI, printing the reference's stdout lines.
 //
 //   spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--acc64]
-//          [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] <file.mtx>
+//          [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] [--smooth lse] [--softgrad N] <file.mtx>
 //
 // Flow as in the reference: read (mmio semantics), reject non-square A unless AAT
 // (exit 0, main.cu:92-96), B = A or B = A^T (AAT and not symmetric, :98-101),
@@ -88,6 +88,17 @@
 //             none: "values NAME witness pass" / "masked NAME witness pass" ("... NAME f32 witness pass"), or "error".
 //             Without --semiring, with plus_times, without --reuse or --masked, or N < 1: the usage message.  Without
 //             the switch nothing is added to the output.
+//   --smooth lse  a modifier of --semiring min_plus | max_plus with --reuse or --masked: after the semiring lines, each
+//             chosen mode once more on a smoothed plan of that semiring (mhs_values_plan_create_smooth: the reduce is
+//             log-sum-exp), on seeded values uniform in [-8, 8): one more line per mode and type with the median time,
+//             and with --check the result against a sequential host loop in long double at the header's bounds:
+//             "values NAME lse pass" / "masked NAME lse pass" ("... NAME f32 lse pass"), or "error".  With another
+//             semiring, without one, or with another word than lse: the usage message.
+//   --softgrad N  a modifier of --smooth lse: after each lse line, N gradient calls (mhs_spgemm_values_softgrad / _f32,
+//             both gradients) on the same plan and values, with seeded cotangents in [0.1, 1): one more line with the
+//             median time, and with --check each gradient entry against the long-double sum of its exact weights on
+//             the device's Cval, at the header's bound: "values NAME softgrad pass" / "masked NAME softgrad pass"
+//             ("... NAME f32 softgrad pass"), or "error".  Without --smooth or N < 1: the usage message.
 // Differences: W untimed warm-up calls (the reference warms the GPU with an
 // empty kernel, MH_spgemm.cuh:10-25), K timed calls averaged with the context's
 // workspace reused between them (the reference's iter/release loop), and an extra
@@ -612,6 +623,124 @@ static void run_witness(Tool& tools, const CSR& A, const CSR& B, const CSR& P, b
     }
 }
 
+// ---- --smooth lse [--softgrad N]: a min-plus or max-plus values mode once more on a smoothed plan
+// (mhs_values_plan_create_smooth), and its gradient (mhs_spgemm_values_softgrad / _f32), in T
+static int softgrad_call(mhs_shim::ValuesPlan& p, const double* a, const double* b, const double* c, const double* g, double* da,
+                         double* db) {
+    return mhs_spgemm_values_softgrad(p.ctx, p.plan, a, b, c, g, da, db, &p.last_ms);
+}
+static int softgrad_call(mhs_shim::ValuesPlan& p, const float* a, const float* b, const float* c, const float* g, float* da,
+                         float* db) {
+    return mhs_spgemm_values_softgrad_f32(p.ctx, p.plan, a, b, c, g, da, db, &p.last_ms);
+}
+// One smoothed plan of semiring sr (min_plus or max_plus) for A * B on P's pattern (masked: a mask): seeded values
+// uniform in [-8, 8) and seeded cotangents in [0.1, 1); `calls` values calls, then `grads` softgrad calls (both
+// gradients; 0: none).  check: a sequential host loop in long double over the products v = a + b formed in T, at the
+// header's bounds (include/mhspgemm.h, "soft semiring plans") -- the forward at the bound of the team, wave, block and
+// dot rows, and at the larger of that and the global rows' bound where the plan has rows of the global class (the CLI
+// does not know which rows they are); the gradient, on the Cval the device computed, at the softgrad bound.
+template <class T>
+static void run_soft(Tool& tools, const CSR& A, const CSR& B, const CSR& P, bool masked, int sr, int calls, int grads, bool check,
+                     const char* label, const char* tag) {
+    const bool f32 = sizeof(T) == sizeof(float);
+    const char* name = SEMIRING_NAMES[sr];
+    const char* stage = "lse";
+    try {
+        const size_t nA = (size_t)A.nnz, nB = (size_t)B.nnz, nC = (size_t)P.nnz;
+        unsigned long long state = 0x9e3779b97f4a7c15ULL;  // the seed
+        auto next = [&]() {
+            state = state * 6364136223846793005ULL + 1442695040888963407ULL;
+            return state >> 11;
+        };
+        auto unit = [&]() { return (double)next() / 9007199254740992.0; };
+        std::vector<T> av(nA), bv(nB), gv(nC);
+        for (T& x : av) x = (T)(16.0 * unit() - 8.0);
+        for (T& x : bv) x = (T)(16.0 * unit() - 8.0);
+        for (T& x : gv) x = (T)(0.1 + 0.9 * unit());
+        mhs_shim::ValuesPlan plan(tools, A, B, P, masked, MHS_MASK_AUTO, f32 ? MHS_F32 : MHS_F64, 1, sr, MHS_ACC_NATIVE, MHS_SMOOTH_LSE);
+        DevArr<T> da(nA), db(nB), dc(nC), dg(nC), dda(nA), ddb(nB);
+        da.put(av), db.put(bv), dg.put(gv);
+        std::vector<double> t;
+        for (int i = 0; i < calls; ++i) {
+            f32_ok(plan.ctx, semiring_call(plan, da.p, db.p, dc.p));
+            t.push_back(plan.last_ms);
+        }
+        std::printf("MH-SpGEMM %s %s lse %s median of %d calls is %.3lf ms\n", label, name, f32 ? "FP32" : "FP64", calls, median(t));
+        const long double u = f32 ? 5.9604644775390625e-8L : 1.1102230246251565e-16L, sg = sr == MHS_SR_MIN_PLUS ? -1.0L : 1.0L;
+        const long double c_exp = 2, c_log = f32 ? 4 : 2;  // (the device library's, measured: include/mhspgemm.h)
+        // every kept product in the host's order: fn(A entry, B entry, C position, the signed product formed in T)
+        auto walk = [&](auto fn) {
+            for (int i = 0; i < A.M; ++i) {
+                const int *row = P.col + P.ptr[i], *end = P.col + P.ptr[i + 1];
+                for (int k = A.ptr[i]; k < A.ptr[i + 1]; ++k)
+                    for (int j = B.ptr[A.col[k]]; j < B.ptr[A.col[k] + 1]; ++j) {
+                        const int* hit = std::lower_bound(row, end, B.col[j]);
+                        if (hit == end || *hit != B.col[j]) continue;  // (outside a mask)
+                        const T v = av[(size_t)k] + bv[(size_t)j];
+                        fn((size_t)k, (size_t)j, (size_t)(hit - P.col), sg * (long double)v);
+                    }
+            }
+        };
+        const std::vector<T> gotC = dc.get();
+        if (check) {
+            const long double ninf = -std::numeric_limits<long double>::infinity();
+            std::vector<long double> M(nC, ninf), sum(nC, 0.0L), V(nC, 0.0L);
+            std::vector<int> m(nC, 0);
+            walk([&](size_t, size_t, size_t s, long double v) { M[s] = std::max(M[s], v), V[s] = std::max(V[s], std::fabs(v)), ++m[s]; });
+            walk([&](size_t, size_t, size_t s, long double v) { sum[s] += std::exp(v - M[s]); });
+            const bool has_global = plan.info().rows[6] > 0;
+            bool ok = gotC.size() == nC;
+            for (size_t s = 0; ok && s < nC; ++s) {
+                if (m[s] == 0) {
+                    ok = (long double)gotC[s] == sg * ninf;  // the identity
+                    continue;
+                }
+                const long double E = sg * (M[s] + std::log(sum[s])), lnm = std::log((long double)m[s]);
+                long double bound = 1.01L * u * (std::fabs(E) + 2 * m[s] + 2 * c_exp + 2 * c_log * lnm);
+                if (has_global) bound = std::max(bound, 1.01L * m[s] * u * (V[s] + lnm + 2 * c_exp + 2 * c_log + 1));
+                ok = std::fabs((long double)gotC[s] - E) <= bound;
+            }
+            std::printf("%s %s%s lse %s\n", tag, name, f32 ? " f32" : "", ok ? "pass" : "error");
+        }
+        if (grads <= 0) return;
+        stage = "softgrad";
+        t.clear();
+        for (int i = 0; i < grads; ++i) {
+            f32_ok(plan.ctx, softgrad_call(plan, da.p, db.p, dc.p, dg.p, dda.p, ddb.p));
+            t.push_back(plan.last_ms);
+        }
+        std::printf("MH-SpGEMM %s %s lse gradient %s (both gradients) median of %d calls is %.3lf ms\n", label, name,
+                    f32 ? "FP32" : "FP64", grads, median(t));
+        if (check) {
+            struct Sum {
+                long double x = 0, S = 0, D = 0;
+                int m = 0;
+            };
+            std::vector<Sum> wa(nA), wb(nB);
+            auto add = [](Sum& e, long double w, long double d) { e.x += w, e.S += std::fabs(w), e.D = std::max(e.D, std::fabs(d)), ++e.m; };
+            walk([&](size_t k, size_t j, size_t s, long double v) {
+                const long double c = sg * (long double)gotC[s];
+                if (!std::isfinite(c)) return add(wa[k], 0, 0), add(wb[j], 0, 0);
+                const long double w = (long double)gv[s] * std::exp(v - c);
+                add(wa[k], w, v - c), add(wb[j], w, v - c);
+            });
+            const long double flush = f32 ? 1.1754943508222875e-38L : 0.0L;  // 2^-126 x max |G| (< 1): a subnormal weight may flush
+            auto within = [&](const std::vector<T>& got, const std::vector<Sum>& want) {
+                for (size_t i = 0; i < want.size(); ++i) {
+                    const long double d = std::fabs((long double)got[i] - want[i].x);
+                    const long double bound = 1.01L * (want[i].m + want[i].D + 2 * c_exp + 1) * u * want[i].S + want[i].m * flush;
+                    if (want[i].m == 0 ? got[i] != T(0) : !(d <= bound)) return false;
+                }
+                return true;
+            };
+            const bool ok = within(dda.get(), wa) && within(ddb.get(), wb);
+            std::printf("%s %s%s softgrad %s\n", tag, name, f32 ? " f32" : "", ok ? "pass" : "error");
+        }
+    } catch (const std::exception&) {
+        std::printf("%s %s%s %s error\n", tag, name, f32 ? " f32" : "", stage);
+    }
+}
+
 // --batch NB: NB seeded value sets in one batched call on a plan of `width`, beside NB unbatched calls on a
 // width-1 plan of the same type T; with check every set of the batched call against its reference (see the top).
 // acc64 (T = float): both plans are mixed ones (FP64 sums), checked by acc64_within on C's host pattern.
@@ -760,7 +889,8 @@ static void run_grad_batch(Tool& tools, const CSR& A, const CSR& B, const CSR& C
 }
 
 int main(int argc, char** argv) {
-    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0, semiring = -1, subgrad = 0, witness = 0;
+    int iters = 1, warmup = 1, reuse = 0, masked = 0, grad = 0, batch = 0, width = 0, semiring = -1, subgrad = 0, witness = 0, softgrad = 0;
+    bool smooth = false;
     bool has_semiring = false;
     bool aat = false, vendor = false, check = false, cache = false, f32 = false, acc64 = false;
     std::string csv;
@@ -791,17 +921,21 @@ int main(int argc, char** argv) {
         }
         else if (!std::strcmp(argv[i], "--subgrad") && i + 1 < argc) subgrad = std::atoi(argv[++i]), bad = bad || subgrad < 1;
         else if (!std::strcmp(argv[i], "--witness") && i + 1 < argc) witness = std::atoi(argv[++i]), bad = bad || witness < 1;
+        else if (!std::strcmp(argv[i], "--smooth") && i + 1 < argc) smooth = true, bad = bad || std::strcmp(argv[++i], "lse") != 0;
+        else if (!std::strcmp(argv[i], "--softgrad") && i + 1 < argc) softgrad = std::atoi(argv[++i]), bad = bad || softgrad < 1;
         else if (!filename && argv[i][0] != '-') filename = argv[i];
         else bad = true;
     }
     if (has_semiring && reuse <= 0 && masked <= 0) bad = true;  // (a modifier of --reuse and --masked)
     if ((subgrad > 0 || witness > 0) && (!has_semiring || semiring <= MHS_SR_PLUS_TIMES)) bad = true;  // (modifiers of --semiring, not plus_times)
+    if (smooth && (!has_semiring || (semiring != MHS_SR_MIN_PLUS && semiring != MHS_SR_MAX_PLUS))) bad = true;  // (of --semiring min_plus | max_plus)
+    if (softgrad > 0 && !smooth) bad = true;  // (a modifier of --smooth)
     if ((batch > 0 && reuse <= 0) || (width > 0 && batch <= 0)) bad = true;  // (modifiers of --reuse and of --batch)
     if (acc64 && !f32) bad = true;  // (a modifier of --f32)
     if (width == 0) width = MHS_VAL_WIDTH_MAX;
     if (bad || !filename || iters < 1 || warmup < 0 || reuse < 0 || masked < 0 || grad < 0) {
         std::puts("Invalid Arguments.");
-        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--acc64] [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] <Input File>");
+        std::puts("Usage:\t ./spgemm [--iters K] [--warmup W] [--aat] [--vendor] [--check] [--csv DIR] [--cache] [--reuse N] [--masked N] [--grad N] [--f32] [--acc64] [--batch NB] [--width W] [--semiring NAME] [--subgrad N] [--witness N] [--smooth lse] [--softgrad N] <Input File>");
         return -1;
     }
     const std::string matrix_name = extract_matrix_name(filename);
@@ -946,6 +1080,8 @@ int main(int argc, char** argv) {
                 if (f32) run_semiring<float>(tools, A, B, C, false, semiring, reuse, check, "values-only (pattern reused)", "values");
                 if (f32 && subgrad > 0) run_subgrad<float>(tools, A, B, C, false, semiring, subgrad, check, "values-only (pattern reused)", "values");
                 if (f32 && witness > 0) run_witness<float>(tools, A, B, C, false, semiring, witness, check, "values-only (pattern reused)", "values");
+                if (smooth) run_soft<double>(tools, A, B, C, false, semiring, reuse, softgrad, check, "values-only (pattern reused)", "values");
+                if (smooth && f32) run_soft<float>(tools, A, B, C, false, semiring, reuse, softgrad, check, "values-only (pattern reused)", "values");
             }
             if (masked > 0 && A.M == A.N) {
                 CSR mask;  // A's pattern (a plan reads no values)
@@ -956,6 +1092,8 @@ int main(int argc, char** argv) {
                 if (f32) run_semiring<float>(tools, A, B, mask, true, semiring, masked, check, "masked (A's pattern)", "masked");
                 if (f32 && subgrad > 0) run_subgrad<float>(tools, A, B, mask, true, semiring, subgrad, check, "masked (A's pattern)", "masked");
                 if (f32 && witness > 0) run_witness<float>(tools, A, B, mask, true, semiring, witness, check, "masked (A's pattern)", "masked");
+                if (smooth) run_soft<double>(tools, A, B, mask, true, semiring, masked, softgrad, check, "masked (A's pattern)", "masked");
+                if (smooth && f32) run_soft<float>(tools, A, B, mask, true, semiring, masked, softgrad, check, "masked (A's pattern)", "masked");
                 unborrow_mask(mask, owns);
             }
         }

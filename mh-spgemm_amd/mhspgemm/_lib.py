@@ -57,6 +57,9 @@ MHS_SR_PLUS_TIMES = 0
 MHS_SR_MIN_PLUS = 1
 MHS_SR_MAX_PLUS = 2
 MHS_SR_MAX_MIN = 3
+# mhs_smooth: whether a min-plus or max-plus values plan reduces by log-sum-exp
+MHS_SMOOTH_NONE = 0
+MHS_SMOOTH_LSE = 1
 
 STATUS_NAMES = {0: "MHS_OK", 1: "MHS_ERR_HIP", 2: "MHS_ERR_OOM", 3: "MHS_ERR_INVALID",
                 4: "MHS_ERR_OVERFLOW", 5: "MHS_ERR_IO"}
@@ -235,6 +238,16 @@ def lib() -> ctypes.CDLL:
         if hasattr(L, "mhs_spgemm_values_witness"):  # (semiring witnesses: a later addition to ABI 10)
             for fn in (L.mhs_spgemm_values_witness, L.mhs_spgemm_values_witness_f32):
                 fn.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(ctypes.c_double)]
+                fn.restype = c_int
+        if hasattr(L, "mhs_values_plan_create_smooth"):  # (soft semiring plans: a later addition to ABI 10)
+            L.mhs_values_plan_create_smooth.argtypes = [c_void_p, P(mhs_csr), P(mhs_csr), P(mhs_csr), c_int, c_int, c_int,
+                                                        c_int, c_int, P(c_void_p)]
+            L.mhs_values_plan_create_smooth.restype = c_int
+            L.mhs_values_plan_smooth.argtypes = [c_void_p, P(c_int)]
+            L.mhs_values_plan_smooth.restype = c_int
+            for fn in (L.mhs_spgemm_values_softgrad, L.mhs_spgemm_values_softgrad_f32):
+                fn.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               P(ctypes.c_double)]
                 fn.restype = c_int
     if hasattr(L, "mhs_ctx_fence_default_stream"):  # (a later addition to ABI 10)
         L.mhs_ctx_fence_default_stream.argtypes = [c_void_p, c_int]

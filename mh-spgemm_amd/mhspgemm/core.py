@@ -403,6 +403,19 @@ def values_accum(accum):
     return name
 
 
+SMOOTHS = {"lse": L.MHS_SMOOTH_LSE}
+
+
+def values_smooth(smooth):
+    """A values plan's ``smooth`` argument as ``None`` (the hard reduce) or ``"lse"`` (log-sum-exp).  ValueError for
+    anything else."""
+    if smooth is None:
+        return None
+    if not isinstance(smooth, str) or smooth not in SMOOTHS:
+        raise ValueError(f"smooth: None or one of {sorted(SMOOTHS)}, not {smooth!r}")
+    return smooth
+
+
 class _AccumKeyword(type):
     """``ValuesPlan(..., accum=...)``: the sum type is taken here, as a keyword only, checked, and left on the instance
     for ``__init__``, whose own signature stays as released -- ``semiring`` is its trailing argument, so positional
@@ -411,9 +424,10 @@ class _AccumKeyword(type):
     plan of native sums -- ``inspect.signature(ValuesPlan)`` does not list it, and a subclass that needs a metaclass of
     its own derives it from this one.  Once the pin may move, ``accum`` becomes an ordinary trailing parameter."""
 
-    def __call__(cls, *args, accum=None, **kw):
+    def __call__(cls, *args, accum=None, smooth=None, **kw):
         self = cls.__new__(cls)
         self.accum = values_accum(accum)
+        self.smooth = values_smooth(smooth)  # (``smooth=`` travels the same way, for the same reason)
         self.__init__(*args, **kw)
         return self
 
@@ -469,9 +483,20 @@ class ValuesPlan(metaclass=_AccumKeyword):
     ``dtype="float64"`` it is the plain float64 plan.  It is refused with another semiring than plus_times
     (``ValueError``).  ``run``, ``run_batched``, ``grad``, ``grad_batched``, ``apply`` and ``apply_batched`` serve a
     mixed plan as they serve a float32 plan.  ``accum`` is a keyword of the constructor call only, taken by the
-    metaclass and not by ``__init__`` (see ``_AccumKeyword`` for what that means for subclasses and direct calls)."""
+    metaclass and not by ``__init__`` (see ``_AccumKeyword`` for what that means for subclasses and direct calls).
+
+    ``smooth`` (``None``, the default, or ``"lse"``; mhs_values_plan_create_smooth) smooths a min_plus or max_plus plan:
+    ``C(i,j) = log sum_k exp(A(i,k) + B(k,j))`` under max_plus and its negated twin under min_plus, at unit temperature
+    (for a temperature tau scale the values by 1 / tau and the result by tau).  ``ValueError`` with another semiring or
+    with ``accum``.  Such a plan holds a max and a sum per C entry, so its rows are classified as the width-2 plus_times
+    plan's; ``run`` and ``run_batched`` serve it, its backward is ``softgrad`` (mhs_spgemm_values_softgrad: the true
+    gradient, softmax weights over the products, no ties) and ``apply_soft`` the pair as a ``torch.autograd.Function``;
+    ``subgrad``, ``apply_subgrad``, ``witness`` and ``run_arg`` raise the library's refusal on it, and ``softgrad`` and
+    ``apply_soft`` on every other plan.  ``plan.smooth`` and ``info()["smooth"]`` say ``None`` or ``"lse"``.  Like
+    ``accum`` it is a keyword of the constructor call only."""
 
     _semiring = "plus_times"
+    smooth = None
 
     def __init__(self, tool: Tool, A: CSR, B: CSR, C, masked: bool = False, form="auto", dtype="float64", width=1,
                  semiring="plus_times"):
@@ -485,8 +510,15 @@ class ValuesPlan(metaclass=_AccumKeyword):
         if semiring != "plus_times" and self.accum is not None:
             raise ValueError(f"accum: a {semiring} plan sums nothing (min and max are exact in any type): accum must be None, "
                              f"not {self.accum!r}")
+        self.smooth = getattr(self, "smooth", None)  # (the keyword ``smooth``, checked: _AccumKeyword)
+        if self.smooth is not None and semiring not in ("min_plus", "max_plus"):
+            raise ValueError(f"smooth: {self.smooth!r} smooths a min_plus or max_plus plan, not a {semiring} one")
+        if self.smooth is not None and self.accum is not None:
+            raise ValueError(f"smooth: a smoothed plan sums in its value type: accum must be None, not {self.accum!r}")
         if not hasattr(L.lib(), "mhs_values_plan_create"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no values-only entry points")
+        if self.smooth is not None and not hasattr(L.lib(), "mhs_values_plan_create_smooth"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no soft semiring entry points")
         if masked and not hasattr(L.lib(), "mhs_values_plan_create_masked"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no masked entry points")
         self.dtype_name = values_dtype_name(dtype)
@@ -514,7 +546,12 @@ class ValuesPlan(metaclass=_AccumKeyword):
         self.nnzA, self.nnzB, self.nnzC = int(a.nnz), int(b.nnz), int(c.nnz)
         self.plan = ctypes.c_void_p()
         self._pad = None
-        if semiring != "plus_times":
+        if self.smooth is not None:
+            rc = L.lib().mhs_values_plan_create_smooth(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                       int(self.masked), self.form, VALUES_DTYPES[self.dtype_name],
+                                                       SEMIRINGS[semiring], SMOOTHS[self.smooth], ctypes.byref(self.plan))
+            _check(tool.ctx, rc, "mhs_values_plan_create_smooth")
+        elif semiring != "plus_times":
             rc = L.lib().mhs_values_plan_create_semiring(tool.ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
                                                          int(self.masked), self.form, VALUES_DTYPES[self.dtype_name],
                                                          SEMIRINGS[semiring], ctypes.byref(self.plan))
@@ -781,7 +818,7 @@ class ValuesPlan(metaclass=_AccumKeyword):
         """The library's refusal of a subgradient call on a plus-times plan, before anything runs or is written."""
         if not hasattr(L.lib(), "mhs_spgemm_values_subgrad"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no semiring subgradient entry points")
-        if self._semiring == "plus_times":
+        if self._semiring == "plus_times" or self.smooth is not None:  # (a smoothed plan has a gradient: softgrad)
             call = L.lib().mhs_spgemm_values_subgrad_f32 if self.f32 else L.lib().mhs_spgemm_values_subgrad
             _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None, None, None, None), what)
 
@@ -839,11 +876,66 @@ class ValuesPlan(metaclass=_AccumKeyword):
         self._refuse_subgrad("ValuesPlan.apply_subgrad")
         return _values_subgrad_function().apply(self, Aval, Bval)
 
+    def _refuse_softgrad(self, what):
+        """The library's refusal of a soft gradient call on a plan that is not smoothed, before anything runs or is
+        written."""
+        if not hasattr(L.lib(), "mhs_spgemm_values_softgrad"):
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no soft semiring entry points")
+        if self.smooth is None:
+            call = L.lib().mhs_spgemm_values_softgrad_f32 if self.f32 else L.lib().mhs_spgemm_values_softgrad
+            _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None, None, None), what)
+
+    def softgrad(self, dC, Cval, Aval, Bval, need_A: bool = True, need_B: bool = True, out_A=None, out_B=None,
+                 timed: bool = False):
+        """The backward of ``run`` on a smoothed plan (``smooth="lse"``; mhs_spgemm_values_softgrad): for the cotangent
+        ``dC`` on C's pattern and ``Cval``, the forward's result for ``Aval`` and ``Bval`` (all device tensors of the
+        plan's dtype; all four are always needed), the gradients of ``Aval`` and ``Bval`` into ``out_A`` / ``out_B``
+        (allocated when not given).  Every kept product carries ``dC * exp(v - Cval)`` (max_plus; min_plus:
+        ``exp(Cval - v)``) -- its softmax weight -- to both operands; an entry whose ``Cval`` is not finite passes
+        nothing.  Returns ``(dA, dB)`` with None for a side not asked for, whose buffer is not touched, and
+        ``(dA, dB, ms)`` when ``timed``.  A plan that is not smoothed raises the library's refusal."""
+        if not self.plan:
+            raise MHSpGEMMError(L.MHS_ERR_INVALID, "ValuesPlan.softgrad: the plan is closed")
+        if not (need_A or need_B):
+            raise ValueError("ValuesPlan.softgrad: need_A or need_B")
+        self._refuse_softgrad("ValuesPlan.softgrad")
+        torch = _torch()
+        dev = f"cuda:{self.tool.device}"
+        # (an empty array has no address; the library wants one for every array it is given: nothing reads it)
+        if self._pad is None:
+            self._pad = torch.zeros(1, dtype=self.dtype, device=dev)
+        pad = self._pad.data_ptr()
+        gp = self._ptr(dC, self.nnzC, "dC") or pad
+        cp = self._ptr(Cval, self.nnzC, "Cval") or pad
+        av = self._ptr(Aval, self.nnzA, "Aval") or pad
+        bv = self._ptr(Bval, self.nnzB, "Bval") or pad
+        pa = pb = None
+        dA = dB = None
+        if need_A:
+            dA = torch.empty(self.nnzA, dtype=self.dtype, device=dev) if out_A is None else out_A
+            pa = self._ptr(dA, self.nnzA, "out_A") or pad
+        if need_B:
+            dB = torch.empty(self.nnzB, dtype=self.dtype, device=dev) if out_B is None else out_B
+            pb = self._ptr(dB, self.nnzB, "out_B") or pad
+        ms = ctypes.c_double(0.0)
+        name = "mhs_spgemm_values_softgrad_f32" if self.f32 else "mhs_spgemm_values_softgrad"
+        rc = getattr(L.lib(), name)(self.tool.ctx, self.plan, av, bv, cp, gp, pa, pb, ctypes.byref(ms) if timed else None)
+        _check(self.tool.ctx, rc, name)
+        return (dA, dB, float(ms.value)) if timed else (dA, dB)
+
+    def apply_soft(self, Aval, Bval):
+        """C's values on a smoothed plan as a differentiable function of ``Aval`` and ``Bval`` (a
+        ``torch.autograd.Function``): the forward is ``run`` into a fresh nnz(C) tensor, saved with both inputs, the
+        backward ``softgrad`` for the inputs that need it (once differentiable).  Both are ordered on torch's current
+        stream as in ``apply_subgrad``.  A plan that is not smoothed raises the library's refusal."""
+        self._refuse_softgrad("ValuesPlan.apply_soft")
+        return _values_soft_function().apply(self, Aval, Bval)
+
     def _refuse_witness(self, what):
         """The library's refusal of a witness call on a plus-times plan, before anything runs or is written."""
         if not hasattr(L.lib(), "mhs_spgemm_values_witness"):
             raise MHSpGEMMError(L.MHS_ERR_INVALID, "this libmhspgemm.so has no semiring witness entry points")
-        if self._semiring == "plus_times":
+        if self._semiring == "plus_times" or self.smooth is not None:  # (a soft reduce has no witness)
             call = L.lib().mhs_spgemm_values_witness_f32 if self.f32 else L.lib().mhs_spgemm_values_witness
             _check(self.tool.ctx, call(self.tool.ctx, self.plan, None, None, None, None, None), what)
 
@@ -912,7 +1004,8 @@ class ValuesPlan(metaclass=_AccumKeyword):
         kept_products: the products that land in C's pattern (all of them unless the plan is masked), dtype:
         the plan's value type by name, width: its value sets per walk, semiring: its semiring by name, and accum: its
         sum type -- ``"float64"`` on a mixed plan (float32 values summed in double), ``None`` where the sums have the
-        value type (all four as the library reports them)."""
+        value type -- and smooth: ``"lse"`` on a smoothed min_plus or max_plus plan, else ``None`` (all five as the
+        library reports them)."""
         i = L.mhs_values_info()
         _check(self.tool.ctx, L.lib().mhs_values_plan_info(self.plan, ctypes.byref(i)), "mhs_values_plan_info")
         rows = [int(x) for x in i.rows]
@@ -943,6 +1036,11 @@ class ValuesPlan(metaclass=_AccumKeyword):
             acc = ctypes.c_int(0)
             _check(self.tool.ctx, L.lib().mhs_values_plan_accum(self.plan, ctypes.byref(acc)), "mhs_values_plan_accum")
             d["accum"] = "float64" if int(acc.value) == L.MHS_ACC_F64 else None
+        d["smooth"] = None
+        if hasattr(L.lib(), "mhs_values_plan_smooth"):
+            sm = ctypes.c_int(0)
+            _check(self.tool.ctx, L.lib().mhs_values_plan_smooth(self.plan, ctypes.byref(sm)), "mhs_values_plan_smooth")
+            d["smooth"] = {v: k for k, v in SMOOTHS.items()}.get(int(sm.value))
         return d
 
     def close(self):
@@ -1027,6 +1125,42 @@ def _values_subgrad_function():
 
     _VALUES_SUBGRAD_FUNCTION = SemiringProduct
     return SemiringProduct
+
+
+_VALUES_SOFT_FUNCTION = None
+
+
+def _values_soft_function():
+    """The autograd function behind ``ValuesPlan.apply_soft`` (made on first use, as ``_values_function``)."""
+    global _VALUES_SOFT_FUNCTION
+    if _VALUES_SOFT_FUNCTION is not None:
+        return _VALUES_SOFT_FUNCTION
+    torch = _torch()
+    from torch.autograd.function import once_differentiable
+
+    class SoftSemiringProduct(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, Aval, Bval):
+            out = torch.empty(plan.nnzC, dtype=plan.dtype, device=f"cuda:{plan.tool.device}")
+            plan._ordered_on_current_stream(lambda: plan.run(Aval, Bval, out=out))
+            ctx.plan = plan
+            ctx.save_for_backward(Aval, Bval, out)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, dC):
+            Aval, Bval, Cval = ctx.saved_tensors
+            _, need_A, need_B = ctx.needs_input_grad
+            if not (need_A or need_B):
+                return None, None, None
+            plan, dC = ctx.plan, dC.contiguous()
+            dA, dB = plan._ordered_on_current_stream(
+                lambda: plan.softgrad(dC, Cval, Aval, Bval, need_A=need_A, need_B=need_B))
+            return None, dA, dB
+
+    _VALUES_SOFT_FUNCTION = SoftSemiringProduct
+    return SoftSemiringProduct
 
 
 _VALUES_BATCHED_FUNCTION = None
