@@ -407,6 +407,24 @@ int check_hard_reduce(mhs_ctx* ctx, const mhs_values_plan* p, const char* call, 
                     "): a soft reduce has weights, not winners, and " + what + ": its gradient is mhs_spgemm_values_softgrad");
 }
 
+// Zero fill of nb segments of n values, `stride` elements apart, as one call: a plain fill where the segments
+// are contiguous (or there is one), a 2-D fill -- rows of n values at a pitch of `stride` -- where padding lies
+// between them, which keeps its bytes.
+template <class V>
+hipError_t zero_sets(V* dst, long long n, long long stride, int nb, hipStream_t s) {
+    if (!dst || n <= 0) return hipSuccess;
+    if (nb == 1 || stride == n) return hipMemsetAsync(dst, 0, sizeof(V) * (size_t)n * (size_t)nb, s);
+    return hipMemset2DAsync(dst, sizeof(V) * (size_t)stride, 0, sizeof(V) * (size_t)n, (size_t)nb, s);
+}
+
+// The zero fill of a backward's wanted outputs, nb sets of each (1: the unbatched calls): dB is summed into; dA is
+// stored once per entry of a listed row, and rows without C entries are in no list.  One fill call per side.
+template <class V>
+hipError_t zero_grads(const mhs_values_plan* p, V* dAval, long long sDA, V* dBval, long long sDB, int nb, hipStream_t s) {
+    const hipError_t e = zero_sets(dAval, p->nnzA, sDA, nb, s);
+    return e == hipSuccess ? zero_sets(dBval, p->nnzB, sDB, nb, s) : e;
+}
+
 // mhs_spgemm_values_grad and mhs_spgemm_values_grad_f32
 template <class V>
 int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V* Bval, const V* dCval, V* dAval, V* dBval,
@@ -426,9 +444,7 @@ int spgemm_values_grad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const V*
     return run_values(
         ctx, p, p->gplan, ms,
         [&](hipStream_t s) {
-            // dB is summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
-            if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(V) * (size_t)p->nnzA, s));
-            if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(V) * (size_t)p->nnzB, s));
+            MHS_HIP(zero_grads(p, dAval, 0, dBval, 0, 1, s));
             return (int)MHS_OK;
         },
         [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_grad(l, 1, a, list, s); });
@@ -459,10 +475,9 @@ int spgemm_values_subgrad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, const
     return run_values(
         ctx, p, p->gplan, ms,
         [&](hipStream_t s) {
-            // ties and dB are summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
+            // ties is summed into, as dB is
             if (p->nnzC > 0) MHS_HIP(hipMemsetAsync(ties, 0, sizeof(int) * (size_t)p->nnzC, s));
-            if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(V) * (size_t)p->nnzA, s));
-            if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(V) * (size_t)p->nnzB, s));
+            MHS_HIP(zero_grads(p, dAval, 0, dBval, 0, 1, s));
             for (int i = 0; i < p->gplan.n; ++i) {  // pass 1, whole, before run_values issues pass 2
                 const ValLaunch& l = p->gplan.launch[i];
                 issue_values_subgrad(l, p->semiring, 1, a, p->lists + p->list_off[l.cls], s);
@@ -524,22 +539,10 @@ int spgemm_values_softgrad(mhs_ctx* ctx, mhs_values_plan* p, const V* Aval, cons
     return run_values(
         ctx, p, p->gplan, ms,
         [&](hipStream_t s) {
-            // dB is summed into; dA is stored once per entry of a listed row, and rows without C entries are in no list
-            if (dAval && p->nnzA > 0) MHS_HIP(hipMemsetAsync(dAval, 0, sizeof(V) * (size_t)p->nnzA, s));
-            if (dBval && p->nnzB > 0) MHS_HIP(hipMemsetAsync(dBval, 0, sizeof(V) * (size_t)p->nnzB, s));
+            MHS_HIP(zero_grads(p, dAval, 0, dBval, 0, 1, s));
             return (int)MHS_OK;
         },
         [&](const ValLaunch& l, const int* list, hipStream_t s) { issue_values_softgrad(l, p->semiring, a, list, s); });
-}
-
-// Zero fill of nb segments of n values, `stride` elements apart, as one call: a plain fill where the segments
-// are contiguous (or there is one), a 2-D fill -- rows of n values at a pitch of `stride` -- where padding lies
-// between them, which keeps its bytes.
-template <class V>
-hipError_t zero_sets(V* dst, long long n, long long stride, int nb, hipStream_t s) {
-    if (!dst || n <= 0) return hipSuccess;
-    if (nb == 1 || stride == n) return hipMemsetAsync(dst, 0, sizeof(V) * (size_t)n * (size_t)nb, s);
-    return hipMemset2DAsync(dst, sizeof(V) * (size_t)stride, 0, sizeof(V) * (size_t)n, (size_t)nb, s);
 }
 
 // mhs_spgemm_values_grad_batched / _f32: the backward of spgemm_values_batched, on a plan of any width.  Set b reads
@@ -574,9 +577,7 @@ int spgemm_values_grad_batched(mhs_ctx* ctx, mhs_values_plan* p, int nb, const V
     return run_values(
         ctx, p, p->gplan, ms,
         [&](hipStream_t s) {
-            // as in the unbatched call, over the nb segments only: one fill call per side
-            MHS_HIP(zero_sets(dAval, p->nnzA, sDA, nb, s));
-            MHS_HIP(zero_sets(dBval, p->nnzB, sDB, nb, s));
+            MHS_HIP(zero_grads(p, dAval, sDA, dBval, sDB, nb, s));  // (over the nb segments only)
             return (int)MHS_OK;
         },
         [&](const ValLaunch& l, const int* list, hipStream_t s) {

@@ -68,7 +68,7 @@ __device__ __forceinline__ void grad_store(const ValGradArgs<V>& a, int nw, bool
         }
 }
 
-// The staged walk of walk_staged (mhs_values.hip) for a wave's or a block's row, backwards.  The row's
+// The staged walk of walk_staged (mhs_valwalk.hpp) for a wave's or a block's row, backwards.  The row's
 // `lanes` lanes stage up to CH A entries; group g of ng then takes staged entries g, g + ng, ... in
 // steps all groups make together, reads its B row val_pieces(W) G-wide pieces at a time, and asks
 // look(column, gv) for the cotangents of each product (false: not in the row).  sync() publishes the

@@ -19,15 +19,15 @@
 //                        product replaces its entry c by sg * logaddexp(sg * c, v) in a compare-and-swap loop
 // exp, log and log1p are the precise ones of the device library.
 //
-// Gradient.  One pass of the plan's backward launch list, by the scheme of mhs_values_grad.hip: the two planes of the
+// Gradient.  One pass of the plan's backward launch list, the backward walk of mhs_backwalk.hpp: the two planes of the
 // row's slice hold G and sg * Cval, staged the same way; per kept product one slot lookup, two LDS reads and one exp
 // give w = G[s] * exp(v - sg * Cval[s]) (Smooth::weight: exactly 0 where Cval[s] is not finite), which feeds the
 // register sum of its A entry -- reduced across the lane group by shuffles and stored once, in a fixed order -- and goes
 // to dB[q] by one unsafeAtomicAdd.  In the direct classes the Cval plane is filled with NaN over the span, so a column
 // outside the pattern has weight 0 (the subgradient's trick).  The global form (the global class, and a masked plan's
 // dot rows) searches C.col and reads G and Cval in HBM.
+#include "mhs_backwalk.hpp"
 #include "mhs_smooth.hpp"
-#include "mhs_valwalk.hpp"
 
 #include <type_traits>
 
@@ -58,62 +58,13 @@ __device__ __forceinline__ void soft_glob(V* p, V v, V sg) {
 }
 
 // ----------------------------------------------------------------- forward ---
-// The signed products of row `row`, as walk_products of mhs_values.hip at width 1: f(column, v) per product.
-template <int G, class V, class F>
-__device__ __forceinline__ void soft_products(const ValArgs<V>& a, V sg, int row, int g, int ng, int t, F f) {
-    const int ae = a.A.ptr[row + 1];
-    for (int k = a.A.ptr[row] + g; k < ae; k += ng) {
-        const int ac = a.A.col[k];
-        const V av = a.A.val[k];
-        const int be = a.B.ptr[ac + 1];
-        for (int j = a.B.ptr[ac] + t; j < be; j += G) f(a.B.col[j], Smooth<V>::mul(sg, av, a.B.val[j]));
-    }
-}
-// ... for a wave's or a block's row, as walk_staged of mhs_values.hip at width 1: up to CH A entries staged as (B row
-// start, length, A value), each group of G lanes reading its B row VAL_PIECES G-wide pieces at a time.  pre() runs
-// once, between the first stage's loads and the sync that publishes them; the walk ends on a sync.
-template <int G, int CH, class V, class Sync, class Pre, class F>
-__device__ __forceinline__ void soft_staged(const ValArgs<V>& a, V sg, int row, int t, int lanes, ValStage<CH, V, 1>& d, Sync sync,
-                                            Pre pre, F f) {
-    constexpr int P = VAL_PIECES;
-    const int g = t / G, ng = lanes / G, tl = t % G;
-    const int ae = a.A.ptr[row + 1], a0 = a.A.ptr[row];
-    if (a0 >= ae) {
-        pre();
-        sync();
-        return;
-    }
-    for (int k0 = a0; k0 < ae; k0 += CH) {
-        const int cnt = ae - k0 < CH ? ae - k0 : CH;
-        if (t < cnt) {
-            const int ac = a.A.col[k0 + t];
-            const int bs = a.B.ptr[ac];
-            d.bs[t] = bs;
-            d.len[t] = a.B.ptr[ac + 1] - bs;
-            d.av[t] = a.A.val[k0 + t];
-        }
-        if (k0 == a0) pre();
-        sync();
-        for (int e = g; e < cnt; e += ng) {
-            const int bs = d.bs[e], len = d.len[e];
-            const V av = d.av[e];
-            for (int j = tl; j < len; j += P * G) {
-                int c[P];
-                V v[P];
-#pragma unroll
-                for (int u = 0; u < P; ++u) {
-                    const int jj = j + u * G;
-                    const bool in = jj < len;
-                    c[u] = in ? a.B.col[bs + jj] : -1;
-                    v[u] = in ? a.B.val[bs + jj] : V(0);
-                }
-#pragma unroll
-                for (int u = 0; u < P; ++u)
-                    if (c[u] >= 0) f(c[u], Smooth<V>::mul(sg, av, v[u]));
-            }
-        }
-        sync();
-    }
+// The signed products of a row are the forward's walks (walk_products and walk_staged of mhs_valwalk.hpp) at width 1
+// under max-plus, whose product is the one rounding of a + b, with the sign applied in the callback: sg * (a + b) is
+// Smooth<V>::mul(sg, a, b) to the bit, a multiplication by +-1 being exact.  f(column, v) per product.
+using MaxPlus = SrPolicy<SR_MAX_PLUS>;
+template <class V, class F>
+__device__ __forceinline__ auto soft_signed(V sg, F f) {
+    return [=](int c, const ValSums<V, 1>& p) { f(c, sg * p.x[0]); };
 }
 
 // One row of a wave or block class in the row frame, guarded at two planes of V: steps 1 to 6 of the header.
@@ -133,8 +84,8 @@ __device__ __forceinline__ void soft_row(const ValArgs<V>& a, V sg, int row, cha
                 return find_slot(cols, n, c);
             }
         };
-        soft_staged<VAL_GROUP>(
-            a, sg, row, t, lanes, d, sync,
+        walk_staged<VAL_GROUP, 1, MaxPlus>(
+            a, row, t, lanes, d, sync,
             [&] {
                 for (int p = t; p < (DIRECT ? span : n); p += lanes) {
                     if constexpr (!DIRECT) cols[p] = a.C.col[s + p];
@@ -142,16 +93,16 @@ __device__ __forceinline__ void soft_row(const ValArgs<V>& a, V sg, int row, cha
                     sm[p] = V(0);
                 }
             },
-            [&](int c, V v) {
+            soft_signed(sg, [&](int c, V v) {
                 const int slot = slot_of(c);
                 if (slot >= 0) soft_lds_max(&mx[slot], v);
-            });
-        soft_staged<VAL_GROUP>(
-            a, sg, row, t, lanes, d, sync, [] {},
-            [&](int c, V v) {
+            }));
+        walk_staged<VAL_GROUP, 1, MaxPlus>(
+            a, row, t, lanes, d, sync, [] {},
+            soft_signed(sg, [&](int c, V v) {
                 const int slot = slot_of(c);
                 if (slot >= 0) soft_lds_add(&sm[slot], Smooth<V>::term(v, mx[slot]));
-            });
+            }));
         for (int p = t; p < n; p += lanes) {
             const int slot = DIRECT ? a.C.col[s + p] - first : p;
             a.C.val[s + p] = sg * Smooth<V>::finish(mx[slot], sm[slot]);
@@ -179,16 +130,16 @@ __global__ __launch_bounds__(256) void k_soft_team(ValArgs<V> a, V sg, const int
         }
         vwave_sync();
         if (n > 0)
-            soft_products<VAL_TEAM_LANES>(a, sg, row, 0, 1, t, [&](int c, V v) {
+            walk_products<VAL_TEAM_LANES, 1, MaxPlus>(a, row, 0, 1, t, soft_signed(sg, [&](int c, V v) {
                 const int slot = find_slot(cols, n, c);
                 if (slot >= 0) soft_lds_max(&mx[slot], v);
-            });
+            }));
         vwave_sync();
         if (n > 0)
-            soft_products<VAL_TEAM_LANES>(a, sg, row, 0, 1, t, [&](int c, V v) {
+            walk_products<VAL_TEAM_LANES, 1, MaxPlus>(a, row, 0, 1, t, soft_signed(sg, [&](int c, V v) {
                 const int slot = find_slot(cols, n, c);
                 if (slot >= 0) soft_lds_add(&sm[slot], Smooth<V>::term(v, mx[slot]));
-            });
+            }));
         vwave_sync();
         for (int p = t; p < n; p += VAL_TEAM_LANES) a.C.val[s + p] = sg * Smooth<V>::finish(mx[p], sm[p]);
         vwave_sync();
@@ -226,10 +177,10 @@ __global__ __launch_bounds__(1024) void k_soft_global(ValArgs<V> a, V sg, const 
         for (int p = t; p < n; p += 1024) a.C.val[s + p] = sg * Smooth<V>::floor();
         __threadfence();
         __syncthreads();
-        soft_products<VAL_GROUP>(a, sg, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, [&](int c, V v) {
+        walk_products<VAL_GROUP, 1, MaxPlus>(a, row, t / VAL_GROUP, 1024 / VAL_GROUP, t % VAL_GROUP, soft_signed(sg, [&](int c, V v) {
             const int slot = find_slot(a.C.col + s, n, c);
             if (slot >= 0) soft_glob(&a.C.val[s + slot], v, sg);
-        });
+        }));
     }
 }
 
@@ -299,239 +250,45 @@ struct SoftKernels {
 };
 
 // ---------------------------------------------------------------- gradient ---
-template <int G, class V>
-__device__ __forceinline__ V soft_group_sum(V v) {
-#pragma unroll
-    for (int m = G / 2; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-// One kept product: B entry q, its signed value v, its entry's cotangent g and signed result c; sum is the lane's share
-// of the A entry's gradient.
-template <class V>
-__device__ __forceinline__ void soft_product(const ValSoftArgs<V>& a, bool wa, bool wb, int q, V v, V c, V g, V& sum) {
-    const V w = Smooth<V>::weight(v, c, g);
-    if (wa) sum += w;
-    if (wb && w != V(0)) unsafeAtomicAdd(a.dB + q, w);  // global_atomic_add_f64 / _f32 (a NaN weight is added)
-}
-// The group's reduction of an A entry's gradient and its one store; every lane of the group must be here.
-template <int G, class V>
-__device__ __forceinline__ void soft_store(const ValSoftArgs<V>& a, bool on, int tl, int k, V sum) {
-    const V r = soft_group_sum<G>(sum);
-    if (on && tl == 0) a.dA[k] = r;
-}
+// The smoothed gradient's rule of the backward walk (mhs_backwalk.hpp), at width 1: two planes, G (0 outside the
+// pattern) and sg * Cval (NaN outside it: no weight); both operands are read always.
+template <class V_>
+struct SoftRule {
+    using V = V_;
+    using Args = ValSoftArgs<V>;
+    static constexpr int PLANES = 2;
+    static __device__ __forceinline__ BackWants wants(const Args& a) { return {a.dA != nullptr, a.dB != nullptr}; }
+    static __device__ __forceinline__ V staged(const Args& a, int pl, int pos) { return pl == 0 ? a.G[pos] : a.sg * a.C.val[pos]; }
+    static __device__ __forceinline__ V fill(int pl) { return pl == 0 ? V(0) : std::numeric_limits<V>::quiet_NaN(); }
 
-// grad_staged's walk (mhs_values_grad.hip) at width 1.  look(column, g, c) gives the cotangent and the signed result
-// of the product's entry (false: not in the row, or no weight).
-template <int G, int CH, class V, class Sync, class Look>
-__device__ __forceinline__ void soft_grad_staged(const ValSoftArgs<V>& a, int a0, int ae, int t, int lanes, ValStage<CH, V, 1>& d,
-                                                 Sync sync, Look look) {
-    constexpr int P = VAL_PIECES;
-    const int g = t / G, ng = lanes / G, tl = t % G;
-    const bool wa = a.dA != nullptr, wb = a.dB != nullptr;
-    for (int k0 = a0; k0 < ae; k0 += CH) {
-        const int cnt = ae - k0 < CH ? ae - k0 : CH;
-        if (t < cnt) {
-            const int ac = a.A.col[k0 + t];
-            const int bs = a.B.ptr[ac];
-            d.bs[t] = bs;
-            d.len[t] = a.B.ptr[ac + 1] - bs;
-            d.av[t] = a.A.val[k0 + t];
-        }
-        sync();
-        for (int e0 = 0; e0 < cnt; e0 += ng) {  // the same trip count in every lane of the row
-            const int e = e0 + g;
-            const bool on = e < cnt;
-            V sum = V(0);
-            if (on) {
-                const int bs = d.bs[e], len = d.len[e];
-                const V av = d.av[e];
-                for (int j = tl; j < len; j += P * G) {
-                    int c[P];
-                    V v[P];
-#pragma unroll
-                    for (int u = 0; u < P; ++u) {
-                        const int jj = j + u * G;
-                        const bool in = jj < len;
-                        c[u] = in ? a.B.col[bs + jj] : -1;
-                        v[u] = in ? a.B.val[bs + jj] : V(0);
-                    }
-#pragma unroll
-                    for (int u = 0; u < P; ++u) {
-                        V gv, cv;
-                        if (c[u] >= 0 && look(c[u], gv, cv))
-                            soft_product(a, wa, wb, bs + j + u * G, Smooth<V>::mul(a.sg, av, v[u]), cv, gv, sum);
-                    }
-                }
-            }
-            // (the group is whole again: its lanes left the B-row loop, and every group makes this step)
-            if (wa) soft_store<G>(a, on, tl, k0 + e, sum);
-        }
-        sync();
+    // One kept product: B entry q, its signed value v, its entry's cotangent g and signed result c; sum is the lane's
+    // share of the A entry's gradient.
+    static __device__ __forceinline__ void soft_product(const Args& a, BackWants f, int q, V v, V c, V g, V& sum) {
+        const V w = Smooth<V>::weight(v, c, g);
+        if (f.wa) sum += w;
+        if (f.wb && w != V(0)) unsafeAtomicAdd(a.dB + q, w);  // global_atomic_add_f64 / _f32 (a NaN weight is added)
     }
-}
-
-// One row of a wave or block class in the row frame: stage G and sg * Cval (and C.col) in the row's slice, then the walk.
-template <bool DIRECT, int CH, class V, class Sync>
-__device__ __forceinline__ void soft_grad_row(const ValSoftArgs<V>& a, int row, char* base, int region, int t, int lanes,
-                                              ValStage<CH, V, 1>& d, Sync sync) {
-    val_row<DIRECT, 2>(a, row, base, region, [&](int s, int n, int first, int span, V* g, int* cols) {
-        const int a0 = a.A.ptr[row], ae = a.A.ptr[row + 1];
-        if (a0 >= ae) return;
-        if constexpr (DIRECT) {
-            V* cv = g + span;
-            const V nan = std::numeric_limits<V>::quiet_NaN();
-            for (int p = t; p < span; p += lanes) {
-                g[p] = V(0);
-                cv[p] = nan;
-            }
-            sync();
-            for (int p = t; p < n; p += lanes) {
-                const int slot = a.C.col[s + p] - first;
-                g[slot] = a.G[s + p];
-                cv[slot] = a.sg * a.C.val[s + p];
-            }
-            soft_grad_staged<VAL_GROUP>(a, a0, ae, t, lanes, d, sync, [&](int c, V& gv, V& x) {
-                const unsigned slot = (unsigned)(c - first);
-                if (slot >= (unsigned)span) return false;
-                x = cv[slot];  // (NaN outside the pattern: no weight)
-                if (!Smooth<V>::finite(x)) return false;
-                gv = g[slot];
-                return true;
-            });
-        } else {
-            const int pitch = val_slice_entries(region, 2 * (int)sizeof(V));  // (the slice's entries, as search_slice)
-            V* cv = g + pitch;
-            for (int p = t; p < n; p += lanes) {
-                cols[p] = a.C.col[s + p];
-                g[p] = a.G[s + p];
-                cv[p] = a.sg * a.C.val[s + p];
-            }
-            soft_grad_staged<VAL_GROUP>(a, a0, ae, t, lanes, d, sync, [&](int c, V& gv, V& x) {
-                const int slot = find_slot(cols, n, c);
-                if (slot < 0) return false;
-                gv = g[slot];
-                x = cv[slot];
-                return true;
-            });
-        }
-    });
-}
-
-// Team class: VAL_TEAM_LANES lanes per row, the teams of a wave in step; a team's lanes are the group of each of its
-// A entries.
-template <class V>
-__global__ __launch_bounds__(256) void k_softgrad_team(ValSoftArgs<V> a, const int* __restrict__ list, int count, int region) {
-    extern __shared__ __align__(16) char lds[];
-    const int team = threadIdx.x / VAL_TEAM_LANES, t = threadIdx.x % VAL_TEAM_LANES;
-    const ValSlice<V> sl = search_slice<V, 2>(lds + (size_t)team * region, region);
-    V* g = sl.val;
-    V* cv = sl.val + sl.ne;
-    int* cols = sl.cols;
-    const bool wa = a.dA != nullptr, wb = a.dB != nullptr;
-    for (int base = blockIdx.x * VAL_TEAM_ROWS; base < count; base += gridDim.x * VAL_TEAM_ROWS) {
-        int s, n, a0 = 0, nA = 0;
-        const int row = val_team_row(a, list, count, base + team, sl.ne, s, n);
-        if (n > 0) {
-            a0 = a.A.ptr[row];
-            nA = a.A.ptr[row + 1] - a0;
-        }
-        for (int p = t; p < n; p += VAL_TEAM_LANES) {
-            cols[p] = a.C.col[s + p];
-            g[p] = a.G[s + p];
-            cv[p] = a.sg * a.C.val[s + p];
-        }
-        // every lane of the wave makes as many steps as its longest A row has entries
-        int steps = nA;
+    template <int P, class Row>
+    static __device__ __forceinline__ void pieces(const Args& a, BackWants f, const Row& row, int q, int, const int (&c)[P],
+                                                  const V (&v)[P], V av, V& sum) {
 #pragma unroll
-        for (int m = VAL_TEAM_LANES; m < 64; m <<= 1) {
-            const int o = __shfl_xor(steps, m);
-            steps = o > steps ? o : steps;
-        }
-        steps = __builtin_amdgcn_readfirstlane(steps);
-        vwave_sync();
-        for (int it = 0; it < steps; ++it) {
-            const bool on = it < nA;
-            V sum = V(0);
-            if (on) {
-                const int ac = a.A.col[a0 + it];
-                const V av = a.A.val[a0 + it];
-                const int be = a.B.ptr[ac + 1];
-                for (int j = a.B.ptr[ac] + t; j < be; j += VAL_TEAM_LANES) {
-                    const int slot = find_slot(cols, n, a.B.col[j]);
-                    if (slot >= 0) soft_product(a, wa, wb, j, Smooth<V>::mul(a.sg, av, a.B.val[j]), cv[slot], g[slot], sum);
-                }
-            }
-            if (wa) soft_store<VAL_TEAM_LANES>(a, on, t, a0 + it, sum);
-        }
-        vwave_sync();
-    }
-}
-
-// Wave classes: one wave64 per row, WPB rows per block.
-template <class V, bool DIRECT>
-__global__ __launch_bounds__(256) void k_softgrad_wave(ValSoftArgs<V> a, const int* __restrict__ list, int count, int region) {
-    extern __shared__ __align__(16) char lds[];
-    __shared__ ValStage<64, V, 1> stage[WPB];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    auto sync = [] { vwave_sync(); };
-    for (int idx = blockIdx.x * WPB + wave; idx < count; idx += gridDim.x * WPB)
-        soft_grad_row<DIRECT>(a, list[idx], lds + (size_t)wave * region, region, lane, 64, stage[wave], sync);
-}
-
-// Block classes: one block of T threads per row, the forward's split of the list over the XCDs.
-template <class V, int T, bool DIRECT>
-__global__ __launch_bounds__(T) void k_softgrad_block(ValSoftArgs<V> a, const int* __restrict__ list, int count, int region) {
-    extern __shared__ __align__(16) char lds[];
-    __shared__ ValStage<VAL_STAGE, V, 1> stage;
-    auto sync = [] { __syncthreads(); };
-    const XcdStretch x = xcd_stretch(count);
-    for (int idx = x.begin; idx < x.end; idx += x.step) soft_grad_row<DIRECT>(a, list[idx], lds, region, threadIdx.x, T, stage, sync);
-}
-
-// Global form, as k_grad_global: LANES lanes per row (1024: a block per row of the global class; 64: a wave per row,
-// the dot rows of a masked plan).  C.col is searched, G and Cval read in HBM; nothing is staged.
-template <class V, int LANES>
-__global__ __launch_bounds__(LANES < 256 ? 256 : LANES) void k_softgrad_global(ValSoftArgs<V> a, const int* __restrict__ list,
-                                                                               int count) {
-    constexpr int THREADS = LANES < 256 ? 256 : LANES, ROWS = THREADS / LANES, NG = LANES / VAL_GROUP;
-    const int t = threadIdx.x % LANES, g = t / VAL_GROUP, tl = t % VAL_GROUP;
-    const bool wa = a.dA != nullptr, wb = a.dB != nullptr;
-    for (int idx = blockIdx.x * ROWS + threadIdx.x / LANES; idx < count; idx += gridDim.x * ROWS) {
-        const int row = list[idx];
-        const int s = a.C.ptr[row], n = a.C.ptr[row + 1] - s;
-        if (n <= 0) continue;
-        const int a0 = a.A.ptr[row], ae = a.A.ptr[row + 1];
-        for (int k0 = a0; k0 < ae; k0 += NG) {  // the same trip count in every lane of the row
-            const int k = k0 + g;
-            const bool on = k < ae;
-            V sum = V(0);
-            if (on) {
-                const int ac = a.A.col[k];
-                const V av = a.A.val[k];
-                const int be = a.B.ptr[ac + 1];
-                for (int j = a.B.ptr[ac] + tl; j < be; j += VAL_GROUP) {
-                    const int slot = find_slot(a.C.col + s, n, a.B.col[j]);
-                    if (slot >= 0)
-                        soft_product(a, wa, wb, j, Smooth<V>::mul(a.sg, av, a.B.val[j]), a.sg * a.C.val[s + slot], a.G[s + slot], sum);
-                }
-            }
-            if (wa) soft_store<VAL_GROUP>(a, on, tl, k, sum);
+        for (int u = 0; u < P; ++u) {
+            const int slot = c[u] >= 0 ? row.slot(c[u]) : -1;
+            if (slot < 0) continue;
+            const V cv = row.at(1, slot);
+            // (direct: NaN outside the pattern, and a result that is not finite, have no weight)
+            if (Row::direct && !Smooth<V>::finite(cv)) continue;
+            soft_product(a, f, q + u * VAL_GROUP, Smooth<V>::mul(a.sg, av, v[u]), cv, row.at(0, slot), sum);
         }
     }
-}
-
-template <class V>
-struct SoftGradKernels {
-    using Fn = void (*)(ValSoftArgs<V>, const int*, int, int);
-    static Fn team() { return k_softgrad_team<V>; }
-    template <bool DIRECT>
-    static Fn wave() { return k_softgrad_wave<V, DIRECT>; }
-    template <int T, bool DIRECT>
-    static Fn block() { return k_softgrad_block<V, T, DIRECT>; }
+    template <class Src>
+    static __device__ __forceinline__ void product(const Args& a, BackWants f, int q, int, V av, const Src& src, int slot, V& sum) {
+        soft_product(a, f, q, Smooth<V>::mul(a.sg, av, a.B.val[q]), src.at(1, slot), src.at(0, slot), sum);
+    }
 };
 
-// The stages are the width-1 kernels': val_static_lds at (vb, width 1) is these kernels' static LDS, beside launches
-// planned at twice the value's bytes (tests/valplan_smooth_check.cpp sums the two)
+// The forward's stages are the width-1 kernels': val_static_lds at (vb, width 1) is these kernels' static LDS, beside
+// launches planned at twice the value's bytes (tests/valplan_smooth_check.cpp sums the two)
 template <class V>
 constexpr bool soft_static_lds_holds() {
     return sizeof(ValStage<64, V, 1>[WPB]) == val_static_lds(VK_WAVE_DIRECT, sizeof(V), 1) &&
@@ -539,13 +296,13 @@ constexpr bool soft_static_lds_holds() {
            sizeof(SoftDotStage<V>[WPB]) == val_static_lds(VK_DOT, sizeof(V), 1);
 }
 static_assert(soft_static_lds_holds<double>() && soft_static_lds_holds<float>(), "val_static_lds is the smoothed kernels' static LDS");
-// (at two planes no team launch is past what a launch may take unasked: only the block kernels are registered)
+// (at two planes no team launch is past what a launch may take unasked: only the forward's block kernels are registered)
 static_assert(!val_team_registers(2 * VAL_VB_F64) && !val_team_registers(2 * VAL_VB_F32), "the team kernels need no attribute");
 
 template <class V>
 hipError_t soft_register() {
     const hipError_t e = val_allow_max_lds<SoftKernels<V>>();
-    return e == hipSuccess ? val_allow_max_lds<SoftGradKernels<V>>() : e;
+    return e == hipSuccess ? back_register<SoftRule<V>>() : e;
 }
 
 }  // namespace
@@ -576,14 +333,7 @@ void issue_values_softgrad(const ValLaunch& l, int semiring, const ValSoftArgs<V
     if (!val_smooth_serves(semiring)) return;
     ValSoftArgs<V> a = args;
     a.sg = V(val_smooth_sign(semiring));
-    const dim3 g(l.grid), b(l.block);
-    if (const typename SoftGradKernels<V>::Fn k = val_lds_kernel<SoftGradKernels<V>>(l.kernel, l.block)) {
-        hipLaunchKernelGGL(k, g, b, l.lds, s, a, list, l.count, l.region);
-    } else if (l.kernel == VK_GLOBAL) {  // (plan_grad has no other kernel)
-        // 1024 threads a row for the global class, a wave a row for the dot rows
-        if (l.block == 1024) hipLaunchKernelGGL((k_softgrad_global<V, 1024>), g, b, 0, s, a, list, l.count);
-        else hipLaunchKernelGGL((k_softgrad_global<V, 64>), g, b, 0, s, a, list, l.count);
-    }
+    back_issue<SoftRule<V>>(l, a, list, s);
 }
 template void issue_values_softgrad<double>(const ValLaunch&, int, const ValSoftArgs<double>&, const int*, hipStream_t);
 template void issue_values_softgrad<float>(const ValLaunch&, int, const ValSoftArgs<float>&, const int*, hipStream_t);

@@ -1,9 +1,11 @@
-// mhs_valwalk.hpp -- what the values kernels (mhs_values.hip), their backward (mhs_values_grad.hip), the
-// semiring plans' subgradient (mhs_values_subgrad.hip) and their host side (mhs_values_api.cpp) share.  First the declarations: the argument structs and
+// mhs_valwalk.hpp -- what the values kernels (mhs_values.hip, and mhs_values_mixed.hip, which is that file once
+// more), the smoothed plans' kernels (mhs_values_smooth.hip), the three backwards (mhs_values_grad.hip,
+// mhs_values_subgrad.hip and the second half of mhs_values_smooth.hip, through mhs_backwalk.hpp, which holds their
+// walk) and the host side (mhs_values_api.cpp) share.  First the declarations: the argument structs and
 // the launchers.  Then the device helpers of the forward and the backward walk: the wave-level LDS
 // ordering point, the slot search, the XCD stretch of a block's list, the row frame (a class row's C
 // segment, guarded against the launch's LDS region), the stage of A entries that the wave and block
-// walks read their B rows from, and the kernel of a launch.
+// walks read their B rows from, the forward's walk over a row's products, and the kernel of a launch.
 #pragma once
 #include "mhs_internal.hpp"
 #include "mhs_semiring.hpp"
@@ -286,6 +288,107 @@ constexpr int VAL_PIECES = 8;  // G-wide pieces of a B row a lane group loads be
 // ... of a walk of W sets: W values a piece, so the values in flight (and their registers) stay VAL_PIECES
 constexpr int val_pieces(int W) { return VAL_PIECES / W; }
 static_assert(val_pieces(1) == VAL_PIECES && val_pieces(VAL_WIDTH_MAX) >= 1, "W = 1 keeps its pieces; the widest walk has one");
+
+// ----------------------------------------------------------- forward walk ---
+// The products of row `row`: group g of ng groups takes A entries g, g + ng, ...; its G lanes
+// stride over the B row.  add(column, value) per product.
+// W: the plan's width.  The pattern work of a product -- the B column and, in add, its slot -- is done
+// once, the value work for each of the pass's sets: add(column, sums) with sums.x[w] the product of set
+// w < val_nw (set w's values lie w strides on: ValArgs); the x of a set the pass has not is not set.
+template <int W, class V>
+__device__ __forceinline__ int val_nw(const ValArgs<V>& a) {
+    return W == 1 ? 1 : a.nw;
+}
+template <int G, int W, class S = PlusTimes, class Acc = void, class V, class F>
+__device__ __forceinline__ void walk_products(const ValArgs<V>& a, int row, int g, int ng, int t, F add) {
+    using Sum = typename ValAccOf<Acc, ValArgs<V>>::type;
+    const int nw = val_nw<W>(a);
+    const int ae = a.A.ptr[row + 1];
+    for (int k = a.A.ptr[row] + g; k < ae; k += ng) {
+        const int ac = a.A.col[k];
+        V av[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            if (w < nw) av[w] = a.A.val[(long long)w * a.sA + k];
+        const int be = a.B.ptr[ac + 1];
+        for (int j = a.B.ptr[ac] + t; j < be; j += G) {
+            const int c = a.B.col[j];
+            ValSums<Sum, W> p;
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+                if (w < nw) p.x[w] = S::mul(Sum(av[w]), Sum(a.B.val[(long long)w * a.sB + j]));
+            add(c, p);
+        }
+    }
+}
+// The same products for a wave's or a block's row, with memory-level parallelism: the row's `lanes`
+// lanes first stage up to CH of its A entries as (B row start, length, A value) in LDS -- one
+// dependent load chain (A.col -> B.ptr) per CH entries, not one per entry -- then each group of G
+// lanes takes staged entries g, g + ng, ... and reads its B row VAL_PIECES G-wide pieces at a time,
+// every load issued before the first sum.  pre() runs once, between the first stage's loads and the
+// sync that publishes them (the row's zero fill rides on that sync).
+// W > 1: the stage holds no A value (ValStage); a group reads each set's at the entry's A position, and
+// val_pieces(W) pieces of W values each are in flight.
+template <int G, int W, class S = PlusTimes, class Acc = void, int CH, class V, class Sync, class Pre, class F>
+__device__ __forceinline__ void walk_staged(const ValArgs<V>& a, int row, int t, int lanes, ValStage<CH, V, W>& d, Sync sync,
+                                            Pre pre, F add) {
+    using Sum = typename ValAccOf<Acc, ValArgs<V>>::type;
+    constexpr int P = val_pieces(W);
+    const int nw = val_nw<W>(a);
+    const int g = t / G, ng = lanes / G, tl = t % G;
+    const int ae = a.A.ptr[row + 1], a0 = a.A.ptr[row];
+    if (a0 >= ae) {
+        pre();
+        sync();
+        return;
+    }
+    for (int k0 = a0; k0 < ae; k0 += CH) {
+        const int cnt = ae - k0 < CH ? ae - k0 : CH;
+        if (t < cnt) {
+            const int ac = a.A.col[k0 + t];
+            const int bs = a.B.ptr[ac];
+            d.bs[t] = bs;
+            d.len[t] = a.B.ptr[ac + 1] - bs;
+            if constexpr (W == 1) d.av[t] = a.A.val[k0 + t];
+        }
+        if (k0 == a0) pre();
+        sync();
+        for (int e = g; e < cnt; e += ng) {
+            const int bs = d.bs[e], len = d.len[e];
+            V av[W];
+            if constexpr (W == 1) {
+                av[0] = d.av[e];
+            } else {
+#pragma unroll
+                for (int w = 0; w < W; ++w)
+                    if (w < nw) av[w] = a.A.val[(long long)w * a.sA + (k0 + e)];
+            }
+            for (int j = tl; j < len; j += P * G) {
+                int c[P];
+                V v[P][W];
+#pragma unroll
+                for (int u = 0; u < P; ++u) {
+                    const int jj = j + u * G;
+                    const bool in = jj < len;
+                    c[u] = in ? a.B.col[bs + jj] : -1;
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        if (w < nw) v[u][w] = in ? a.B.val[(long long)w * a.sB + (bs + jj)] : V(0);
+                }
+#pragma unroll
+                for (int u = 0; u < P; ++u)
+                    if (c[u] >= 0) {
+                        ValSums<Sum, W> p;
+#pragma unroll
+                        for (int w = 0; w < W; ++w)
+                            if (w < nw) p.x[w] = S::mul(Sum(av[w]), Sum(v[u][w]));
+                        add(c[u], p);
+                    }
+            }
+        }
+        sync();
+    }
+}
 
 // ---------------------------------------------------------------- launch ---
 // The kernel of a launch over an LDS class's list, nullptr for the other kernels.  K names a direction's

@@ -1,6 +1,7 @@
 """Shared test helpers (test infrastructure)."""
 from __future__ import annotations
 
+import functools
 import json
 from pathlib import Path
 
@@ -731,3 +732,29 @@ def row_shapes(A, B, Cp, Ci):
     colspan[has] = Ci[last].astype(np.int64) - Ci[first] + 1
     return {"span": span, "t": _per_row(Cp, _new_tile(Cp, Ci)), "n": n, "flop": _per_row(Ap, np.diff(Bp)[Ac]),
             "tflop": _per_row(Ap, btiles[Ac]), "nA": np.diff(Ap), "colspan": colspan}
+
+
+@functools.lru_cache(maxsize=None)
+def many_a_entries():
+    """A with rows of 65 to 700 entries over tiny_zoo's B, the product's pattern and its kept products (expand):
+    wave rows whose A entries need more than one stage (64 entries a stage, 256 in a block), and a block's row."""
+    import mhspgemm
+    from oracle import oracle as orc
+    (_, K, _, _, _), Bt = tiny_zoo(7)
+    _, N, Bp, Bc, Bv = Bt
+    rng = np.random.default_rng(23)
+    blen = np.diff(Bp)
+    narrow = np.nonzero((np.arange(K) % 5 == 1))[0]               # B rows inside columns [0, 200): a direct span
+    wide = np.nonzero((np.arange(K) % 5 >= 2) & (blen > 0))[0]    # B rows anywhere in [0, 5000): searched
+    arows = []
+    for na in (65, 100, 150, 257, 300):
+        arows.append(np.sort(rng.choice(narrow, na, replace=False)))
+        arows.append(np.sort(rng.choice(wide, na, replace=False)))
+    arows.append(np.sort(rng.choice(wide, 700, replace=False)))    # past the wave's product cap: a block's row
+    Ap = np.zeros(len(arows) + 1, np.int64)
+    Ap[1:] = np.cumsum([len(r) for r in arows])
+    Ac = np.concatenate(arows).astype(np.int32)
+    A = mhspgemm.CSR(len(arows), K, Ap.astype(np.int32), Ac, np.ones(len(Ac)))
+    B = csr_of(Bt)
+    Cp, Ci, _ = orc.spgemm(A.ptr, A.col, A.val, B.ptr, B.col, B.val, B.N)
+    return A, B, Cp, Ci, expand(A.ptr, A.col, B.ptr, B.col, Cp, Ci, B.N)

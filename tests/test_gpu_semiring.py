@@ -18,7 +18,7 @@ import mhspgemm
 from mhspgemm import _lib
 from oracle import oracle as orc
 from _util import (GOLDEN, PRODUCT_CASES, assert_f64_bound, bin_zoo, csr_of, device_csr, exact_forward, expand, filled, keys,
-                   load_golden, random_csr, tiny_zoo)
+                   load_golden, many_a_entries, random_csr, tiny_zoo)
 
 pytestmark = pytest.mark.gpu
 
@@ -176,28 +176,6 @@ def test_semiring_every_class_has_rows(tool):
 
 
 # 3. stage boundaries: wave rows whose A entries need more than one stage (64 entries a stage, 256 in a block)
-@functools.lru_cache(maxsize=None)
-def many_a_entries():
-    (_, K, _, _, _), Bt = tiny_zoo(7)
-    _, N, Bp, Bc, Bv = Bt
-    rng = np.random.default_rng(23)
-    blen = np.diff(Bp)
-    narrow = np.nonzero((np.arange(K) % 5 == 1))[0]               # B rows inside columns [0, 200): a direct span
-    wide = np.nonzero((np.arange(K) % 5 >= 2) & (blen > 0))[0]    # B rows anywhere in [0, 5000): searched
-    arows = []
-    for na in (65, 100, 150, 257, 300):
-        arows.append(np.sort(rng.choice(narrow, na, replace=False)))
-        arows.append(np.sort(rng.choice(wide, na, replace=False)))
-    arows.append(np.sort(rng.choice(wide, 700, replace=False)))    # past the wave's product cap: a block's row
-    Ap = np.zeros(len(arows) + 1, np.int64)
-    Ap[1:] = np.cumsum([len(r) for r in arows])
-    Ac = np.concatenate(arows).astype(np.int32)
-    A = mhspgemm.CSR(len(arows), K, Ap.astype(np.int32), Ac, np.ones(len(Ac)))
-    B = csr_of(Bt)
-    Cp, Ci, _ = orc.spgemm(A.ptr, A.col, A.val, B.ptr, B.col, B.val, B.N)
-    return A, B, Cp, Ci, expand(A.ptr, A.col, B.ptr, B.col, Cp, Ci, B.N)
-
-
 @pytest.mark.parametrize("sr", SEMIRINGS)
 def test_semiring_stage_boundaries(tool, sr):
     A, B, Cp, Ci, pqs = many_a_entries()

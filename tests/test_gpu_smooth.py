@@ -23,7 +23,8 @@ import torch
 import mhspgemm
 from mhspgemm import _lib
 from oracle import oracle as orc
-from _util import GOLDEN, PRODUCT_CASES, bin_zoo, csr_of, device_csr, edge_val, expand, load_golden, random_csr, tiny_zoo
+from _util import (GOLDEN, PRODUCT_CASES, bin_zoo, csr_of, device_csr, edge_val, expand, load_golden, many_a_entries, random_csr,
+                   tiny_zoo)
 from test_gpu_values_batched import rect_mask_case, triangle_case, val_class
 
 pytestmark = pytest.mark.gpu
@@ -291,6 +292,37 @@ def test_smooth_every_class_has_rows(tool):
             rows += info["rows"]
         for cls in (TEAM, WAVE_DIRECT, WAVE_SEARCH, BLOCK_DIRECT, BLOCK_SEARCH, GLOBAL):
             assert rows[cls] > 0, f"class {cls} has no rows in bin_zoo + tiny_zoo ({dtype})"
+
+
+# A rows of 65, 257 and 700 entries (_util.many_a_entries): the staged walk of the forward and of the
+# gradient refills its stage inside a row -- past 64 entries in a wave class, past 256 in a block class -- and leaves
+# lane groups idle in the last step
+@types
+@both
+def test_smooth_stage_boundaries(tool, sr, dtype):
+    A, B, Cp, Ci, pqs = many_a_entries()
+    nA = np.diff(A.ptr)
+    assert {65, 257, 700} <= set(nA.tolist())
+    dA, dB, dC = on_device(tool, A, B, Cp, Ci)
+    av, bv = pair_values(A, B, 121, dtype)
+    G = values(len(Ci), 123, dtype, -1.0, 1.0)
+    # the class of every row at the plan's two planes, and through it the rows whose stage is refilled
+    products = np.add.reduceat(np.append(np.diff(B.ptr)[A.col], 0), A.ptr[:-1].astype(np.int64))
+    cls = np.array([val_class(int(Cp[i + 1] - Cp[i]), int(Ci[Cp[i + 1] - 1]) - int(Ci[Cp[i]]) + 1, int(products[i]), 2 * VB[dtype])
+                    for i in range(A.M)])
+    plan, info = soft_plan(tool, dA, dB, dC, sr, dtype)
+    try:
+        assert list(info["rows"]) == np.bincount(cls, minlength=len(info["rows"])).tolist(), info
+        assert (np.isin(cls, (WAVE_DIRECT, WAVE_SEARCH)) & (nA > 64)).any(), "a wave row that refills its stage"
+        assert (np.isin(cls, (BLOCK_DIRECT, BLOCK_SEARCH)) & (nA > 256)).any(), "a block row that refills its stage"
+        got = forward(tool, plan, av, bv, len(Ci), dtype)
+        assert_forward(got, soft_reference(sr, pqs, av, bv, len(Ci), dtype), np.repeat(cls == GLOBAL, np.diff(Cp)), dtype, f"stage {sr} {dtype}")
+        rA, rB = grad_reference(sr, pqs, av, bv, got, G, A.nnz, B.nnz, dtype)
+        gA, gB = backward(tool, plan, G, got, av, bv, A.nnz, B.nnz, dtype)
+        assert_grad(gA, rA, G, dtype, f"stage {sr} {dtype} dA")
+        assert_grad(gB, rB, G, dtype, f"stage {sr} {dtype} dB")
+    finally:
+        plan.close()
 
 
 # ------------------------------------------------------------------ 3. class edges ---
