@@ -6,7 +6,15 @@ repeat of a B entry contributes to dAval and gets its own dBval, and mhs_transpo
 A's order".  The inputs are the repeat twins of tests/_dups.py.  Values and cotangents are integers of +-{1, 2, 3}:
 every sum is exact in either type in any order while 9 * (products of an entry) < 2^24, which exact_sets asserts
 on the host, so every output is compared with np.array_equal against sums of the expanded products taken in
-float64; nothing here carries a tolerance.  Outputs start NaN-filled; entries no product reaches are exactly 0."""
+float64; nothing here carries a tolerance.  Outputs start NaN-filled; entries no product reaches are exactly 0.
+Mixed plans (float values summed in double) run as a third kind of plan on the same inputs, exact for the same reason.
+
+Under min-plus, max-plus and max-min "every duplicate entry is a product of its own": repeats count in ties and share
+their k in the witness.  The same twins run through the semiring plans' forward, subgradient and witness with the
+checks of tests/test_gpu_subgrad.py and test_gpu_witness.py as they are, then once more on values in which every repeat
+of a B entry copies the first of its run, where those sentences can be tested: all comparisons are np.array_equal.  The
+smoothed min-plus and max-plus plans run on the twins too, held to the header's bounds by tests/test_gpu_smooth.py's
+assert_forward and assert_grad."""
 import functools
 import re
 import subprocess
@@ -24,11 +32,17 @@ import test_gpu_values_batched as fb
 from test_gpu_values_batched import (BLOCK_DIRECT, BLOCK_SEARCH, DOT, GLOBAL, TEAM, TYPES, WAVE_DIRECT, WAVE_SEARCH, WIDE,
                                      make_plan, nans, pattern_of, up)
 from test_gpu_values_grad_batched import bits, call
+import test_gpu_semiring as srf
+import test_gpu_smooth as sm
+import test_gpu_subgrad as sub
+import test_gpu_witness as wit
 
 pytestmark = pytest.mark.gpu
 
-PLANS = [(dt, W) for dt in ("f64", "f32") for W in (1, 2, 4)]
-plans = pytest.mark.parametrize("dt,W", PLANS, ids=[f"{d}-w{w}" for d, w in PLANS])
+# (dt, W, accum): the FP64 and FP32 plans, and the mixed plans -- float values summed in double (accum "float64"), whose
+# classes are those of the sum bytes 8 W.  Integer values make a mixed plan's double sums exact as well.
+PLANS = [(dt, W, None) for dt in ("f64", "f32") for W in (1, 2, 4)] + [("f32", W, "float64") for W in (1, 2, 4)]
+plans = pytest.mark.parametrize("dt,W,accum", PLANS, ids=[f"{'mixed' if a else d}-w{w}" for d, w, a in PLANS])
 PRODUCT = (TEAM, WAVE_DIRECT, WAVE_SEARCH, BLOCK_DIRECT, BLOCK_SEARCH, GLOBAL)
 NB_MOST = 5  # W + 1 sets for the widest plan
 
@@ -134,27 +148,35 @@ CASES = {
 }
 
 
-def plain_inputs(dt, W):
+def plain_inputs(dt, W, accum=None):
     """The inputs of a plan: the twins of bin_zoo, tiny_zoo and global_rows, and wave_direct_rows, without which
     the FP64 width-4 plans have no wave-direct row.  edge_val(13313, ...) is past every plan's block-search cap but
-    the FP32 width-1 plan's, whose rows of the global class need 19,969 entries (tests/test_gpu_f64_bound.py's)."""
-    return ["bin_zoo", "tiny_zoo", "global_rows_f32" if (dt, W) == ("f32", 1) else "global_rows", "wave_direct_rows"]
+    the FP32 width-1 plan's, whose rows of the global class need 19,969 entries (tests/test_gpu_f64_bound.py's).
+    A mixed plan (accum) classifies at 8 W sum bytes: it never has the 4 of that plan."""
+    four_sum_bytes = (dt, W) == ("f32", 1) and accum is None
+    return ["bin_zoo", "tiny_zoo", "global_rows_f32" if four_sum_bytes else "global_rows", "wave_direct_rows"]
+
+
+def plan_keywords(accum):
+    """make_plan's keywords of a PLANS entry: accum reaches ValuesPlan through them, on mixed plans only."""
+    return {} if accum is None else {"accum": accum}
 
 
 _PLAIN = {}
 
 
-def plain(tool, key, dt, W):
-    if (key, dt, W) not in _PLAIN:
-        _PLAIN[key, dt, W] = check_plan(tool, key, dt, W)[0]
-    return _PLAIN[key, dt, W]
+def plain(tool, key, dt, W, accum=None):
+    if (key, dt, W, accum) not in _PLAIN:
+        _PLAIN[key, dt, W, accum] = check_plan(tool, key, dt, W, **plan_keywords(accum))[0]
+    return _PLAIN[key, dt, W, accum]
 
 
 @plans
 @pytest.mark.parametrize("which", [0, 1, 2, 3], ids=["bin_zoo", "tiny_zoo", "global_rows", "wave_direct_rows"])
-def test_repeats_plain_plan(tool, which, dt, W):
-    key = plain_inputs(dt, W)[which]
-    info = plain(tool, key, dt, W)
+def test_repeats_plain_plan(tool, which, dt, W, accum):
+    key = plain_inputs(dt, W, accum)[which]
+    info = plain(tool, key, dt, W, accum)
+    assert info["accum"] == accum and info["dtype"] == ("float64" if dt == "f64" else "float32"), info
     A, B = exact_sets(key)[:2]
     assert len(repeat_pairs(B)) > 0 and (which == 2 or len(repeat_pairs(A)) > 0), "repeats in B, and in A but for global_rows"
     if which == 3:
@@ -166,11 +188,147 @@ def test_repeats_plain_plan(tool, which, dt, W):
 
 
 @plans
-def test_repeats_plain_every_class_has_rows(tool, dt, W):
-    rows = np.sum([plain(tool, key, dt, W)["rows"] for key in plain_inputs(dt, W)], axis=0)
+def test_repeats_plain_every_class_has_rows(tool, dt, W, accum):
+    rows = np.sum([plain(tool, key, dt, W, accum)["rows"] for key in plain_inputs(dt, W, accum)], axis=0)
     for cls in PRODUCT:
-        assert rows[cls] > 0, f"class {cls} has no rows at {dt} W={W}"
+        assert rows[cls] > 0, f"class {cls} has no rows at {dt} W={W} accum={accum}"
     assert rows[DOT] == 0
+
+
+# ------------------------------------------------------------------ semiring plans ---
+INPUT_IDS = ["bin_zoo", "tiny_zoo", "global_rows", "wave_direct_rows"]
+DTYPES = {"float64": "f64", "float32": "f32"}
+
+
+@functools.lru_cache(maxsize=None)
+def semiring_input(key):
+    """A case for the semiring plans: (A, B, Cp, Ci, kept products), then what the repeats of B are -- per stored B
+    entry whether it is one of several copies and the position of the first of its run, the positions of the runs'
+    first copies, and the kept products of A times B with every run collapsed to one entry (the same C pattern)."""
+    A, B, Cp, Ci, pqs = exact_sets(key)[:5]
+    p1, c1, mult, start = split_repeats((B.M, B.N, B.ptr, B.col, B.val))
+    assert (mult > 1).any() and np.array_equal(B.col[start], c1)
+    return (A, B, Cp, Ci, pqs, np.repeat(mult > 1, mult), np.repeat(start, mult), start,
+            expand(A.ptr, A.col, p1, c1, Cp, Ci, B.N))
+
+
+_HARD = {}
+
+
+def hard_info(tool, key, dtype, sr):
+    """info() of the semiring plan of a case, from the test that ran it where it has."""
+    if (key, dtype, sr) not in _HARD:
+        A, B, Cp, Ci = semiring_input(key)[:4]
+        plan = mhspgemm.ValuesPlan(tool, *srf.on_device(tool, A, B, Cp, Ci), dtype=dtype, semiring=sr)
+        try:
+            _HARD[key, dtype, sr] = plan.info()
+        finally:
+            plan.close()
+    return _HARD[key, dtype, sr]
+
+
+@pytest.mark.parametrize("sr", srf.SEMIRINGS)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("which", [0, 1, 2, 3], ids=INPUT_IDS)
+def test_repeats_semiring_plan(tool, which, dtype, sr):
+    key = plain_inputs(DTYPES[dtype], 1)[which]
+    A, B, Cp, Ci, pqs, copied, first_copy, start, merged_pqs = semiring_input(key)
+    nC = len(Ci)
+    what = f"{key} {sr} {dtype}"
+    plan = mhspgemm.ValuesPlan(tool, *srf.on_device(tool, A, B, Cp, Ci), dtype=dtype, semiring=sr)
+    try:
+        _HARD[key, dtype, sr] = info = plan.info()
+        assert info["kept_products"] == len(pqs[0]) and info["semiring"] == sr and info["dtype"] == dtype
+        if which == 2:
+            assert info["rows"][GLOBAL] == 2, info
+        if which == 3:
+            assert info["rows"][WAVE_DIRECT] == A.M, info
+        # the forward, the subgradient and the witness as any input's: both regimes of both
+        sub.check_exact(tool, plan, A, B, nC, pqs, sr, dtype, 700)
+        sub.check_general(tool, plan, A, B, nC, pqs, sr, dtype, 707, what)
+        wit.check_exact(tool, plan, A, B, nC, pqs, sr, dtype, 700)
+        wit.check_general(tool, plan, A, B, nC, pqs, sr, dtype, 707)
+        # a second draw: every repeat of a B entry has the value of the first of its run.  (A B row that exact_values
+        # saw without an infinity has none after the copying either: still no product is Inf - Inf.)
+        av, bv = sub.exact_values(sr, A, B, 720)
+        bv = bv[first_copy]
+        cdev = sub.forward_values(tool, plan, nC, dtype, av, bv)
+        c = cdev.cpu().numpy()
+        assert np.array_equal(c, srf.reference(sr, pqs, av, bv, nC, dtype)) and not np.isnan(c).any(), f"{what}: the forward"
+        win, T = sub.winners(sr, pqs, av, bv, c, dtype)
+        p, q, s = pqs
+        through = win & copied[q]  # the products won through a repeated B entry
+        assert through.any(), "the case needs a winner that is a repeat"
+        g = np.random.default_rng(721).integers(-2, 3, nC).astype(np.float64)
+        G = np.where(T > 0, T * g, np.nan)
+        _, gA, gB, ties = sub.call(tool, plan, A.nnz, B.nnz, nC, dtype, av, bv, G, cval=cdev)
+        wA, wB = sub.exact_reference(sr, pqs, win, T, av, bv, G, A.nnz, B.nnz, dtype)
+        assert np.array_equal(ties, T) and np.array_equal(gA, wA) and np.array_equal(gB, wB), what
+        jb = repeat_pairs(B)
+        won = np.bincount(q[win], minlength=B.nnz)
+        assert np.array_equal(won[jb], won[jb + 1]), "the reference: both copies win or neither does"
+        assert (won[jb] > 0).any() and np.array_equal(gB[jb], gB[jb + 1]), f"{what}: the repeats of a B entry get equal dB"
+        assert np.all(ties[s[through]] >= 2), f"{what}: every duplicate is a product of its own, so a repeat that wins ties"
+        # duplicates share their k: the witness is that of B with every run of repeats collapsed to one entry
+        _, w = wit.call(tool, plan, nC, dtype, av, bv, cval=cdev)
+        merged, _ = wit.witness_reference(sr, A, merged_pqs, av, bv[start], c, dtype)
+        assert np.array_equal(w, merged), f"{what}: wit is the witness of the collapsed B"
+        assert np.array_equal(w >= 0, ties >= 1)
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("sr", srf.SEMIRINGS)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+def test_repeats_semiring_every_class_has_rows(tool, dtype, sr):
+    rows = np.sum([hard_info(tool, key, dtype, sr)["rows"] for key in plain_inputs(DTYPES[dtype], 1)], axis=0)
+    for cls in PRODUCT:
+        assert rows[cls] > 0, f"class {cls} has no rows at {sr} {dtype}"
+    assert rows[DOT] == 0
+
+
+# ------------------------------------------------------------------ smoothed plans ---
+@pytest.mark.parametrize("sr", sm.SEMIRINGS)
+@pytest.mark.parametrize("dtype", list(DTYPES))
+@pytest.mark.parametrize("which", [0, 1, 2, 3], ids=INPUT_IDS)
+def test_repeats_smooth_plan(tool, which, dtype, sr):
+    """The log-sum-exp plans classify at twice the value's bytes, as a width-2 plan: global_rows(13313) is past the
+    block-search cap at both sizes.  Global rows are held to the global bound, the others to the LDS classes'."""
+    key = plain_inputs(DTYPES[dtype], 2)[which]
+    assert key != "global_rows_f32"
+    A, B, Cp, Ci, pqs = semiring_input(key)[:5]
+    nC = len(Ci)
+    what = f"{key} {sr} {dtype}"
+    av, bv = sm.values(A.nnz, 731, dtype), sm.values(B.nnz, 1731, dtype)
+    G = sm.values(nC, 733, dtype, -1.0, 1.0)
+    is_global, nglobal = sm.global_entries(A, B, Cp, Ci, dtype)
+    plan, info = sm.soft_plan(tool, *srf.on_device(tool, A, B, Cp, Ci), sr, dtype)
+    try:
+        assert info["rows"][GLOBAL] == nglobal and info["rows"][DOT] == 0 and info["kept_products"] == len(pqs[0]), info
+        if which == 2:
+            assert nglobal == 2 and is_global.all(), info
+        got = sm.forward(tool, plan, av, bv, nC, dtype)
+        sm.assert_forward(got, sm.soft_reference(sr, pqs, av, bv, nC, dtype), is_global, dtype, what)
+        rA, rB = sm.grad_reference(sr, pqs, av, bv, got, G, A.nnz, B.nnz, dtype)
+        gA, gB = sm.backward(tool, plan, G, got, av, bv, A.nnz, B.nnz, dtype)
+        sm.assert_grad(gA, rA, G, dtype, f"{what} dA")
+        sm.assert_grad(gB, rB, G, dtype, f"{what} dB")
+        again, _ = sm.backward(tool, plan, G, got, av, bv, A.nnz, B.nnz, dtype)
+        assert again.tobytes() == gA.tobytes(), f"{what}: dA has a fixed order, the same bits on two calls"
+    finally:
+        plan.close()
+
+
+@pytest.mark.parametrize("dtype", list(DTYPES))
+def test_repeats_smooth_every_class_has_rows(tool, dtype):
+    rows = np.zeros(8, np.int64)
+    for key in plain_inputs(DTYPES[dtype], 2):
+        A, B, Cp, Ci = semiring_input(key)[:4]
+        plan, info = sm.soft_plan(tool, *srf.on_device(tool, A, B, Cp, Ci), "min_plus", dtype)
+        plan.close()
+        rows += info["rows"]
+    for cls in PRODUCT:
+        assert rows[cls] > 0, f"class {cls} has no rows at lse {dtype}"
 
 
 # ------------------------------------------------------------------ masked plans ---
@@ -200,10 +358,12 @@ CASES["rect"] = rect_twin
 @plans
 @pytest.mark.parametrize("form", ["product", "dot", "auto"])
 @pytest.mark.parametrize("case", ["triangle", "rect"])
-def test_repeats_masked_forms(tool, case, form, dt, W):
+def test_repeats_masked_forms(tool, case, form, dt, W, accum):
     A, B, Mp, Mc, pqs, av, bv = exact_sets(case)[:7]
     assert len(repeat_pairs(A)) > 0 and len(repeat_pairs(B)) > 0
-    info, gC = check_plan(tool, case, dt, W, masked=True, form=form)
+    kw = dict(masked=True, form=form, **plan_keywords(accum))
+    info, gC = check_plan(tool, case, dt, W, **kw)
+    assert info["accum"] == accum, info
     assert 0 < info["kept_products"] < info["products"] == orc.flop(A.col, B.ptr), "the case needs products outside the mask"
     if form == "dot":
         assert info["rows"][DOT] > 0 and info["dot"] > 0, info
@@ -212,13 +372,13 @@ def test_repeats_masked_forms(tool, case, form, dt, W):
     if info["rows"][DOT] > 0:  # dot rows: two calls give the same bits, a batched set has the unbatched call's bits
         nb = W + 1
         dAv, dBv = up(tool, av[:nb], dt), up(tool, bv[:nb], dt)
-        plan, plan1 = make_plan(tool, A, B, Mp, Mc, dt, W, masked=True, form=form), None
+        plan, plan1 = make_plan(tool, A, B, Mp, Mc, dt, W, **kw), None
         try:
             again = nans(tool, (nb, len(Mc)), dt)
             plan.run_batched(dAv, dBv, out=again)
             torch.cuda.synchronize()
             assert np.array_equal(bits(again.cpu().numpy()), bits(gC)), "two batched calls, the same bits"
-            plan1 = make_plan(tool, A, B, Mp, Mc, dt, 1, masked=True, form=form)
+            plan1 = make_plan(tool, A, B, Mp, Mc, dt, 1, **kw)
             assert plan1.info()["dot"] == info["dot"]
             for b in range(nb):
                 o = nans(tool, (len(Mc),), dt)

@@ -32,7 +32,9 @@ from mhspgemm import _lib as L
 from oracle import oracle as orc
 from _util import assert_f64_bound, bin_zoo, device_csr, exact_forward, random_csr, with_hub_row
 import test_gpu_semiring as sr
+import test_gpu_subgrad as sub
 import test_gpu_values_batched as vb
+import test_gpu_witness as wit
 from test_gpu_f64_bound import fresh_tool, masked_case, plain_case, plan_check, reference
 from test_gpu_nonfinite import CALLS  # FULL_CALLS and perturbed_fem_row_chunked
 from test_gpu_parity import test_device_transpose_bit_exact as _transpose_shapes
@@ -392,6 +394,59 @@ def test_poisoned_min_plus_plan(tool, byte):
             assert info == plan.info()
         finally:
             plan.close()
+    finally:
+        t2.close()
+        released(dA, dB, dC)
+
+
+@poisons
+@pytest.mark.parametrize("dtype", ["float64", "float32"])
+@pytest.mark.parametrize("semiring", sr.SEMIRINGS)
+def test_poisoned_semiring_subgrad_and_witness(tool, semiring, dtype, byte):
+    """The subgradient and the witness of a semiring plan created on a poisoned context -- its row lists and counters
+    are allocated under poison, and the pre-fills of ties and wit are all that stands between the kernels and the
+    poison byte -- twice each, a full call on the context ahead of every call after the first.  The exact regime of
+    tests/test_gpu_subgrad.py: ties, dA, dB and wit equal the reference on every call."""
+    A, B, Cp, Ci, pqs = sr.case("bin_zoo")
+    nC = len(Ci)
+    av, bv = sub.exact_values(semiring, A, B, 600)
+    c = sr.reference(semiring, pqs, av, bv, nC, dtype)
+    win, T = sub.winners(semiring, pqs, av, bv, c, dtype)
+    assert (T == 0).any() and (T >= 2).any(), "entries the ties pre-fill alone writes, and entries with ties"
+    g = np.random.default_rng(601).integers(-2, 3, nC).astype(np.float64)
+    G = np.where(T > 0, T * g, np.nan)
+    wA, wB = sub.exact_reference(semiring, pqs, win, T, av, bv, G, A.nnz, B.nnz, dtype)
+    wW, _ = wit.witness_reference(semiring, A, pqs, av, bv, c, dtype)
+    assert (wW == -1).any() and (wW >= 0).any(), "entries the wit pre-fill alone writes, and entries with a witness"
+    t2 = poisoned_tool(tool, byte)
+    dA, dB, dC = sr.on_device(tool, A, B, Cp, Ci)
+    try:
+        plan = mhspgemm.ValuesPlan(t2, dA, dB, dC, dtype=dtype, semiring=semiring)
+        try:
+            info = plan.info()
+            between = full_call_between(t2, dA, dB)
+            cdev = sub.forward_values(t2, plan, nC, dtype, av, bv)
+            assert np.array_equal(cdev.cpu().numpy(), c), "the forward"
+            for k in range(2):
+                for what in ("subgrad", "witness"):
+                    if k or what == "witness":
+                        between()
+                        assert plan.info() == info, "the plan after other work on its context"
+                    if what == "subgrad":
+                        _, gA, gB, ties = sub.call(t2, plan, A.nnz, B.nnz, nC, dtype, av, bv, G, cval=cdev)
+                        assert np.array_equal(ties, T), f"ties, call {k}"
+                        assert np.array_equal(gA, wA) and np.array_equal(gB, wB), f"dA and dB, call {k}"
+                    else:
+                        _, w = wit.call(t2, plan, nC, dtype, av, bv, cval=cdev)
+                        assert np.array_equal(w, wW), f"wit, call {k}"
+            assert t2.stat("poison_fills") > 0
+        finally:
+            plan.close()
+        plain = mhspgemm.ValuesPlan(tool, dA, dB, dC, dtype=dtype, semiring=semiring)
+        try:
+            assert info == plain.info(), "info() is the unpoisoned context's"
+        finally:
+            plain.close()
     finally:
         t2.close()
         released(dA, dB, dC)
